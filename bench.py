@@ -6,17 +6,34 @@ generated in HBM.  One "step" = one full solve (computeEntireTotalCostMap's
 propagation: T initialised, relaxed to convergence, result in HBM).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--obst P]
+                  [--dump-outputs DIR] [--full]
 
 N > 1 runs under torch.distributed.run, one rank per GPU: the grid is cut in
 row slabs, one per rank, with RCCL halo exchange driven from C++
 (include/dymu_dist.h; bench_sharded.py); value is the whole-job rate
 N^2 / max-over-ranks solve time.
 
-Rank 0 prints ONE JSON line with the roofline of the dominant kernel
-(k_fim_pass, per-launch HIP events over the timed region) and the CPU baseline
-(the oracle's heap FMM, same pop order as the reference, one thread, on a
-bounded sample), plus `cpu_reference_algorithm`: the reference's own
-linear-scan narrow band (SURVEY s8(d) cpu_fmm_linear) on a 1024^2 sample.
+Rank 0 prints ONE JSON line with the headline rate, `ms_per_step` and the roofline
+of the dominant kernel (k_fim_pass, per-launch HIP events sampled inside the timed
+region).  A plain run does nothing else: set up, warm up, time the K steps, write
+the outputs if --dump-outputs is given, print the line.
+
+--dump-outputs DIR writes what the last timed step left for its caller, the
+total-cost map, as DIR/total_cost.npy (float64, every value finite: obstacles and
+unreached cells, +inf in the engine's map, are written as -1.0, the way the
+reference's getTotalCostMatrix hands the map out, :799-811): the whole map up to
+32 MiB, else the cells sample_cells() picks (fixed seed, the same cells in every
+run).  The speed map is generated from fixed seeds, so two builds run with
+the same arguments solve the same grid.
+
+--full adds the legs that take runs of their own: the sustained back-to-back
+rate, the exact-sqrt / deterministic variants, the class-surface (planner) leg,
+the CPU baseline (the oracle's heap FMM, same pop order as the reference, one
+thread, on a bounded sample) with the whole-map parity check against it,
+`cpu_reference_algorithm` (the reference's own linear-scan narrow band, SURVEY
+s8(d) cpu_fmm_linear, on a 2048^2 sample) and `cpu_parallel`.  The --no-* /
+--cpu-sample / --sustain-s options trim a --full run.  (The N > 1 and --sharded
+runs keep the self-check of their stitched map, bench_sharded.py, in every run.)
 """
 import argparse
 import json
@@ -50,8 +67,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=16384)
     ap.add_argument("--obst", type=float, default=0.02)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: sustained rate, variants, "
+                         "planner leg, CPU baselines, whole-map parity with the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's total-cost map (a fixed "
+                         "seeded sample of it above 32 MiB; +inf cells as -1.0) to "
+                         "DIR/total_cost.npy")
     ap.add_argument("--cpu-sample", type=int, default=16384,
-                    help="edge of the grid the CPU baseline solves (0 = skip)")
+                    help="--full: edge of the grid the CPU baseline solves (0 = skip)")
     ap.add_argument("--no-profile", action="store_true",
                     help="no per-launch events (roofline reported as null)")
     ap.add_argument("--backend", default="nccl",
@@ -88,7 +112,37 @@ def parse():
     ap.add_argument("--fake-cpu", action="store_true",
                     help="tests only: the N-rank plumbing on CPU (gloo, numpy stand-in engine, "
                          "python exchange loop); no GPU is touched")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure only
+        args.sustain_s = 0.0
+        args.cpu_sample = 0
+        args.no_variants = args.no_parity = args.no_planner = True
+    return args
+
+
+DUMP_MAX_BYTES = 32 << 20  # of float64 per dump (the whole run stays far below 64 MB)
+
+
+def sample_cells(n_cells, max_bytes=DUMP_MAX_BYTES):
+    """Flat indices of the cells --dump-outputs keeps of an n_cells map: all of them
+    when they fit in max_bytes of float64, else max_bytes / 8 distinct cells drawn
+    with a fixed seed (sorted; the same cells for the same n_cells in every run)."""
+    keep = max_bytes // 8
+    if n_cells <= keep:
+        return None
+    idx = np.random.default_rng(20240531).integers(0, n_cells, size=keep, dtype=np.int64)
+    return np.unique(idx)
+
+
+def dump_map(out_dir, name, T, max_bytes=DUMP_MAX_BYTES):
+    """T (2-D float64, host) -> out_dir/name.npy, whole or sample_cells()' cells, with
+    +inf written as -1.0 (getTotalCostMatrix's convention, reference :799-811) so that
+    every stored value is finite."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = sample_cells(T.size, max_bytes)
+    out = T if idx is None else T.reshape(-1)[idx]
+    out = np.where(np.isinf(out), -1.0, out)
+    np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(out, dtype=np.float64))
 
 
 def spawn_ranks(n):
@@ -270,6 +324,11 @@ def run_single(args):
     eng.set_profiling(False)
     T = np.empty(2)
     eng.d2h(T, dT)  # touch the result
+    if args.dump_outputs:  # the last timed solve's map, as its caller finds it in dT
+        T = np.empty((N, N))
+        eng.d2h(T, dT)
+        dump_map(args.dump_outputs, "total_cost", T)
+        del T
     if args.sustain_s > 0:  # untimed for `value`: the same solve back to back
         per = []
         t1 = time.perf_counter()

@@ -289,6 +289,11 @@ def run(args):
     if native:
         for sv in solvers.values():
             sv.close()
+    if getattr(args, "dump_outputs", None):  # this rank's owned rows of the last timed solve
+        import bench
+
+        bench.dump_map(args.dump_outputs, f"total_cost_rank{rank}_row{row0}",
+                       T_buf[1:nrows + 1].cpu().numpy(), bench.DUMP_MAX_BYTES // world)
     tot["parity"] = self_check(eng, F, T_buf, N, row0, nrows, rank, world, g, args.obst, fake,
                                dt.device)
     if not fake:

@@ -137,9 +137,9 @@ def test_bench_gpus2_fixed_transport_self_check(exchange):
 def test_bench_single_gpu_oracle_parity():
     """The single-GPU bench line checks its whole map against the cpu_baseline's
     oracle FMM map of the same grid (bench.oracle_parity) and carries the block."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "1024",
-                          "--cpu-sample", "1024", "--cpu-linear-size", "256", "--steps", "2",
-                          "--warmup", "1", "--no-variants", "--no-planner"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--size",
+                          "1024", "--cpu-sample", "1024", "--cpu-linear-size", "256", "--steps",
+                          "2", "--warmup", "1", "--no-variants", "--no-planner"],
                          env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -147,3 +147,81 @@ def test_bench_single_gpu_oracle_parity():
     assert par["ok"] and par["mismatched_cells"] == 0 and par["max_rel"] <= 1e-12
     assert par["finite_cells"] > 0.9 * 1024 * 1024
     assert rec["cpu_baseline"]["sample"].startswith("1024x1024")
+
+
+def test_bench_dump_outputs_fake_rank_same_map_every_run(oracle, tmp_path):
+    """--dump-outputs on the CPU rehearsal path: the owned rows of the last timed step,
+    float64, the same from run to run (fixed seeds), equal to the oracle FMM's map;
+    --steps is the number of timed steps on the line."""
+    import socket
+
+    n, maps = 64, []
+    for d in ("a", "b"):
+        s = socket.socket()
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+        s.close()
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                              "--fake-cpu", "--size", str(n), "--steps", "3", "--warmup", "1",
+                              "--obst", "0.05", "--dump-outputs", str(tmp_path / d)],
+                             env=_env(MASTER_PORT=str(port)), cwd=ROOT, capture_output=True,
+                             text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-3000:]
+        rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+        assert os.listdir(tmp_path / d) == ["total_cost_rank0_row0.npy"]
+        maps.append(np.load(tmp_path / d / "total_cost_rank0_row0.npy"))
+    assert maps[0].dtype == np.float64 and maps[0].shape == (n, n)
+    assert np.array_equal(maps[0], maps[1])
+    g = (n // 2, n // 2)
+    F = oracle.synth_speed(n, n, seed=1, obst_frac=0.05, obst_seed=3, goal=g)
+    Tref, _ = oracle.fmm(F, g)
+    fin = np.isfinite(Tref)
+    assert np.isfinite(maps[0]).all() and np.array_equal(maps[0] != -1.0, fin)  # +inf -> -1
+    assert (np.abs(maps[0][fin] - Tref[fin]) / np.maximum(1, Tref[fin])).max() <= 1e-12
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1024, 2304])  # the whole map; above the cap: the fixed sample
+def test_bench_plain_run_is_lean_and_dumps_its_map(oracle, tmp_path, n):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` prints the headline fields and
+    none of the --full legs, and --dump-outputs writes the last timed solve's map
+    (or sample_cells()' cells of it), every value finite: -1.0 exactly where the
+    oracle FMM of the same grid has +inf, and <= 1e-12 relative (the project's parity
+    tolerance) elsewhere."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                          "--steps", "3", "--warmup", "1", "--size", str(n), "--dump-outputs",
+                          str(tmp_path)],
+                         env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["n_gpus"] == 1
+    assert rec["unit"] == "Mcells/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+    assert rec["ms_per_step"] > 0
+    assert abs(rec["value"] - n * n / rec["ms_per_step"] / 1e3) <= 1e-3 * rec["value"]
+    assert rec["roofline"] is not None  # sampled inside the timed steps: no run of its own
+    assert rec["cpu_baseline"] is None
+    for leg in ("variants", "sustained", "planner", "parity", "cpu_reference_algorithm",
+                "cpu_parallel"):
+        assert leg not in rec
+    assert os.listdir(tmp_path) == ["total_cost.npy"]
+    T = np.load(tmp_path / "total_cost.npy")
+    assert T.dtype == np.float64 and T.nbytes <= bench.DUMP_MAX_BYTES
+    g = (n // 2, n // 2)
+    F = oracle.synth_speed(n, n, seed=1, obst_frac=0.02, obst_seed=3, goal=g)
+    Tref, _ = oracle.fmm(F, g)
+    idx = bench.sample_cells(n * n)
+    if idx is None:
+        assert T.shape == (n, n)
+    else:
+        assert T.shape == idx.shape
+        Tref = Tref.reshape(-1)[idx]
+    fin = np.isfinite(Tref)
+    assert np.isfinite(T).all()  # the map's +inf cells are stored as -1.0
+    assert 0.9 * T.size < fin.sum() < T.size and np.array_equal(T != -1.0, fin)
+    assert (np.abs(T[fin] - Tref[fin]) / np.maximum(1, Tref[fin])).max() <= 1e-12

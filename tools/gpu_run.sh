@@ -6,7 +6,7 @@
 # Steps:
 #   tests[=PYTEST_ARGS]   pytest -m gpu (default: all of tests/), one process
 #   smoke                 __graft_entry__.smoke()
-#   bench[=ARGS]          python bench.py ARGS (default line)
+#   bench[=ARGS]          python bench.py --full ARGS (the line with every leg)
 #   quick                 bench.py --no-planner --cpu-sample 0 --no-variants --steps 10 --warmup 2
 #   maze=N                tools/maze_bench.py N 64 1
 #   configs               tools/configs.py (config 2 / 5 at 4096^2)
@@ -38,7 +38,7 @@ for step in "$@"; do
            args=(); for w in ${val:-tests}; do args+=("${w//\~/ }"); done
            run tests 1100 python -u -m pytest "${args[@]}" -m gpu -x -v --timeout 300 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python -u bench.py $val ;;
+    bench) run bench 600 python -u bench.py --full $val ;;
     quick) run quick 300 python -u bench.py --no-planner --cpu-sample 0 --no-variants --steps 10 --warmup 2 ;;
     maze) run "maze${val// /_}" 600 python -u tools/maze_bench.py $val 64 1 ;;
     configs) run configs 300 python -u tools/configs.py ;;
