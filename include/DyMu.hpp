@@ -298,6 +298,26 @@ class DyMuPathPlanner {
   // reference's public globalNode::total_cost / state writes).  The next
   // solve starts cold.  No solve runs here.
   bool loadTotalCostMap(const double* T);
+  // Batched path extraction: for each start, the path computeGlobalPath would leave in
+  // current_path (the offset removed on entry and added on exit, as getPath does).
+  // These are GLOBAL paths: getPaths does not run evaluatePath and does not touch
+  // current_path.  While the device map holds what the host copy would show (after a
+  // solve, an early exit, loadTotalCostMap with an engine) the descents run on the GPU,
+  // one lane per path (dymu_extract_paths_device; x, y, z, heading and the counts are
+  // bit-identical to the host loop); otherwise -- after
+  // propagateGlobalNode, resetTotalCostMap, resetGlobalNarrowBand, or without an
+  // engine -- the same host descent runs per start on the host threads.
+  // status (optional, one per start): 1 the sink was appended; 0 the descent stalled
+  // ("ERROR in trajectory": the waypoints so far are kept); -1 the first step is NaN or
+  // the start is off the grid (empty path); -3 more than max_wp waypoints (the first
+  // max_wp kept).  stride >= 1 keeps waypoints 0, stride, 2 stride, ... and the sink.
+  std::vector<std::vector<base::Waypoint>> getPaths(const std::vector<base::Waypoint>& starts,
+                                                    std::vector<int>* status = nullptr,
+                                                    unsigned max_wp = 1u << 20,
+                                                    unsigned stride = 1);
+  // whether the last getPaths ran on the device, and its kernel time (HIP events, ms)
+  bool lastPathsOnDevice() const { return last_paths_device_; }
+  double lastPathsKernelMs() const { return last_paths_kernel_ms_; }
   // local-layer inspection: how many global nodes are subdivided (mask: ny*nx
   // bytes, may be null), and one subdivided node's sub-cells (r*r each,
   // row-major) -- false if (i, j) has no local map
@@ -380,6 +400,20 @@ class DyMuPathPlanner {
   // band_cells_ into the reference's insertion order, if still in grid order
   void orderBand();
   bool safeNode(unsigned i, unsigned j) const;
+  // computeNextGlobalWaypoint / computeGlobalPath without member writes (getPaths'
+  // host threads share them): descend returns getPaths' status
+  base::Waypoint nextWaypoint(base::Waypoint& wPos, double tau) const;
+  int descend(base::Waypoint wPos, std::vector<base::Waypoint>& path, uint64_t max_wp,
+              unsigned stride) const;
+  void pathsOnDevice(const std::vector<base::Waypoint>& starts,
+                     std::vector<std::vector<base::Waypoint>>& out, std::vector<int>& st,
+                     unsigned max_wp, unsigned stride);
+  // dT_ holds what the host mirror would show: set by the solves, the early exit's
+  // scatters and uploads, loadTotalCostMap with an engine; cleared wherever the host
+  // copy is written alone
+  bool dev_map_current_ = false;
+  bool last_paths_device_ = false;
+  double last_paths_kernel_ms_ = 0.0;
   std::optional<globalNode> snapshot(uint64_t k);
   void nominalCost(unsigned i, unsigned j, int range, int num_locs, double cmax);
   // local layer internals (csrc/local_layer.cpp)

@@ -160,6 +160,31 @@ int dymu_region_stats(dymu_ctx* ctx, const double* dF, const double* dT, uint32_
 int dymu_scatter(dymu_ctx* ctx, double* dT, uint32_t nx, uint64_t ld, const uint64_t* idx,
                  const double* vals, uint64_t n, void* stream);
 
+/* ---- batched path extraction (DyMuPathPlanner::getPaths) ----
+ * The reference's gradient descent on T (computeGlobalPath and its helpers,
+ * src/DyMu_GlobalPathPlanning.cpp:615-784), one GPU lane per path.  dT: total cost
+ * (device, pitch ld, as a solve leaves it); res: global_res; (goal_i, goal_j): the sink;
+ * tau: the step in cells (the planner's min(0.4, risk_distance)); d_start_xy: n_paths
+ * (x, y) starts in grid-local metres (device).  Path p writes at most max_wp slots of 4
+ * doubles at d_out + p * max_wp * 4: x, y and the descent direction (dcx, dcy) that
+ * produced the waypoint (0, 0 for the start and the sink) -- heading = atan2(-dcy, -dcx)
+ * and z are the caller's, so that they are the host libm's and the host's elevation.  x,
+ * y and the counts are bit-identical to the host loop on the same T.  stride >= 1 keeps
+ * waypoints 0, stride, 2 stride, ... and always the sink.  d_count[p] = slots written;
+ * d_status[p] = 1 sink appended; 0 stalled ("ERROR in trajectory": the waypoints so far
+ * are kept); -1 the first step is NaN or off the grid (nothing written); -3 max_wp
+ * reached (the first max_wp kept).  A lane stops after max_wp * stride steps, and a
+ * coordinate off the grid (negative, huge, NaN) ends its path before any load.
+ * Asynchronous on `stream` (NULL: the context's stream). */
+int dymu_extract_paths_device(dymu_ctx* ctx, const double* dT, uint32_t nx, uint32_t ny,
+                              uint64_t ld, double res, uint32_t goal_i, uint32_t goal_j,
+                              double tau, const double* d_start_xy, uint32_t n_paths,
+                              uint32_t max_wp, uint32_t stride, double* d_out, int32_t* d_count,
+                              int32_t* d_status, void* stream);
+/* Device time (ms, HIP events) of the last dymu_extract_paths_device kernel; waits for
+ * it.  DYMU_ERR_STATE before the first one. */
+int dymu_last_paths_ms(dymu_ctx* ctx, double* ms);
+
 /* ---- row-slab domains (multi-GPU sharding; also single-GPU virtual slabs) ----
  * A rank owns rows [row0, row0+nrows) of an nx-wide global grid.  T points at
  * its first owned row; with ghost_lo the row above it (T - ld) holds the

@@ -60,6 +60,24 @@ int dymu_planner_get_total_cost(dymu_planner* p, double x, double y, double z, d
  * the number of waypoints (>= 0) or a negative status */
 int dymu_planner_get_path(dymu_planner* p, double x, double y, double z, double heading,
                           double* out_xyzh, int max_wp);
+/* getPaths (extension, DyMu.hpp): the global path of each of n starts (starts_xyzh: n x
+ * (x, y, z, heading)) on the current total-cost map -- on the GPU next to the map while
+ * the device copy is current, else by the host descent per start.  No evaluatePath, and
+ * current_path is not touched.  counts[q] (may be NULL) = waypoints of path q, at most
+ * max_wp; status[q] (may be NULL) = 1 sink appended, 0 stalled ("ERROR in trajectory",
+ * the waypoints so far kept), -1 first step NaN / start off the grid (empty), -3 more
+ * than max_wp waypoints (the first max_wp kept).  stride >= 1 keeps waypoints 0, stride,
+ * 2 stride, ... and the sink.  out_xyzh receives the paths PACKED one after another
+ * (sum of counts waypoints; n * max_wp in the worst case).  As the sizes are not known
+ * before the call, out_xyzh may be NULL: the result is then kept in the handle, and a
+ * second call with starts_xyzh = NULL and the same n copies it into out_xyzh (sized
+ * from the first call's counts) and drops it.  Returns n or a negative status. */
+int dymu_planner_get_paths(dymu_planner* p, const double* starts_xyzh, int n, int max_wp,
+                           int stride, double* out_xyzh, int* counts, int* status);
+/* 1 if the last dymu_planner_get_paths ran on the device, 0 on the host threads */
+int dymu_planner_last_paths_on_device(dymu_planner* p);
+/* its kernel time (HIP events, ms; 0 on the host route) */
+int dymu_planner_last_paths_kernel_ms(dymu_planner* p, double* ms);
 /* getLocomotionMode (:788-795) into buf (NUL-terminated) */
 int dymu_planner_get_locomotion_mode(dymu_planner* p, double x, double y, double z, double heading,
                                      char* buf, int buflen);

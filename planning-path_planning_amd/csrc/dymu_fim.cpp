@@ -28,6 +28,8 @@ struct dymu_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev_path0 = nullptr, ev_path1 = nullptr;  // around the last k_extract_paths
+  bool path_timed = false;
   dymu_opts opts{};
   int cu_count = 256;
   uint32_t* d_xchg = nullptr;  // k_exchange's block ticket (zero between launches)
@@ -1234,6 +1236,8 @@ int dymu_destroy(dymu_ctx* c) {
   for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
+  if (c->ev_path0) (void)hipEventDestroy(c->ev_path0);
+  if (c->ev_path1) (void)hipEventDestroy(c->ev_path1);
   if (c->d_lists) (void)hipFree(c->d_lists);
   if (c->d_tile_epoch) (void)hipFree(c->d_tile_epoch);
   if (c->d_counts) (void)hipFree(c->d_counts);
@@ -1414,6 +1418,58 @@ int dymu_scatter(dymu_ctx* c, double* dT, uint32_t nx, uint64_t ld, const uint64
   const double* dv = reinterpret_cast<const double*>(di + n);
   HIPC(c, launch_scatter(dT, (int64_t)ld, nx, di, dv, n, st));
   HIPC(c, hipStreamSynchronize(st));
+  return DYMU_OK;
+}
+
+int dymu_extract_paths_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
+                              double res, uint32_t gi, uint32_t gj, double tau,
+                              const double* d_start_xy, uint32_t n_paths, uint32_t max_wp,
+                              uint32_t stride, double* d_out, int32_t* d_count, int32_t* d_status,
+                              void* stream) {
+  if (!c || !dT || nx == 0 || ny == 0 || ld < nx || gi >= nx || gj >= ny) return DYMU_ERR_ARG;
+  if (!(res > 0) || !(res < HUGE_VAL) || !(tau > 0) || !(tau < HUGE_VAL)) return DYMU_ERR_ARG;
+  if (max_wp == 0 || max_wp > 0x7fffffffu || stride == 0) return DYMU_ERR_ARG;
+  if (n_paths && (!d_start_xy || !d_out || !d_count || !d_status)) return DYMU_ERR_ARG;
+  if (n_paths == 0) return DYMU_OK;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  if (!c->ev_path0) HIPC(c, hipEventCreate(&c->ev_path0));
+  if (!c->ev_path1) HIPC(c, hipEventCreate(&c->ev_path1));
+  PathArgs a{};
+  a.T = dT;
+  a.ld = (int64_t)ld;
+  a.nx = nx;
+  a.ny = ny;
+  a.res = res;
+  // the host's expressions (planner.cpp computeGlobalPath / computeNextGlobalWaypoint)
+  a.res_tau = res * tau;
+  a.two_res = 2.0 * res;
+  a.stall = 0.01 * tau * res;
+  a.sink_x = res * (double)gi;
+  a.sink_y = res * (double)gj;
+  a.start_xy = d_start_xy;
+  a.n_paths = n_paths;
+  a.max_wp = max_wp;
+  a.stride = stride;
+  a.out = d_out;
+  a.count = d_count;
+  a.status = d_status;
+  c->path_timed = false;
+  HIPC(c, hipEventRecord(c->ev_path0, st));
+  HIPC(c, launch_extract_paths(a, st));
+  HIPC(c, hipEventRecord(c->ev_path1, st));
+  c->path_timed = true;
+  return DYMU_OK;
+}
+
+int dymu_last_paths_ms(dymu_ctx* c, double* ms) {
+  if (!c || !ms) return DYMU_ERR_ARG;
+  if (!c->path_timed) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipEventSynchronize(c->ev_path1));
+  float f = 0.0f;
+  HIPC(c, hipEventElapsedTime(&f, c->ev_path0, c->ev_path1));
+  *ms = (double)f;
   return DYMU_OK;
 }
 

@@ -299,6 +299,25 @@ hipError_t launch_store_u64(unsigned long long* p, unsigned long long v, hipStre
 hipError_t launch_scatter(double* T, int64_t ld, uint32_t nx, const uint64_t* idx,
                           const double* vals, uint64_t n, hipStream_t st);
 
+// batched path extraction (path_kernels.hip): one lane per path runs the reference's
+// gradient descent on T from start_xy[p] (grid-local metres) towards the sink
+struct PathArgs {
+  const double* T;  // total cost, pitch ld
+  int64_t ld;
+  uint32_t nx, ny;
+  double res;              // global_res
+  double res_tau;          // res * tau: the step length
+  double two_res;          // 2 * res: within this of the sink the descent ends
+  double stall;            // 0.01 * tau * res: a shorter step is "ERROR in trajectory"
+  double sink_x, sink_y;   // res * goal_i, res * goal_j
+  const double* start_xy;  // n_paths x 2
+  uint32_t n_paths, max_wp, stride;
+  double* out;      // [path][slot][4]: x, y and the (dcx, dcy) that produced the waypoint
+  int32_t* count;   // slots written per path
+  int32_t* status;  // 1 sink appended, 0 stalled, -1 first step NaN / off the grid, -3 max_wp
+};
+hipError_t launch_extract_paths(const PathArgs& a, hipStream_t st);
+
 hipError_t launch_prio_init(const double* F, int64_t ld, int64_t nx, int64_t ny,
                            unsigned long long* keys, uint64_t nkeys, uint32_t* hist, uint64_t nhist,
                            unsigned long long* minkey, double* base, double* delta, double kappa,

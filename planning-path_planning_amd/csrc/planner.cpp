@@ -68,6 +68,7 @@ void DyMuPathPlanner::setEngineOptions(const dymu_opts& o) {
   // device buffers go, so T(), getPath and the matrix getters keep working
   if (ctx_ && dT_ && blk_missing_) fetchAll();
   release_engine(ctx_, dF_, dT_, registered_, dcells_);
+  dev_map_current_ = false;
   solved_ = false;
   speed_valid_ = false;
   markDirty(0, ny_);
@@ -109,6 +110,7 @@ bool DyMuPathPlanner::initGlobalLayer(double globalres, double localres, unsigne
   // a new grid: new device buffers and an empty total-cost map (every node
   // OPEN at +inf, as the globalNode constructor leaves it)
   release_engine(ctx_, dF_, dT_, registered_, dcells_);
+  dev_map_current_ = false;
   total_cost_.assign(n, kInf);
   nbx_ = (nx_ + kBlk - 1) / kBlk;
   nby_ = (ny_ + kBlk - 1) / kBlk;
@@ -513,6 +515,7 @@ void DyMuPathPlanner::ensureEngine() {
     if (dT_) (void)dymu_device_free(ctx_, dT_);
     dF_ = dT_ = nullptr;
     dcells_ = 0;
+    dev_map_current_ = false;
     void *f = nullptr, *t = nullptr;
     if (dymu_device_alloc(ctx_, sizeof(double) * n, &f) != DYMU_OK ||
         dymu_device_alloc(ctx_, sizeof(double) * n, &t) != DYMU_OK) {
@@ -723,6 +726,7 @@ bool DyMuPathPlanner::propagate(bool early, unsigned si, unsigned sj) {
     }
   }
   double t_closed = kInf;
+  dev_map_current_ = false;  // until the engine call below succeeds
   if (rc != DYMU_OK) {
     solved_ = false;
     rc = early ? dymu_solve_until_device(ctx_, dF_, dT_, nx_, ny_, nx_, goal_i_, goal_j_, si, sj,
@@ -734,7 +738,9 @@ bool DyMuPathPlanner::propagate(bool early, unsigned si, unsigned sj) {
                                dymu_last_error(ctx_));
     incremental_ = 0;
   }
-  // the host mirror is stale; node states and the propagated list follow the new map
+  // the host mirror is stale (its blocks are fetched from dT_ on first read); node
+  // states and the propagated list follow the new map
+  dev_map_current_ = true;
   std::fill(blk_ok_.begin(), blk_ok_.end(), 0);
   blk_missing_ = blk_ok_.size();
   band_cells_.clear();
@@ -1410,6 +1416,7 @@ bool DyMuPathPlanner::exactEarlyExit(unsigned si, unsigned sj, const int64_t box
   if (dymu_memcpy_h2d(ctx_, dT_, total_cost_.data(), sizeof(double) * n) != DYMU_OK)
     throw std::runtime_error(std::string("dymu: total-cost upload failed: ") +
                              dymu_last_error(ctx_));
+  dev_map_current_ = true;
   band_cells_.clear();
   band_unordered_ = false;
   band_values_checked_ = true;
@@ -1653,57 +1660,98 @@ std::vector<base::Waypoint> DyMuPathPlanner::getPath(base::Waypoint wPos) {
 bool DyMuPathPlanner::computeGlobalPath(base::Waypoint wPos) {
   current_path.clear();
   if (!has_goal_) return false;
+  const int st = descend(wPos, current_path, std::numeric_limits<uint64_t>::max(), 1);
+  if (st == -1) log_error("PLANNER: Gradient Descent Method failed");
+  if (st == 0) log_error("ERROR in trajectory");
+  return st == 1;
+}
+
+// The loop of computeGlobalPath into `path`, without member writes.  Returns getPaths'
+// status: 1 sink appended, 0 "ERROR in trajectory" (the waypoints so far kept), -1 the
+// first step is NaN (empty path), -3 more than max_wp waypoints (the first max_wp
+// kept).  Waypoint w of the reference's path is kept when w % stride == 0, the sink
+// always; the loop runs at most max_wp * stride steps (k_extract_paths' bound).
+int DyMuPathPlanner::descend(base::Waypoint wPos, std::vector<base::Waypoint>& path,
+                             uint64_t max_wp, unsigned stride) const {
+  path.clear();
+  if (!has_goal_) return -1;
+  const uint64_t limit = max_wp > std::numeric_limits<uint64_t>::max() / stride
+                             ? std::numeric_limits<uint64_t>::max()
+                             : max_wp * stride;
   base::Waypoint sink;
   sink.position[0] = global_res_ * (double)goal_i_;
   sink.position[1] = global_res_ * (double)goal_j_;
   sink.position[2] = elevation_.empty() ? 0.0 : elevation_[idx(goal_i_, goal_j_)];
   sink.heading = goal_heading_;
   const double tau = std::min(0.4, risk_distance_);
-  base::Waypoint wNext = computeNextGlobalWaypoint(wPos, tau);
-  if (std::isnan(wNext.position[0]) || std::isnan(wNext.position[1])) {
-    log_error("PLANNER: Gradient Descent Method failed");
-    return false;
-  }
-  current_path.push_back(wPos);
+  base::Waypoint wNext = nextWaypoint(wPos, tau);
+  if (std::isnan(wNext.position[0]) || std::isnan(wNext.position[1])) return -1;
+  unsigned phase = 0;
+  auto push = [&](const base::Waypoint& w) {
+    if (phase == 0) path.push_back(w);
+    if (++phase == stride) phase = 0;
+  };
+  push(wPos);
   wPos = wNext;
   auto dist = [](const base::Waypoint& a, const base::Waypoint& b) {
     const double dx = a.position[0] - b.position[0], dy = a.position[1] - b.position[1];
     return std::sqrt(dx * dx + dy * dy);
   };
-  while (dist(wPos, sink) > 2.0 * global_res_) {
-    wNext = computeNextGlobalWaypoint(wPos, tau);
-    current_path.push_back(wPos);
-    if (dist(wPos, wNext) < 0.01 * tau * global_res_) {
-      log_error("ERROR in trajectory");
-      return false;
-    }
+  for (uint64_t w = 1; dist(wPos, sink) > 2.0 * global_res_; ++w) {
+    if (w == limit) return -3;
+    wNext = nextWaypoint(wPos, tau);
+    push(wPos);
+    if (dist(wPos, wNext) < 0.01 * tau * global_res_) return 0;
     wPos = wNext;
   }
-  current_path.push_back(sink);
+  if (path.size() >= max_wp) return -3;
+  path.push_back(sink);
+  return 1;
+}
+
+namespace {
+// The cell of grid coordinate g on an axis of n nodes: the reference's (uint) cast of
+// an in-range value (grid_u32), tested in 64-bit so that nothing wraps; false when the
+// cell or its +1 neighbour is off the grid -- negative (below -1), huge and NaN
+// coordinates included.  k_extract_paths (path_kernels.hip) makes the same test.
+bool path_cell(double g, unsigned n, unsigned& c) {
+  if (!(g > -9.2e18 && g < 9.2e18)) return false;
+  const int64_t t = (int64_t)g;
+  if (t < 0 || t + 1 >= (int64_t)n) return false;
+  c = (unsigned)t;
   return true;
 }
+// :776-784 (interpolate)
+double bilinear(double a, double b, double g00, double g01, double g10, double g11) {
+  return g00 + (g10 - g00) * a + (g01 - g00) * b + (g11 + g00 - g10 - g01) * a * b;
+}
+}  // namespace
 
 // :666-714 (wPos.position[2] is written: elevation, bilinear, with the
 // reference's argument order at :699-704)
 base::Waypoint DyMuPathPlanner::computeNextGlobalWaypoint(base::Waypoint& wPos, double tau) {
+  return nextWaypoint(wPos, tau);
+}
+
+base::Waypoint DyMuPathPlanner::nextWaypoint(base::Waypoint& wPos, double tau) const {
   base::Waypoint wNext;
   const double gx = wPos.position[0] / global_res_, gy = wPos.position[1] / global_res_;
-  const unsigned cx = grid_u32(gx), cy = grid_u32(gy);
-  const double ax = gx - (double)cx, ay = gy - (double)cy;
-  if (cx + 1 >= nx_ || cy + 1 >= ny_) {  // reference: NULL dereference
+  unsigned cx = 0, cy = 0;
+  if (!path_cell(gx, nx_, cx) || !path_cell(gy, ny_, cy)) {  // reference: NULL dereference
     wNext.position[0] = wNext.position[1] = std::numeric_limits<double>::quiet_NaN();
     return wNext;
   }
+  const double ax = gx - (double)cx, ay = gy - (double)cy;
   double gx00, gx10, gx01, gx11, gy00, gy10, gy01, gy11;
   gradientNode(cx, cy, gx00, gy00);
   gradientNode(cx + 1, cy, gx10, gy10);
   gradientNode(cx, cy + 1, gx01, gy01);
   gradientNode(cx + 1, cy + 1, gx11, gy11);
-  const double dcx = interpolate(ax, ay, gx00, gx01, gx10, gx11);
-  const double dcy = interpolate(ax, ay, gy00, gy01, gy10, gy11);
+  const double dcx = bilinear(ax, ay, gx00, gx01, gx10, gx11);
+  const double dcy = bilinear(ax, ay, gy00, gy01, gy10, gy11);
   const uint64_t k = idx(cx, cy);
   wPos.position[2] =
-      interpolate(ax, ay, elevation_[k], elevation_[k + 1], elevation_[k + nx_],
+      bilinear(ax, ay, elevation_[k], elevation_[k + 1], elevation_[k + nx_],
                   elevation_[k + nx_ + 1]);
   wNext.position[0] = wPos.position[0] - global_res_ * tau * dcx;
   wNext.position[1] = wPos.position[1] - global_res_ * tau * dcy;
@@ -1748,7 +1796,215 @@ void DyMuPathPlanner::gradientNode(unsigned i, unsigned j, double& dnx, double& 
 // :776-784
 double DyMuPathPlanner::interpolate(double a, double b, double g00, double g01, double g10,
                                     double g11) {
-  return g00 + (g10 - g00) * a + (g01 - g00) * b + (g11 + g00 - g10 - g01) * a * b;
+  return bilinear(a, b, g00, g01, g10, g11);
+}
+
+// ---- getPaths: batched path extraction (extension) ----
+
+// The planner runs over any implementation of the engine C-ABI (tests/hostengine is a
+// host one).  One that predates the path entries leaves these two references null,
+// and getPaths then takes its host route (lastPathsOnDevice() says which ran);
+// libdymu_fim.so always has them.
+#pragma weak dymu_extract_paths_device
+#pragma weak dymu_last_paths_ms
+
+std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getPaths(
+    const std::vector<base::Waypoint>& starts, std::vector<int>* status, unsigned max_wp,
+    unsigned stride) {
+  if (max_wp == 0 || stride == 0) throw std::invalid_argument("getPaths: max_wp, stride >= 1");
+  const size_t n = starts.size();
+  std::vector<std::vector<base::Waypoint>> out(n);
+  std::vector<int> st(n, -1);
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  if (n && has_goal_) {
+    if (ctx_ && dT_ && dev_map_current_ && n <= 0xffffffffull && &dymu_extract_paths_device &&
+        &dymu_last_paths_ms) {
+      pathsOnDevice(starts, out, st, max_wp, stride);
+      last_paths_device_ = true;
+    } else {
+      // the host descent per start (T() is thread-safe; descend writes no member)
+      const unsigned nt = (unsigned)std::min<size_t>(host_threads(), n);
+      std::atomic<size_t> next{0};
+      parallel_tasks(nt, [&](unsigned) {
+        for (size_t q = next++; q < n; q = next++) {
+          base::Waypoint w = starts[q];
+          w.position[0] -= global_offset_[0];
+          w.position[1] -= global_offset_[1];
+          st[q] = descend(w, out[q], max_wp, stride);
+          for (auto& p : out[q]) {
+            p.position[0] += global_offset_[0];
+            p.position[1] += global_offset_[1];
+          }
+        }
+      });
+    }
+  }
+  if (status) status->swap(st);
+  return out;
+}
+
+namespace {
+// device buffers of one getPaths call, freed on every path out of it
+struct DeviceScratch {
+  dymu_ctx* ctx;
+  std::vector<void*> ptrs;
+  explicit DeviceScratch(dymu_ctx* c) : ctx(c) {}
+  ~DeviceScratch() {
+    for (void* p : ptrs) (void)dymu_device_free(ctx, p);
+  }
+  template <class P>
+  P* alloc(uint64_t count) {
+    void* p = nullptr;
+    if (dymu_device_alloc(ctx, sizeof(P) * std::max<uint64_t>(count, 1), &p) != DYMU_OK)
+      throw std::runtime_error(std::string("dymu: getPaths device allocation failed: ") +
+                               dymu_last_error(ctx));
+    ptrs.push_back(p);
+    return static_cast<P*>(p);
+  }
+  void release(void* p) {
+    ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end());
+    (void)dymu_device_free(ctx, p);
+  }
+};
+}  // namespace
+
+// The device route: upload the starts, k_extract_paths, download the counts and
+// statuses, then the waypoints written (runs of paths by pitched copies); z and the
+// heading on the host threads.  The kernel's output has one fixed number of slots per path, and a caller's
+// max_wp (2^20 by default) times thousands of paths is more memory than a path needs:
+// the paths run in batches with a slot capacity sized from the grid, and those that
+// overflow it (status -3 below max_wp) run again with four times the capacity.
+void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
+                                    std::vector<std::vector<base::Waypoint>>& out,
+                                    std::vector<int>& st, unsigned max_wp, unsigned stride) {
+  constexpr uint64_t kOutBytes = 4ull << 30;  // device output of one batch, at most
+  const size_t n = starts.size();
+  const double tau = std::min(0.4, risk_distance_);
+  auto check = [&](int rc, const char* what) {
+    if (rc != DYMU_OK)
+      throw std::runtime_error(std::string("dymu: getPaths ") + what + " failed: " +
+                               dymu_strerror(rc) + " " + dymu_last_error(ctx_));
+  };
+  base::Waypoint sink;
+  sink.position[0] = global_res_ * (double)goal_i_ + global_offset_[0];
+  sink.position[1] = global_res_ * (double)goal_j_ + global_offset_[1];
+  sink.position[2] = elevation_[idx(goal_i_, goal_j_)];
+  sink.heading = goal_heading_;
+  // a straight descent across the grid is (nx + ny) / tau waypoints at most
+  uint64_t cap = std::max<uint64_t>(1024, 4 * ((uint64_t)nx_ + ny_) / stride);
+  cap = std::min<uint64_t>(cap, max_wp);
+  std::vector<uint32_t> pending(n), again;
+  for (size_t q = 0; q < n; ++q) pending[q] = (uint32_t)q;
+  std::vector<double> xy, raw;
+  std::vector<int32_t> cnt, sts;
+  std::vector<uint64_t> off, len;  // per path: its row in `raw` (waypoints), its count
+  struct Run {
+    uint32_t q0, n;
+    uint64_t width, base;
+  };
+  std::vector<Run> runs;
+  DeviceScratch dev(ctx_);
+  while (!pending.empty()) {
+    const uint64_t per_batch = std::max<uint64_t>(1, kOutBytes / (32 * cap));
+    again.clear();
+    for (size_t b0 = 0; b0 < pending.size(); b0 += per_batch) {
+      const uint32_t m = (uint32_t)std::min<uint64_t>(per_batch, pending.size() - b0);
+      const uint32_t* ids = &pending[b0];
+      xy.resize(2 * (size_t)m);
+      for (uint32_t q = 0; q < m; ++q) {
+        xy[2 * q] = starts[ids[q]].position[0] - global_offset_[0];
+        xy[2 * q + 1] = starts[ids[q]].position[1] - global_offset_[1];
+      }
+      double* d_xy = dev.alloc<double>(2 * (uint64_t)m);
+      int32_t* d_cnt = dev.alloc<int32_t>(m);
+      int32_t* d_st = dev.alloc<int32_t>(m);
+      double* d_out = dev.alloc<double>(4 * cap * m);
+      check(dymu_memcpy_h2d(ctx_, d_xy, xy.data(), sizeof(double) * xy.size()), "upload");
+      check(dymu_extract_paths_device(ctx_, dT_, nx_, ny_, nx_, global_res_, goal_i_, goal_j_, tau,
+                                      d_xy, m, (uint32_t)cap, stride, d_out, d_cnt, d_st, nullptr),
+            "kernel");
+      cnt.resize(m);
+      sts.resize(m);
+      check(dymu_memcpy_d2h(ctx_, cnt.data(), d_cnt, sizeof(int32_t) * m), "download");
+      check(dymu_memcpy_d2h(ctx_, sts.data(), d_st, sizeof(int32_t) * m), "download");
+      double ms = 0.0;
+      if (dymu_last_paths_ms(ctx_, &ms) == DYMU_OK) last_paths_kernel_ms_ += ms;
+      // the waypoints: runs of consecutive paths, each downloaded by one pitched copy
+      // as wide as its longest path -- a run grows while that moves at most twice its
+      // waypoints (plus 1024), so few commands move little more than the counts
+      len.assign(m, 0);
+      off.assign(m, 0);
+      for (uint32_t q = 0; q < m; ++q) {
+        const bool rerun = sts[q] == -3 && cap < max_wp;
+        len[q] = rerun ? 0 : (uint64_t)std::max(cnt[q], 0);
+        if (rerun) again.push_back(ids[q]);
+      }
+      runs.clear();
+      uint64_t total = 0;
+      for (uint32_t q0 = 0; q0 < m;) {
+        uint64_t width = len[q0], sum = len[q0];
+        uint32_t q1 = q0 + 1;
+        for (; q1 < m; ++q1) {
+          const uint64_t w2 = std::max(width, len[q1]), s2 = sum + len[q1];
+          if (w2 * (q1 + 1 - q0) > 2 * s2 + 1024) break;
+          width = w2;
+          sum = s2;
+        }
+        for (uint32_t q = q0; q < q1; ++q) off[q] = total + (uint64_t)(q - q0) * width;
+        runs.push_back({q0, q1 - q0, width, total});
+        total += width * (q1 - q0);
+        q0 = q1;
+      }
+      raw.resize(4 * total);
+      for (const Run& r : runs)
+        if (r.width)
+          check(dymu_memcpy2d_d2h(ctx_, &raw[4 * r.base], 32 * r.width, d_out + 4 * cap * r.q0,
+                                  32 * cap, 32 * r.width, r.n),
+                "download");
+      for (void* p : {(void*)d_xy, (void*)d_cnt, (void*)d_st, (void*)d_out}) dev.release(p);
+      // host post-pass: z from the elevation with the host's interpolate call and its
+      // argument order (nextWaypoint), heading = atan2(-dcy, -dcx) with the host libm
+      const unsigned nt = std::min<unsigned>(host_threads(), m);
+      std::atomic<uint32_t> next{0};
+      parallel_tasks(nt, [&](unsigned) {
+        for (uint32_t q = next++; q < m; q = next++) {
+          const uint32_t id = ids[q];
+          st[id] = sts[q];
+          if (sts[q] == -3 && cap < max_wp) continue;
+          const uint64_t c = len[q];
+          const double* r = raw.data() + 4 * off[q];
+          std::vector<base::Waypoint>& path = out[id];
+          path.assign(c, base::Waypoint());
+          for (uint64_t k = 0; k < c; ++k, r += 4) {
+            base::Waypoint& w = path[k];
+            if (sts[q] == 1 && k + 1 == c) {
+              w = sink;
+              continue;
+            }
+            if (k == 0) w = starts[id];
+            else w.heading = std::atan2(-r[3], -r[2]);
+            w.position[0] = r[0];
+            w.position[1] = r[1];
+            const double gx = r[0] / global_res_, gy = r[1] / global_res_;
+            unsigned cx = 0, cy = 0;
+            if (path_cell(gx, nx_, cx) && path_cell(gy, ny_, cy)) {
+              const double ax = gx - (double)cx, ay = gy - (double)cy;
+              const uint64_t e = idx(cx, cy);
+              w.position[2] = bilinear(ax, ay, elevation_[e], elevation_[e + 1],
+                                       elevation_[e + nx_], elevation_[e + nx_ + 1]);
+            } else if (k > 0) {
+              w.position[2] = 0.0;  // nextWaypoint left the default waypoint's z
+            }
+            w.position[0] += global_offset_[0];
+            w.position[1] += global_offset_[1];
+          }
+        }
+      });
+    }
+    pending.swap(again);
+    cap = std::min<uint64_t>(cap * 4, max_wp);
+  }
 }
 
 // :788-795
@@ -1903,6 +2159,7 @@ void DyMuPathPlanner::resetTotalCostMap() {
   propagated_extra_.clear();
   manual_list_ = true;
   solved_ = false;
+  dev_map_current_ = false;  // the host copy alone was written
 }
 
 // the node states of the last solve made explicit, so a caller can change some
@@ -1959,6 +2216,7 @@ void DyMuPathPlanner::propagateGlobalNode(unsigned i, unsigned j) {
     }
     total_cost_[k] = Tn;
     solved_ = false;  // the device map no longer matches the host's
+    dev_map_current_ = false;
   }
 }
 
@@ -2063,6 +2321,7 @@ void DyMuPathPlanner::resetGlobalNarrowBand() {
   const uint64_t k = idx(goal_i_, goal_j_);
   (void)T(k);  // the goal's block in the host mirror before the write
   total_cost_[k] = 0.0;
+  dev_map_current_ = false;  // written on the host alone
   band_cells_.push_back(k);
   propagated_extra_.push_back(k);  // global_propagated_nodes.push_back(global_goal)
 }
@@ -2082,10 +2341,13 @@ bool DyMuPathPlanner::loadTotalCostMap(const double* Tin) {
   propagated_extra_.clear();
   manual_list_ = false;
   solved_ = false;
-  if (ctx_ && dT_ && dcells_ == n &&
-      dymu_memcpy_h2d(ctx_, dT_, total_cost_.data(), sizeof(double) * n) != DYMU_OK)
-    throw std::runtime_error(std::string("dymu: total-cost upload failed: ") +
-                             dymu_last_error(ctx_));
+  dev_map_current_ = false;
+  if (ctx_ && dT_ && dcells_ == n) {
+    if (dymu_memcpy_h2d(ctx_, dT_, total_cost_.data(), sizeof(double) * n) != DYMU_OK)
+      throw std::runtime_error(std::string("dymu: total-cost upload failed: ") +
+                               dymu_last_error(ctx_));
+    dev_map_current_ = true;
+  }
   return true;
 }
 

@@ -18,6 +18,9 @@ using PathPlanning_lib::OPEN;
 
 struct dymu_planner {
   DyMuPathPlanner pl;
+  // the last dymu_planner_get_paths result, kept until it is copied out
+  std::vector<std::vector<base::Waypoint>> paths;
+  std::vector<int> paths_status;
   dymu_planner(double a, double b, double c, PathPlanning_lib::repairingAproach r)
       : pl(a, b, c, r) {}
 };
@@ -401,6 +404,43 @@ int put_path(const std::vector<base::Waypoint>& path, double* out, int max_wp) {
 int dymu_planner_get_current_path(dymu_planner* p, double* out, int max_wp) {
   if (!p || !out || max_wp < 0) return DYMU_ERR_ARG;
   return put_path(p->pl.current_path, out, max_wp);
+}
+
+int dymu_planner_get_paths(dymu_planner* p, const double* starts, int n, int max_wp, int stride,
+                           double* out, int* counts, int* status) {
+  if (!p || n < 0) return DYMU_ERR_ARG;
+  if (starts && (max_wp <= 0 || stride <= 0)) return DYMU_ERR_ARG;
+  if (!starts && (!out || (size_t)n != p->paths.size())) return DYMU_ERR_ARG;
+  return guarded([&] {
+    if (starts) {
+      std::vector<base::Waypoint> s((size_t)n);
+      for (int q = 0; q < n; ++q)
+        s[q] = wp(starts[4 * q], starts[4 * q + 1], starts[4 * q + 2], starts[4 * q + 3]);
+      p->paths = p->pl.getPaths(s, &p->paths_status, (unsigned)max_wp, (unsigned)stride);
+    }
+    for (int q = 0; q < n; ++q) {
+      if (counts) counts[q] = (int)p->paths[q].size();
+      if (status) status[q] = p->paths_status[q];
+    }
+    if (out) {
+      for (const auto& path : p->paths) out += 4 * put_path(path, out, (int)path.size());
+      p->paths.clear();
+      p->paths.shrink_to_fit();
+      p->paths_status.clear();
+    }
+    return n;
+  });
+}
+
+int dymu_planner_last_paths_on_device(dymu_planner* p) {
+  if (!p) return DYMU_ERR_ARG;
+  return p->pl.lastPathsOnDevice() ? 1 : 0;
+}
+
+int dymu_planner_last_paths_kernel_ms(dymu_planner* p, double* ms) {
+  if (!p || !ms) return DYMU_ERR_ARG;
+  *ms = p->pl.lastPathsKernelMs();
+  return DYMU_OK;
 }
 
 int dymu_planner_compute_local_planning(dymu_planner* p, double x, double y, double z, double h,

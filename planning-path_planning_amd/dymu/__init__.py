@@ -163,6 +163,10 @@ FIM_SYMBOLS = {
     "dymu_region_stats": (_i32, [_vp, _vp, _vp, _u32, _u32, _u64, _u32, _u32, ctypes.c_double,
                                  ctypes.c_double, ctypes.c_double, ctypes.POINTER(DymuRegion),
                                  _vp]),
+    "dymu_extract_paths_device": (_i32, [_vp, _vp, _u32, _u32, _u64, ctypes.c_double, _u32, _u32,
+                                         ctypes.c_double, _vp, _u32, _u32, _u32, _vp, _vp, _vp,
+                                         _vp]),
+    "dymu_last_paths_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "dymu_memcpy2d_d2h": (_i32, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
                                  ctypes.c_size_t, ctypes.c_size_t]),
     "dymu_memcpy2d_h2d": (_i32, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
@@ -345,6 +349,43 @@ class Engine:
                                            hi, ctypes.byref(r), None), self.ctx)
         return {"box": (r.i0, r.j0, r.i1, r.j1), "n_range": r.n_range, "r_const": r.r_const}
 
+    def extract_paths(self, dT: int, nx: int, ny: int, ld: int, res: float, goal_i: int,
+                      goal_j: int, tau: float, starts_xy, max_wp: int, stride: int = 1,
+                      stream: int = 0):
+        """dymu_extract_paths_device on the device map dT for host starts (n, 2) in
+        grid-local metres: (out [n, max_wp, 4] of x, y, dcx, dcy; counts [n]; status [n])."""
+        xy = np.ascontiguousarray(starts_xy, dtype=np.float64).reshape(-1, 2)
+        n = len(xy)
+        out = np.zeros((n, max_wp, 4))
+        cnt = np.zeros(n, dtype=np.int32)
+        st = np.zeros(n, dtype=np.int32)
+        if n == 0:
+            return out, cnt, st
+        ptrs = [self.alloc(xy.nbytes), self.alloc(out.nbytes), self.alloc(4 * n),
+                self.alloc(4 * n)]
+        try:
+            self.h2d(ptrs[0], xy)
+            _check(self._lib.dymu_extract_paths_device(
+                self.ctx, dT, nx, ny, ld, res, goal_i, goal_j, tau, ptrs[0], n, max_wp, stride,
+                ptrs[1], ptrs[2], ptrs[3], stream or None), self.ctx)
+            if stream:  # d2h is ordered on the context stream only
+                self.last_paths_ms()
+            self.d2h(cnt, ptrs[2])
+            self.d2h(st, ptrs[3])
+            self.d2h(out, ptrs[1])
+        finally:
+            for p in ptrs:
+                self.free(p)
+        for q in range(n):  # slots past the count were never written
+            out[q, max(cnt[q], 0):] = 0.0
+        return out, cnt, st
+
+    def last_paths_ms(self) -> float:
+        """Device time of the last extract_paths kernel (waits for it)."""
+        ms = ctypes.c_double()
+        _check(self._lib.dymu_last_paths_ms(self.ctx, ctypes.byref(ms)), self.ctx)
+        return ms.value
+
     def alloc(self, nbytes: int) -> int:
         p = _vp()
         _check(self._lib.dymu_device_alloc(self.ctx, nbytes, ctypes.byref(p)), self.ctx)
@@ -496,6 +537,9 @@ PLANNER_SYMBOLS = {
     "dymu_planner_get_total_cost_raw": (_i32, [_vp, _dp]),
     "dymu_planner_get_total_cost": (_i32, [_vp, _d, _d, _d, _d, ctypes.POINTER(_d)]),
     "dymu_planner_get_path": (_i32, [_vp, _d, _d, _d, _d, _dp, _i32]),
+    "dymu_planner_get_paths": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dymu_planner_last_paths_on_device": (_i32, [_vp]),
+    "dymu_planner_last_paths_kernel_ms": (_i32, [_vp, ctypes.POINTER(_d)]),
     "dymu_planner_get_locomotion_mode": (_i32, [_vp, _d, _d, _d, _d, ctypes.c_char_p, _i32]),
     "dymu_planner_set_hazard_density": (_i32, [_vp, _dp]),
     "dymu_planner_set_trafficability": (_i32, [_vp, _dp]),
@@ -697,6 +741,34 @@ class Planner:
         if n < 0:
             raise DymuError(n)
         return buf[:4 * min(n, max_wp)].reshape(-1, 4).copy()
+
+    def getPaths(self, starts, max_wp: int = 1 << 20, stride: int = 1):
+        """Batched getPath without evaluatePath (DyMuPathPlanner::getPaths): the global
+        path of every start (x, y[, z, heading]) on the current map, on the GPU while the
+        device map is current.  Returns (list of (n_q, 4) arrays, status int32 array: 1
+        sink appended, 0 stalled, -1 first step NaN / off the grid, -3 max_wp reached).
+        current_path is not touched."""
+        s = np.ascontiguousarray([self._wp(w) for w in starts], dtype=np.float64).reshape(-1, 4)
+        n = len(s)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        _b_int(self._lib.dymu_planner_get_paths(self.h, s.ctypes.data, n, max_wp, stride, None,
+                                                cnt.ctypes.data, st.ctypes.data))
+        buf = np.empty((max(int(cnt[:n].sum()), 1), 4))
+        _b_int(self._lib.dymu_planner_get_paths(self.h, None, n, 0, 0, buf.ctypes.data, None,
+                                                None))
+        ends = np.cumsum(cnt[:n])
+        return [buf[e - c:e].copy() for e, c in zip(ends, cnt[:n])], st[:n].copy()
+
+    def lastPathsOnDevice(self) -> bool:
+        """Whether the last getPaths ran on the device (else on the host threads)."""
+        return _b(self._lib.dymu_planner_last_paths_on_device(self.h))
+
+    def lastPathsKernelMs(self) -> float:
+        """Kernel time of the last getPaths (HIP events, ms; 0 on the host route)."""
+        ms = ctypes.c_double()
+        _check(self._lib.dymu_planner_last_paths_kernel_ms(self.h, ctypes.byref(ms)))
+        return ms.value
 
     def getLocomotionMode(self, w) -> str:
         buf = ctypes.create_string_buffer(256)
