@@ -311,10 +311,34 @@ class DyMuPathPlanner {
   // ("ERROR in trajectory": the waypoints so far are kept); -1 the first step is NaN or
   // the start is off the grid (empty path); -3 more than max_wp waypoints (the first
   // max_wp kept).  stride >= 1 keeps waypoints 0, stride, 2 stride, ... and the sink.
+  // sinks (optional, one per start): the goal whose sink waypoint ends the path (0 for a
+  // single goal), -1 where status != 1
   std::vector<std::vector<base::Waypoint>> getPaths(const std::vector<base::Waypoint>& starts,
                                                     std::vector<int>* status = nullptr,
                                                     unsigned max_wp = 1u << 20,
-                                                    unsigned stride = 1);
+                                                    unsigned stride = 1,
+                                                    std::vector<int>* sinks = nullptr);
+  // Goal sets: several goals at once, each with an optional offset (a
+  // cost >= 0 already paid when the route ends there).  Every goal is validated as
+  // setGoal validates its one; offsets must be finite and >= 0, as many as the goals or
+  // none.  Any failure returns false and changes nothing.  setGoal clears the set.
+  // With a set active computeEntireTotalCostMap and computeTotalCostMap run one cold
+  // multi-source solve of the whole map (dymu_solve_seeds_device; no early exit, no
+  // windowed reuse), getPath / computeGlobalPath / getPaths end at the goal the label
+  // map names for the cell the path is in, and computeLocalPlanning / repairPath with
+  // more than one goal return false / -1.  globalGoal(), goalI(), goalJ() report goal 0.
+  bool setGoals(const std::vector<base::Waypoint>& goals, const std::vector<double>& offsets = {});
+  unsigned goalCount() const {
+    return !has_goal_ ? 0u : goals_.empty() ? 1u : (unsigned)goals_.size();
+  }
+  // The nearest-goal label of every node (ny*nx, row-major): the index of the goal its
+  // optimal route drains to, 0xFFFFFFFF (DYMU_LABEL_NONE) for none -- a function of the
+  // total-cost map alone (include/dymu_fim.h, dymu_goal_labels_device).  On the device
+  // while the device map is current, else by the same rule on the host; cached until
+  // the map or the goals change.  goalLabel: the nearest node's label, -1 for none.
+  void copyGoalLabels(uint32_t* out);
+  int goalLabel(base::Waypoint w);
+  uint32_t lastLabelRounds() const { return label_rounds_; }
   // whether the last getPaths ran on the device, and its kernel time (HIP events, ms)
   bool lastPathsOnDevice() const { return last_paths_device_; }
   double lastPathsKernelMs() const { return last_paths_kernel_ms_; }
@@ -404,10 +428,31 @@ class DyMuPathPlanner {
   // host threads share them): descend returns getPaths' status
   base::Waypoint nextWaypoint(base::Waypoint& wPos, double tau) const;
   int descend(base::Waypoint wPos, std::vector<base::Waypoint>& path, uint64_t max_wp,
-              unsigned stride) const;
+              unsigned stride, int* sink = nullptr) const;
   void pathsOnDevice(const std::vector<base::Waypoint>& starts,
                      std::vector<std::vector<base::Waypoint>>& out, std::vector<int>& st,
-                     unsigned max_wp, unsigned stride);
+                     std::vector<int>& sinks, unsigned max_wp, unsigned stride);
+  // goal sets: empty = the single goal of setGoal
+  struct Goal {
+    unsigned i, j;
+    double heading, t0;
+  };
+  std::vector<Goal> goals_;
+  std::vector<dymu_seed> seedList() const;      // the goals as engine seeds
+  base::Waypoint sinkWaypoint(size_t k) const;  // goal k's sink, grid-local
+  bool propagateGoals();                        // the cold multi-source solve
+  std::vector<uint64_t> sortedFinite();         // finite cells by (total cost, index)
+  bool goalsOnDevice() const;                   // the engine has the goal-set entries
+  // label caches: the host copy (labels_) and the device map (d_label_, plain cached
+  // device memory of dcells_ words, allocated on first use, freed with the engine)
+  std::vector<uint32_t> labels_;
+  bool labels_valid_ = false, d_label_valid_ = false;
+  uint32_t* d_label_ = nullptr;
+  uint32_t label_rounds_ = 0;
+  void invalidateLabels() { labels_valid_ = d_label_valid_ = false; }
+  void dropLabels();           // ... and free the device map
+  void ensureDeviceLabels();   // d_label_ from dT_
+  void ensureHostLabels();     // labels_: downloaded, or by the host routine
   // dT_ holds what the host mirror would show: set by the solves, the early exit's
   // scatters and uploads, loadTotalCostMap with an engine; cleared wherever the host
   // copy is written alone

@@ -185,6 +185,55 @@ int dymu_extract_paths_device(dymu_ctx* ctx, const double* dT, uint32_t nx, uint
  * it.  DYMU_ERR_STATE before the first one. */
 int dymu_last_paths_ms(dymu_ctx* ctx, double* ms);
 
+/* ---- goal sets: multi-source solve, nearest-goal labels and paths ----
+ * A seed is a source cell (i, j) with a start value t0 >= 0, finite (an offset: the
+ * cost already paid when the route ends there).  seeds: HOST array. */
+typedef struct dymu_seed {
+  uint32_t i, j;
+  double t0;
+} dymu_seed;
+#define DYMU_LABEL_NONE 0xFFFFFFFFu
+/* dymu_solve_device for a seed list: dT = +inf, then T[seed] = the smallest t0 given for
+ * that cell, then the converged solve -- the discrete upwind solution of all sources
+ * together (not the cellwise minimum of single-source solves, which only bounds it from
+ * above).  Any pass kernel, deterministic and exact_sqrt as for a single goal; one seed
+ * with t0 = 0 in deterministic mode is bitwise dymu_solve_device.  DYMU_ERR_ARG:
+ * n_seeds = 0, a seed off the grid, t0 negative, NaN or infinite.  A seed on a
+ * +inf-speed cell keeps its value and spreads from there, like a goal on one. */
+int dymu_solve_seeds_device(dymu_ctx* ctx, const double* dF, double* dT, uint32_t nx, uint32_t ny,
+                            uint64_t ld, const dymu_seed* seeds, uint32_t n_seeds, void* stream,
+                            dymu_stats* stats);
+/* d_label[j*nx + i] (device, nx*ny words, pitch nx; plain cached device memory serves the
+ * random gathers best) = the index of the seed the cell's optimal route drains to, a
+ * function of dT alone:
+ *   parent(c) = among the in-grid 4-neighbours in the order (i,j-1), (i-1,j), (i+1,j),
+ *     (i,j+1) the first one holding the smallest T, if that is strictly below T[c];
+ *   c is a root with label k if it is seed k's cell and T[c] is bitwise t0_k (duplicate
+ *     cells: the smallest t0, the lowest k among equal ones; a seed whose cell ended
+ *     below its t0 is dominated and no root);
+ *   DYMU_LABEL_NONE for T = +inf, for a non-root without a strictly smaller neighbour,
+ *     and for every cell that drains to such a cell; else label(c) = label(parent(c)).
+ * Requires nx*ny < 2^31 and n_seeds < 2^31.  *rounds (may be NULL) = pointer-jumping
+ * rounds run (about log2 of the longest chain; DYMU_ERR_NOT_CONVERGED beyond 64).
+ * Blocks until done. */
+int dymu_goal_labels_device(dymu_ctx* ctx, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
+                            const dymu_seed* seeds, uint32_t n_seeds, uint32_t* d_label,
+                            void* stream, uint32_t* rounds);
+/* dymu_extract_paths_device with a sink per path: whenever the path enters another
+ * cell (cx, cy) its sink becomes goal d_label[cy*nx + cx] at d_goal_xy[2k], [2k+1]
+ * (device, n_goals x 2: res*i, res*j); DYMU_LABEL_NONE keeps the previous sink, and a
+ * path whose first cell has none gets status -1.  The end test and the appended sink
+ * waypoint use the current sink; d_sink[p] = the goal appended, or -1. */
+int dymu_extract_paths_goals_device(dymu_ctx* ctx, const double* dT, uint32_t nx, uint32_t ny,
+                                    uint64_t ld, double res, const uint32_t* d_label,
+                                    const double* d_goal_xy, uint32_t n_goals, double tau,
+                                    const double* d_start_xy, uint32_t n_paths, uint32_t max_wp,
+                                    uint32_t stride, double* d_out, int32_t* d_count,
+                                    int32_t* d_status, void* stream, int32_t* d_sink);
+/* Device time (ms, HIP events) of the last dymu_goal_labels_device, first kernel to last.
+ * DYMU_ERR_STATE before the first one. */
+int dymu_last_labels_ms(dymu_ctx* ctx, double* ms);
+
 /* ---- row-slab domains (multi-GPU sharding; also single-GPU virtual slabs) ----
  * A rank owns rows [row0, row0+nrows) of an nx-wide global grid.  T points at
  * its first owned row; with ghost_lo the row above it (T - ld) holds the
@@ -309,6 +358,9 @@ int dymu_eikonal_batch(dymu_ctx* ctx, const double* tx, const double* ty, const 
  * and are complete on return. */
 int dymu_device_alloc(dymu_ctx* ctx, size_t bytes, void** dptr);
 int dymu_device_free(dymu_ctx* ctx, void* dptr);
+/* plain hipMalloc memory (L2-cached), whatever DYMU_MAP_MEM says: for buffers read by
+ * random gathers, such as dymu_goal_labels_device's d_label.  Freed by dymu_device_free. */
+int dymu_device_alloc_cached(dymu_ctx* ctx, size_t bytes, void** dptr);
 int dymu_memcpy_d2h(dymu_ctx* ctx, void* dst, const void* src, size_t bytes);
 int dymu_memcpy_h2d(dymu_ctx* ctx, void* dst, const void* src, size_t bytes);
 /* pitched copies (hipMemcpy2D: width bytes per row, height rows) */

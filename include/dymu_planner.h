@@ -74,6 +74,22 @@ int dymu_planner_get_path(dymu_planner* p, double x, double y, double z, double 
  * from the first call's counts) and drops it.  Returns n or a negative status. */
 int dymu_planner_get_paths(dymu_planner* p, const double* starts_xyzh, int n, int max_wp,
                            int stride, double* out_xyzh, int* counts, int* status);
+/* ---- goal sets (DyMuPathPlanner::setGoals) ----
+ * n goals (x, y, z, heading each) with offsets (n costs >= 0, finite) or NULL for none;
+ * each goal validated as dymu_planner_set_goal validates its one.  1 = set, 0 = rejected
+ * (nothing changed).  dymu_planner_set_goal clears the set. */
+int dymu_planner_set_goals(dymu_planner* p, const double* goals_xyzh, const double* offsets,
+                           int n);
+/* goals in force: 0 none, 1 after dymu_planner_set_goal, n after dymu_planner_set_goals */
+int dymu_planner_goal_count(dymu_planner* p);
+/* the nearest-goal label of every node (ny*nx, row-major; 0xFFFFFFFF = none) */
+int dymu_planner_get_goal_labels(dymu_planner* p, uint32_t* out);
+/* the label of the node nearest (x, y): >= 0, -1 for none (or off the grid, or a NULL
+ * handle); an engine failure returns its status (<= -2) */
+int dymu_planner_goal_label(dymu_planner* p, double x, double y);
+/* the goal each path of the last dymu_planner_get_paths ended on (-1: status != 1);
+ * n = that call's n.  Returns n or a negative status. */
+int dymu_planner_last_path_sinks(dymu_planner* p, int* out, int n);
 /* 1 if the last dymu_planner_get_paths ran on the device, 0 on the host threads */
 int dymu_planner_last_paths_on_device(dymu_planner* p);
 /* its kernel time (HIP events, ms; 0 on the host route) */

@@ -30,6 +30,9 @@ struct dymu_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_path0 = nullptr, ev_path1 = nullptr;  // around the last k_extract_paths
   bool path_timed = false;
+  hipEvent_t ev_lab0 = nullptr, ev_lab1 = nullptr;  // around the last dymu_goal_labels_device
+  bool lab_timed = false;
+  uint32_t* d_lab_cnt = nullptr;  // kLabelRounds + 1 counters of unresolved label entries
   dymu_opts opts{};
   int cu_count = 256;
   uint32_t* d_xchg = nullptr;  // k_exchange's block ticket (zero between launches)
@@ -1109,6 +1112,125 @@ int resolve_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_
   return converge_auto(c, st, stats);
 }
 
+// ---- goal sets (goal_kernels.hip) ----
+static_assert(sizeof(dymu_seed) == sizeof(GoalSeed) && offsetof(dymu_seed, t0) == offsetof(GoalSeed, t0),
+              "dymu_seed is GoalSeed");
+constexpr uint32_t kLabelRounds = 64;  // pointer-jumping rounds: ~log2 of the longest chain
+
+// The seeds checked and copied into the pinned transfer buffer, where the kernels read
+// them in place (ensure_xfer; the stream is drained first); *tmin = the smallest t0.
+// t0 + 0.0 turns a -0.0 into +0.0, so that the values' bit patterns order like them.
+int stage_seeds(dymu_ctx* c, uint32_t nx, uint32_t ny, const dymu_seed* seeds, uint32_t n,
+                hipStream_t st, const GoalSeed** d_seeds, double* tmin) {
+  if (!seeds || n == 0 || n >= (1u << 31)) return DYMU_ERR_ARG;
+  double m = __builtin_inf();
+  for (uint32_t k = 0; k < n; ++k) {
+    const dymu_seed& s = seeds[k];
+    if (s.i >= nx || s.j >= ny || !(s.t0 >= 0.0) || !(s.t0 < __builtin_inf())) return DYMU_ERR_ARG;
+    m = std::min(m, s.t0);
+  }
+  HIPC(c, hipStreamSynchronize(st));  // no earlier kernel still uses the transfer buffer
+  int rc = ensure_xfer(c, sizeof(GoalSeed) * (uint64_t)n);
+  if (rc) return rc;
+  GoalSeed* h = static_cast<GoalSeed*>(c->h_xfer);
+  for (uint32_t k = 0; k < n; ++k) h[k] = GoalSeed{seeds[k].i, seeds[k].j, seeds[k].t0 + 0.0};
+  *d_seeds = static_cast<const GoalSeed*>(c->d_xfer);
+  if (tmin) *tmin = m + 0.0;
+  return DYMU_OK;
+}
+
+// A cold domain without a goal, every seed min-written into T and its tile queued in
+// list 0 (priority kernels: key = the tile's smallest seed value, binned against
+// base = min t0), then the unchanged passes to convergence.
+int solve_seeds_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t ny,
+                     uint64_t ld, const dymu_seed* seeds, uint32_t n, hipStream_t st,
+                     dymu_stats* stats) {
+  if (!dF || !dT || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
+  const GoalSeed* d_seeds = nullptr;
+  double tmin = 0.0;
+  int rc = stage_seeds(c, nx, ny, seeds, n, st, &d_seeds, &tmin);
+  if (rc) return rc;
+  rc = dom_begin(c, dF, dT, nx, ny, ld, 0, 0, -1, -1, st);
+  if (rc) return rc;
+  auto& D = c->dom;
+  SeedArgs a{};
+  a.seeds = d_seeds;
+  a.n = n;
+  a.T = dT;
+  a.ld = (int64_t)ld;
+  a.nx = nx;
+  a.ny = ny;
+  a.tw = (uint32_t)tile_w(D.variant);
+  a.th = (uint32_t)tile_h(D.variant);
+  a.ntx = (uint32_t)D.a.ntx;
+  a.list = D.lists[0];
+  a.counts = D.counts[0];
+  a.shard_cap = D.ntiles;
+  a.tile_epoch = c->d_tile_epoch;
+  a.epoch = D.eb + 1;  // the epoch of list 0 (dom_launch: eb + p + 2 for list p + 1)
+  a.ec = D.a.ec;       // +inf after the cold dom_begin: the seeds on a tile's edge columns
+  hipError_t e = hipSuccess;
+  if (is_prio(D.variant)) {
+    a.keys = prio_keys(c, 0);
+    a.hist = prio_hist(c, 0);
+    a.base = prio_base(c, 0);
+    a.delta = prio_delta(c);
+    unsigned long long tb;
+    std::memcpy(&tb, &tmin, sizeof tb);
+    e = launch_store_u64(prio_minkey(c, 0), tb, st);
+    if (e == hipSuccess)
+      e = launch_store_u64(reinterpret_cast<unsigned long long*>(prio_base(c, 0)), tb, st);
+  }
+  if (e == hipSuccess) e = launch_seed_goals(a, st);
+  if (e != hipSuccess) {
+    dom_retire(c);
+    return fail_hip(c, e, "goal seeding");
+  }
+  return converge_auto(c, st, stats);
+}
+
+int goal_labels_core(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
+                     const dymu_seed* seeds, uint32_t n_seeds, uint32_t* d_label, hipStream_t st,
+                     uint32_t* rounds) {
+  if (!dT || !d_label || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
+  if ((uint64_t)nx * ny >= (1ull << 31)) return DYMU_ERR_ARG;  // entries hold a cell index + tag
+  const uint32_t n = nx * ny;
+  const GoalSeed* d_seeds = nullptr;
+  int rc = stage_seeds(c, nx, ny, seeds, n_seeds, st, &d_seeds, nullptr);
+  if (rc) return rc;
+  if (!c->ev_lab0) HIPC(c, hipEventCreate(&c->ev_lab0));
+  if (!c->ev_lab1) HIPC(c, hipEventCreate(&c->ev_lab1));
+  if (!c->d_lab_cnt) HIPC(c, hipMalloc(&c->d_lab_cnt, sizeof(uint32_t) * (kLabelRounds + 1)));
+  c->lab_timed = false;
+  HIPC(c, hipEventRecord(c->ev_lab0, st));
+  HIPC(c, hipMemsetAsync(c->d_lab_cnt, 0, sizeof(uint32_t) * (kLabelRounds + 1), st));
+  HIPC(c, launch_label_init(dT, (int64_t)ld, nx, ny, d_seeds, n_seeds, d_label, st));
+  // rounds in batches of 4 between read-backs of the counters; a round launched
+  // behind the one that resolved the last entry returns at once
+  uint32_t launched = 0, done = 0;
+  uint32_t h_cnt[kLabelRounds];
+  while (done == 0 && launched < kLabelRounds) {
+    const uint32_t r0 = launched;
+    for (uint32_t k = 0; k < 4 && launched < kLabelRounds; ++k, ++launched)
+      HIPC(c, launch_label_jump(d_label, n, c->d_lab_cnt, launched, st));
+    HIPC(c, hipStreamSynchronize(st));
+    HIPC(c, hipMemcpy(h_cnt + r0, c->d_lab_cnt + r0, sizeof(uint32_t) * (launched - r0),
+                      hipMemcpyDeviceToHost));
+    for (uint32_t r = r0; r < launched && done == 0; ++r)
+      if (h_cnt[r] == 0) done = r + 1;
+  }
+  HIPC(c, launch_label_strip(d_label, n, st));
+  HIPC(c, hipEventRecord(c->ev_lab1, st));
+  HIPC(c, hipStreamSynchronize(st));
+  c->lab_timed = true;
+  if (rounds) *rounds = done ? done : launched;
+  if (done == 0) {
+    c->last_error = "goal labels: round cap reached";
+    return DYMU_ERR_NOT_CONVERGED;
+  }
+  return DYMU_OK;
+}
+
 hipStream_t pick_stream(dymu_ctx* c, void* s) { return s ? (hipStream_t)s : c->stream; }
 
 }  // namespace
@@ -1238,6 +1360,9 @@ int dymu_destroy(dymu_ctx* c) {
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev_path0) (void)hipEventDestroy(c->ev_path0);
   if (c->ev_path1) (void)hipEventDestroy(c->ev_path1);
+  if (c->ev_lab0) (void)hipEventDestroy(c->ev_lab0);
+  if (c->ev_lab1) (void)hipEventDestroy(c->ev_lab1);
+  if (c->d_lab_cnt) (void)hipFree(c->d_lab_cnt);
   if (c->d_lists) (void)hipFree(c->d_lists);
   if (c->d_tile_epoch) (void)hipFree(c->d_tile_epoch);
   if (c->d_counts) (void)hipFree(c->d_counts);
@@ -1421,11 +1546,14 @@ int dymu_scatter(dymu_ctx* c, double* dT, uint32_t nx, uint64_t ld, const uint64
   return DYMU_OK;
 }
 
-int dymu_extract_paths_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
-                              double res, uint32_t gi, uint32_t gj, double tau,
-                              const double* d_start_xy, uint32_t n_paths, uint32_t max_wp,
-                              uint32_t stride, double* d_out, int32_t* d_count, int32_t* d_status,
-                              void* stream) {
+namespace {
+// dymu_extract_paths_device (d_label null: one sink, the goal (gi, gj)) and
+// dymu_extract_paths_goals_device (the sink follows the label map)
+int extract_paths(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld, double res,
+                  uint32_t gi, uint32_t gj, const uint32_t* d_label, const double* d_goal_xy,
+                  uint32_t n_goals, double tau, const double* d_start_xy, uint32_t n_paths,
+                  uint32_t max_wp, uint32_t stride, double* d_out, int32_t* d_count,
+                  int32_t* d_status, int32_t* d_sink, void* stream) {
   if (!c || !dT || nx == 0 || ny == 0 || ld < nx || gi >= nx || gj >= ny) return DYMU_ERR_ARG;
   if (!(res > 0) || !(res < HUGE_VAL) || !(tau > 0) || !(tau < HUGE_VAL)) return DYMU_ERR_ARG;
   if (max_wp == 0 || max_wp > 0x7fffffffu || stride == 0) return DYMU_ERR_ARG;
@@ -1454,11 +1582,65 @@ int dymu_extract_paths_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32
   a.out = d_out;
   a.count = d_count;
   a.status = d_status;
+  a.label = d_label;
+  a.goal_xy = d_goal_xy;
+  a.n_goals = n_goals;
+  a.sink = d_sink;
   c->path_timed = false;
   HIPC(c, hipEventRecord(c->ev_path0, st));
-  HIPC(c, launch_extract_paths(a, st));
+  HIPC(c, d_label ? launch_extract_paths_goals(a, st) : launch_extract_paths(a, st));
   HIPC(c, hipEventRecord(c->ev_path1, st));
   c->path_timed = true;
+  return DYMU_OK;
+}
+}  // namespace
+
+int dymu_extract_paths_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
+                              double res, uint32_t gi, uint32_t gj, double tau,
+                              const double* d_start_xy, uint32_t n_paths, uint32_t max_wp,
+                              uint32_t stride, double* d_out, int32_t* d_count, int32_t* d_status,
+                              void* stream) {
+  return extract_paths(c, dT, nx, ny, ld, res, gi, gj, nullptr, nullptr, 0, tau, d_start_xy,
+                       n_paths, max_wp, stride, d_out, d_count, d_status, nullptr, stream);
+}
+
+int dymu_extract_paths_goals_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny,
+                                    uint64_t ld, double res, const uint32_t* d_label,
+                                    const double* d_goal_xy, uint32_t n_goals, double tau,
+                                    const double* d_start_xy, uint32_t n_paths, uint32_t max_wp,
+                                    uint32_t stride, double* d_out, int32_t* d_count,
+                                    int32_t* d_status, void* stream, int32_t* d_sink) {
+  if (!d_label || !d_goal_xy || n_goals == 0 || n_goals >= (1u << 31)) return DYMU_ERR_ARG;
+  if ((uint64_t)nx * ny >= (1ull << 31) || (n_paths && !d_sink)) return DYMU_ERR_ARG;
+  return extract_paths(c, dT, nx, ny, ld, res, 0, 0, d_label, d_goal_xy, n_goals, tau, d_start_xy,
+                       n_paths, max_wp, stride, d_out, d_count, d_status, d_sink, stream);
+}
+
+int dymu_solve_seeds_device(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t ny,
+                            uint64_t ld, const dymu_seed* seeds, uint32_t n_seeds, void* stream,
+                            dymu_stats* stats) {
+  if (!c) return DYMU_ERR_ARG;
+  HIPC(c, hipSetDevice(c->device));
+  return solve_seeds_core(c, dF, dT, nx, ny, ld, seeds, n_seeds, pick_stream(c, stream), stats);
+}
+
+int dymu_goal_labels_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
+                            const dymu_seed* seeds, uint32_t n_seeds, uint32_t* d_label,
+                            void* stream, uint32_t* rounds) {
+  if (!c) return DYMU_ERR_ARG;
+  HIPC(c, hipSetDevice(c->device));
+  return goal_labels_core(c, dT, nx, ny, ld, seeds, n_seeds, d_label, pick_stream(c, stream),
+                          rounds);
+}
+
+int dymu_last_labels_ms(dymu_ctx* c, double* ms) {
+  if (!c || !ms) return DYMU_ERR_ARG;
+  if (!c->lab_timed) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipEventSynchronize(c->ev_lab1));
+  float f = 0.0f;
+  HIPC(c, hipEventElapsedTime(&f, c->ev_lab0, c->ev_lab1));
+  *ms = (double)f;
   return DYMU_OK;
 }
 
@@ -1572,6 +1754,13 @@ int dymu_device_alloc(dymu_ctx* c, size_t bytes, void** p) {
   if (!c || !p) return DYMU_ERR_ARG;
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, dev_alloc(p, bytes, c->map_mem));
+  return DYMU_OK;
+}
+
+int dymu_device_alloc_cached(dymu_ctx* c, size_t bytes, void** p) {
+  if (!c || !p) return DYMU_ERR_ARG;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, dev_alloc(p, bytes, 0));
   return DYMU_OK;
 }
 

@@ -315,8 +315,51 @@ struct PathArgs {
   double* out;      // [path][slot][4]: x, y and the (dcx, dcy) that produced the waypoint
   int32_t* count;   // slots written per path
   int32_t* status;  // 1 sink appended, 0 stalled, -1 first step NaN / off the grid, -3 max_wp
+  // ---- goal sets (launch_extract_paths_goals; unused by launch_extract_paths) ----
+  const uint32_t* label;  // nearest-goal label per cell, pitch nx (0xFFFFFFFF: none)
+  const double* goal_xy;  // n_goals x 2: the sinks (res * i, res * j)
+  uint32_t n_goals;
+  int32_t* sink;          // per path: the goal whose sink was appended, or -1
 };
 hipError_t launch_extract_paths(const PathArgs& a, hipStream_t st);
+// the same descent with a per-path sink: the goal labelled on the cell the path is in
+hipError_t launch_extract_paths_goals(const PathArgs& a, hipStream_t st);
+
+// goal sets (goal_kernels.hip)
+struct GoalSeed {  // dymu_seed's layout
+  uint32_t i, j;
+  double t0;
+};
+struct SeedArgs {
+  const GoalSeed* seeds;  // device-readable
+  uint32_t n;
+  double* T;
+  int64_t ld;
+  uint32_t nx, ny;
+  uint32_t tw, th, ntx;
+  uint32_t* list;    // list 0 (kShards x shard_cap)
+  uint32_t* counts;  // its kShards counters
+  uint32_t shard_cap;
+  uint32_t* tile_epoch;
+  uint32_t epoch;
+  unsigned long long* keys;  // priority kernels: keys / histogram of list 0, else null
+  uint32_t* hist;
+  const double* base;   // histogram origin of list 0 (= min t0) and bin width
+  const double* delta;
+  double* ec;  // kernel 5 edge columns, else null
+};
+// T[seed] = min(T, t0) for every seed; each seeded tile once into list 0, its key the
+// smallest seed value in it, binned against *base
+hipError_t launch_seed_goals(const SeedArgs& a, hipStream_t st);
+// L (nx * ny entries, pitch nx): per cell a resolved label (top bit set) or its parent's
+// cell index; then in-place pointer-jumping rounds (cnt[round] = entries still
+// unresolved after it; a round after a 0 does nothing) and the tag bit's removal
+hipError_t launch_label_init(const double* T, int64_t ld, uint32_t nx, uint32_t ny,
+                             const GoalSeed* seeds, uint32_t n_seeds, uint32_t* L,
+                             hipStream_t st);
+hipError_t launch_label_jump(uint32_t* L, uint32_t n, uint32_t* cnt, uint32_t round,
+                             hipStream_t st);
+hipError_t launch_label_strip(uint32_t* L, uint32_t n, hipStream_t st);
 
 hipError_t launch_prio_init(const double* F, int64_t ld, int64_t nx, int64_t ny,
                            unsigned long long* keys, uint64_t nkeys, uint32_t* hist, uint64_t nhist,

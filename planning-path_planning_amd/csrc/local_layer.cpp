@@ -728,6 +728,7 @@ std::vector<base::Waypoint> DyMuPathPlanner::getLocalPath(const localNode& lSetN
 int DyMuPathPlanner::repairPath(base::Waypoint start, unsigned index) {
   std::vector<base::Waypoint>& P = current_path;
   if (P.empty()) return -1;
+  if (goals_.size() > 1) return -1;  // local repair toward a goal set: not supported
   double overtake_index;
   if (repairing_approach_ == CONSERVATIVE) {
     overtake_index =
@@ -833,6 +834,7 @@ bool DyMuPathPlanner::computeLocalPlanning(base::Waypoint wPos,
                                            double res, std::vector<base::Waypoint>& trajectory,
                                            base::Time& localTime) {
   if (!local_) return false;
+  if (goals_.size() > 1) return false;  // local repair toward a goal set: not supported
   wPos.position[0] -= global_offset_[0];
   wPos.position[1] -= global_offset_[1];
   const unsigned height = traversabilityMap.getHeight(), width = traversabilityMap.getWidth();

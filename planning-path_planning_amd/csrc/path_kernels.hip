@@ -66,6 +66,12 @@ __device__ __forceinline__ double dist2d(double ax, double ay, double bx, double
   return sqrt(dx * dx + dy * dy);
 }
 
+// GOALS: the sink is per path and follows the label map (goal sets):
+// whenever the cell the lane holds gradients for changes, the sink becomes the goal
+// labelled on that cell; a cell without a label keeps the previous sink, and a path
+// whose first cell has none ends with status -1.  GOALS = false is the single-sink
+// kernel, unchanged.
+template <bool GOALS>
 __global__ __launch_bounds__(64) void k_extract_paths(PathArgs a) {
   const uint32_t p = blockIdx.x * 64u + threadIdx.x;
   if (p >= a.n_paths) return;
@@ -79,9 +85,11 @@ __global__ __launch_bounds__(64) void k_extract_paths(PathArgs a) {
   double pdx = 0, pdy = 0;  // the direction that produced the current waypoint
   int64_t ccx = -1, ccy = -1;  // the cell whose corner gradients are held
   double gx00 = 0, gx10 = 0, gx01 = 0, gx11 = 0, gy00 = 0, gy10 = 0, gy01 = 0, gy11 = 0;
+  double sink_x = a.sink_x, sink_y = a.sink_y;
+  int32_t sink_k = -1;  // GOALS: the goal of the current sink
   for (uint64_t w = 0;; ++w) {
     // (x, y) is the path's waypoint w unless the descent ends here
-    if (w > 0 && !(dist2d(x, y, a.sink_x, a.sink_y) > a.two_res)) break;  // NaN ends it too (Q5)
+    if (w > 0 && !(dist2d(x, y, sink_x, sink_y) > a.two_res)) break;  // NaN ends it too (Q5)
     if (w == limit) {
       status = -3;
       break;
@@ -113,6 +121,14 @@ __global__ __launch_bounds__(64) void k_extract_paths(PathArgs a) {
         gradient_node(true, e_ok, true, n_ok, t21, t23, t12, t32, t22, gx11, gy11);
         ccx = cx;
         ccy = cy;
+        if (GOALS) {  // the cell is inside the grid: cy * nx + cx < nx * ny
+          const uint32_t lab = a.label[cy * nx + cx];
+          if (lab < a.n_goals) {
+            sink_x = a.goal_xy[2 * (uint64_t)lab];
+            sink_y = a.goal_xy[2 * (uint64_t)lab + 1];
+            sink_k = (int32_t)lab;
+          }
+        }
       }
       const double ax = gx - (double)cx, ay = gy - (double)cy;
       dcx = interpolate(ax, ay, gx00, gx01, gx10, gx11);
@@ -121,6 +137,10 @@ __global__ __launch_bounds__(64) void k_extract_paths(PathArgs a) {
       nxt_y = y - a.res_tau * dcy;
     }
     if (w == 0 && (nxt_x != nxt_x || nxt_y != nxt_y)) {  // :628-633
+      status = -1;
+      break;
+    }
+    if (GOALS && w == 0 && sink_k < 0) {  // no goal drains the start's cell
       status = -1;
       break;
     }
@@ -145,8 +165,8 @@ __global__ __launch_bounds__(64) void k_extract_paths(PathArgs a) {
   if (status == 1) {
     if (n < a.max_wp) {
       double* o = out + 4 * (uint64_t)n;
-      o[0] = a.sink_x;
-      o[1] = a.sink_y;
+      o[0] = sink_x;
+      o[1] = sink_y;
       o[2] = 0;
       o[3] = 0;
       ++n;
@@ -156,6 +176,7 @@ __global__ __launch_bounds__(64) void k_extract_paths(PathArgs a) {
   }
   a.count[p] = (int32_t)n;
   a.status[p] = status;
+  if (GOALS) a.sink[p] = status == 1 ? sink_k : -1;
 }
 
 }  // namespace
@@ -163,7 +184,14 @@ __global__ __launch_bounds__(64) void k_extract_paths(PathArgs a) {
 hipError_t launch_extract_paths(const PathArgs& a, hipStream_t st) {
   if (a.n_paths == 0) return hipSuccess;
   const uint32_t blocks = (a.n_paths + 63u) / 64u;
-  hipLaunchKernelGGL(k_extract_paths, dim3(blocks), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_extract_paths<false>, dim3(blocks), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_extract_paths_goals(const PathArgs& a, hipStream_t st) {
+  if (a.n_paths == 0) return hipSuccess;
+  const uint32_t blocks = (a.n_paths + 63u) / 64u;
+  hipLaunchKernelGGL(k_extract_paths<true>, dim3(blocks), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

@@ -59,6 +59,7 @@ void release_engine(dymu_ctx*& ctx, double*& dF, double*& dT, void*& reg, uint64
 }  // namespace
 
 DyMuPathPlanner::~DyMuPathPlanner() {
+  dropLabels();
   release_engine(ctx_, dF_, dT_, registered_, dcells_);
 }
 
@@ -67,6 +68,7 @@ void DyMuPathPlanner::setEngineOptions(const dymu_opts& o) {
   // the solved map lives in dT_: bring the host mirror up to date before the
   // device buffers go, so T(), getPath and the matrix getters keep working
   if (ctx_ && dT_ && blk_missing_) fetchAll();
+  dropLabels();
   release_engine(ctx_, dF_, dT_, registered_, dcells_);
   dev_map_current_ = false;
   solved_ = false;
@@ -106,6 +108,8 @@ bool DyMuPathPlanner::initGlobalLayer(double globalres, double localres, unsigne
   is_obstacle_.assign(n, 0);
   loc_mode_.assign(n, -1);
   has_goal_ = false;
+  goals_.clear();
+  dropLabels();
   current_path.clear();
   // a new grid: new device buffers and an empty total-cost map (every node
   // OPEN at +inf, as the globalNode constructor leaves it)
@@ -428,6 +432,8 @@ bool DyMuPathPlanner::setGoal(base::Waypoint wGoal) {
   goal_i_ = i;
   goal_j_ = j;
   goal_heading_ = wGoal.heading;
+  goals_.clear();
+  invalidateLabels();
   return true;
 }
 
@@ -514,6 +520,7 @@ void DyMuPathPlanner::ensureEngine() {
     if (dF_) (void)dymu_device_free(ctx_, dF_);
     if (dT_) (void)dymu_device_free(ctx_, dT_);
     dF_ = dT_ = nullptr;
+    dropLabels();
     dcells_ = 0;
     dev_map_current_ = false;
     void *f = nullptr, *t = nullptr;
@@ -727,6 +734,7 @@ bool DyMuPathPlanner::propagate(bool early, unsigned si, unsigned sj) {
   }
   double t_closed = kInf;
   dev_map_current_ = false;  // until the engine call below succeeds
+  invalidateLabels();
   if (rc != DYMU_OK) {
     solved_ = false;
     rc = early ? dymu_solve_until_device(ctx_, dF_, dT_, nx_, ny_, nx_, goal_i_, goal_j_, si, sj,
@@ -1402,6 +1410,7 @@ bool DyMuPathPlanner::exactEarlyExit(unsigned si, unsigned sj, const int64_t box
   const uint64_t n = (uint64_t)nx_ * ny_;
   HostFmm r = hostFmm(si, sj, box);
   const int64_t* bx = r.bx;
+  invalidateLabels();
   std::fill(total_cost_.begin(), total_cost_.end(), kInf);
   node_state_.assign(n, 0);
   for (int64_t j = bx[1]; j <= bx[3]; ++j)
@@ -1599,6 +1608,7 @@ bool DyMuPathPlanner::computeEntireTotalCostMap() {
     log_warn("The goal is not valid");
     return false;
   }
+  if (!goals_.empty()) return propagateGoals();
   return propagate(false, 0, 0);
 }
 
@@ -1633,7 +1643,9 @@ bool DyMuPathPlanner::computeTotalCostMap(base::Waypoint wPos) {
     log_error("PLANNER: The rover is located too close to an obstacle");
     return false;
   }
-  if (!propagate(true, si, sj)) {
+  // a goal set has no early exit (the reference's tie and insertion-order rules are
+  // single-goal): the whole map, and "unreachable" read from it
+  if (!goals_.empty() ? !(propagateGoals() && T(idx(si, sj)) < kInf) : !propagate(true, si, sj)) {
     log_error("The goal is unreachable");
     return false;
   }
@@ -1660,53 +1672,11 @@ std::vector<base::Waypoint> DyMuPathPlanner::getPath(base::Waypoint wPos) {
 bool DyMuPathPlanner::computeGlobalPath(base::Waypoint wPos) {
   current_path.clear();
   if (!has_goal_) return false;
+  if (!goals_.empty()) ensureHostLabels();
   const int st = descend(wPos, current_path, std::numeric_limits<uint64_t>::max(), 1);
   if (st == -1) log_error("PLANNER: Gradient Descent Method failed");
   if (st == 0) log_error("ERROR in trajectory");
   return st == 1;
-}
-
-// The loop of computeGlobalPath into `path`, without member writes.  Returns getPaths'
-// status: 1 sink appended, 0 "ERROR in trajectory" (the waypoints so far kept), -1 the
-// first step is NaN (empty path), -3 more than max_wp waypoints (the first max_wp
-// kept).  Waypoint w of the reference's path is kept when w % stride == 0, the sink
-// always; the loop runs at most max_wp * stride steps (k_extract_paths' bound).
-int DyMuPathPlanner::descend(base::Waypoint wPos, std::vector<base::Waypoint>& path,
-                             uint64_t max_wp, unsigned stride) const {
-  path.clear();
-  if (!has_goal_) return -1;
-  const uint64_t limit = max_wp > std::numeric_limits<uint64_t>::max() / stride
-                             ? std::numeric_limits<uint64_t>::max()
-                             : max_wp * stride;
-  base::Waypoint sink;
-  sink.position[0] = global_res_ * (double)goal_i_;
-  sink.position[1] = global_res_ * (double)goal_j_;
-  sink.position[2] = elevation_.empty() ? 0.0 : elevation_[idx(goal_i_, goal_j_)];
-  sink.heading = goal_heading_;
-  const double tau = std::min(0.4, risk_distance_);
-  base::Waypoint wNext = nextWaypoint(wPos, tau);
-  if (std::isnan(wNext.position[0]) || std::isnan(wNext.position[1])) return -1;
-  unsigned phase = 0;
-  auto push = [&](const base::Waypoint& w) {
-    if (phase == 0) path.push_back(w);
-    if (++phase == stride) phase = 0;
-  };
-  push(wPos);
-  wPos = wNext;
-  auto dist = [](const base::Waypoint& a, const base::Waypoint& b) {
-    const double dx = a.position[0] - b.position[0], dy = a.position[1] - b.position[1];
-    return std::sqrt(dx * dx + dy * dy);
-  };
-  for (uint64_t w = 1; dist(wPos, sink) > 2.0 * global_res_; ++w) {
-    if (w == limit) return -3;
-    wNext = nextWaypoint(wPos, tau);
-    push(wPos);
-    if (dist(wPos, wNext) < 0.01 * tau * global_res_) return 0;
-    wPos = wNext;
-  }
-  if (path.size() >= max_wp) return -3;
-  path.push_back(sink);
-  return 1;
 }
 
 namespace {
@@ -1726,6 +1696,79 @@ double bilinear(double a, double b, double g00, double g01, double g10, double g
   return g00 + (g10 - g00) * a + (g01 - g00) * b + (g11 + g00 - g10 - g01) * a * b;
 }
 }  // namespace
+
+// The loop of computeGlobalPath into `path`, without member writes.  Returns getPaths'
+// status: 1 sink appended, 0 "ERROR in trajectory" (the waypoints so far kept), -1 the
+// first step is NaN (empty path), -3 more than max_wp waypoints (the first max_wp
+// kept).  Waypoint w of the reference's path is kept when w % stride == 0, the sink
+// always; the loop runs at most max_wp * stride steps (k_extract_paths' bound).
+// With a goal set (labels_ valid: ensureHostLabels) the sink follows the label map as in
+// k_extract_paths<true>: before each step, when the position is in another cell than the
+// last one looked up, the sink becomes the goal labelled on that cell's node (no label:
+// the previous sink stays; none yet at the first step: -1).  *sink_out = the goal whose
+// sink was appended, -1 otherwise.
+int DyMuPathPlanner::descend(base::Waypoint wPos, std::vector<base::Waypoint>& path,
+                             uint64_t max_wp, unsigned stride, int* sink_out) const {
+  path.clear();
+  if (sink_out) *sink_out = -1;
+  if (!has_goal_) return -1;
+  const uint64_t limit = max_wp > std::numeric_limits<uint64_t>::max() / stride
+                             ? std::numeric_limits<uint64_t>::max()
+                             : max_wp * stride;
+  base::Waypoint sink;
+  sink.position[0] = global_res_ * (double)goal_i_;
+  sink.position[1] = global_res_ * (double)goal_j_;
+  sink.position[2] = elevation_.empty() ? 0.0 : elevation_[idx(goal_i_, goal_j_)];
+  sink.heading = goal_heading_;
+  const bool gs = !goals_.empty();
+  int sink_k = gs ? -1 : 0;
+  bool held = false;
+  unsigned hcx = 0, hcy = 0;
+  auto track = [&](const base::Waypoint& p) {
+    if (!gs) return;
+    unsigned cx = 0, cy = 0;
+    if (!path_cell(p.position[0] / global_res_, nx_, cx) ||
+        !path_cell(p.position[1] / global_res_, ny_, cy))
+      return;
+    if (held && cx == hcx && cy == hcy) return;
+    held = true;
+    hcx = cx;
+    hcy = cy;
+    const uint32_t lab = labels_[idx(cx, cy)];
+    if (lab < goals_.size()) {
+      sink = sinkWaypoint(lab);
+      sink_k = (int)lab;
+    }
+  };
+  const double tau = std::min(0.4, risk_distance_);
+  track(wPos);
+  base::Waypoint wNext = nextWaypoint(wPos, tau);
+  if (std::isnan(wNext.position[0]) || std::isnan(wNext.position[1])) return -1;
+  if (sink_k < 0) return -1;
+  unsigned phase = 0;
+  auto push = [&](const base::Waypoint& w) {
+    if (phase == 0) path.push_back(w);
+    if (++phase == stride) phase = 0;
+  };
+  push(wPos);
+  wPos = wNext;
+  auto dist = [](const base::Waypoint& a, const base::Waypoint& b) {
+    const double dx = a.position[0] - b.position[0], dy = a.position[1] - b.position[1];
+    return std::sqrt(dx * dx + dy * dy);
+  };
+  for (uint64_t w = 1; dist(wPos, sink) > 2.0 * global_res_; ++w) {
+    if (w == limit) return -3;
+    track(wPos);
+    wNext = nextWaypoint(wPos, tau);
+    push(wPos);
+    if (dist(wPos, wNext) < 0.01 * tau * global_res_) return 0;
+    wPos = wNext;
+  }
+  if (path.size() >= max_wp) return -3;
+  path.push_back(sink);
+  if (sink_out) *sink_out = sink_k;
+  return 1;
+}
 
 // :666-714 (wPos.position[2] is written: elevation, bilinear, with the
 // reference's argument order at :699-704)
@@ -1810,19 +1853,20 @@ double DyMuPathPlanner::interpolate(double a, double b, double g00, double g01, 
 
 std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getPaths(
     const std::vector<base::Waypoint>& starts, std::vector<int>* status, unsigned max_wp,
-    unsigned stride) {
+    unsigned stride, std::vector<int>* sinks) {
   if (max_wp == 0 || stride == 0) throw std::invalid_argument("getPaths: max_wp, stride >= 1");
   const size_t n = starts.size();
   std::vector<std::vector<base::Waypoint>> out(n);
-  std::vector<int> st(n, -1);
+  std::vector<int> st(n, -1), sk(n, -1);
   last_paths_device_ = false;
   last_paths_kernel_ms_ = 0.0;
   if (n && has_goal_) {
     if (ctx_ && dT_ && dev_map_current_ && n <= 0xffffffffull && &dymu_extract_paths_device &&
-        &dymu_last_paths_ms) {
-      pathsOnDevice(starts, out, st, max_wp, stride);
+        &dymu_last_paths_ms && (goals_.empty() || goalsOnDevice())) {
+      pathsOnDevice(starts, out, st, sk, max_wp, stride);
       last_paths_device_ = true;
     } else {
+      if (!goals_.empty()) ensureHostLabels();
       // the host descent per start (T() is thread-safe; descend writes no member)
       const unsigned nt = (unsigned)std::min<size_t>(host_threads(), n);
       std::atomic<size_t> next{0};
@@ -1831,7 +1875,7 @@ std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getPaths(
           base::Waypoint w = starts[q];
           w.position[0] -= global_offset_[0];
           w.position[1] -= global_offset_[1];
-          st[q] = descend(w, out[q], max_wp, stride);
+          st[q] = descend(w, out[q], max_wp, stride, &sk[q]);
           for (auto& p : out[q]) {
             p.position[0] += global_offset_[0];
             p.position[1] += global_offset_[1];
@@ -1841,6 +1885,7 @@ std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getPaths(
     }
   }
   if (status) status->swap(st);
+  if (sinks) sinks->swap(sk);
   return out;
 }
 
@@ -1877,7 +1922,8 @@ struct DeviceScratch {
 // overflow it (status -3 below max_wp) run again with four times the capacity.
 void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
                                     std::vector<std::vector<base::Waypoint>>& out,
-                                    std::vector<int>& st, unsigned max_wp, unsigned stride) {
+                                    std::vector<int>& st, std::vector<int>& sinks,
+                                    unsigned max_wp, unsigned stride) {
   constexpr uint64_t kOutBytes = 4ull << 30;  // device output of one batch, at most
   const size_t n = starts.size();
   const double tau = std::min(0.4, risk_distance_);
@@ -1891,6 +1937,11 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
   sink.position[1] = global_res_ * (double)goal_j_ + global_offset_[1];
   sink.position[2] = elevation_[idx(goal_i_, goal_j_)];
   sink.heading = goal_heading_;
+  // a goal set: the label map and the goals' sinks on the device, one sink per path back
+  const bool gs = !goals_.empty();
+  std::vector<base::Waypoint> gsinks;
+  std::vector<int32_t> snk;
+  double* d_gxy = nullptr;
   // a straight descent across the grid is (nx + ny) / tau waypoints at most
   uint64_t cap = std::max<uint64_t>(1024, 4 * ((uint64_t)nx_ + ny_) / stride);
   cap = std::min<uint64_t>(cap, max_wp);
@@ -1905,6 +1956,20 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
   };
   std::vector<Run> runs;
   DeviceScratch dev(ctx_);
+  if (gs) {
+    ensureDeviceLabels();
+    std::vector<double> gxy(2 * goals_.size());
+    for (size_t k = 0; k < goals_.size(); ++k) {
+      base::Waypoint w = sinkWaypoint(k);
+      gxy[2 * k] = w.position[0];
+      gxy[2 * k + 1] = w.position[1];
+      w.position[0] += global_offset_[0];
+      w.position[1] += global_offset_[1];
+      gsinks.push_back(w);
+    }
+    d_gxy = dev.alloc<double>(gxy.size());
+    check(dymu_memcpy_h2d(ctx_, d_gxy, gxy.data(), sizeof(double) * gxy.size()), "upload");
+  }
   while (!pending.empty()) {
     const uint64_t per_batch = std::max<uint64_t>(1, kOutBytes / (32 * cap));
     again.clear();
@@ -1921,11 +1986,22 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
       int32_t* d_st = dev.alloc<int32_t>(m);
       double* d_out = dev.alloc<double>(4 * cap * m);
       check(dymu_memcpy_h2d(ctx_, d_xy, xy.data(), sizeof(double) * xy.size()), "upload");
-      check(dymu_extract_paths_device(ctx_, dT_, nx_, ny_, nx_, global_res_, goal_i_, goal_j_, tau,
-                                      d_xy, m, (uint32_t)cap, stride, d_out, d_cnt, d_st, nullptr),
-            "kernel");
+      int32_t* d_snk = gs ? dev.alloc<int32_t>(m) : nullptr;
+      if (gs)
+        check(dymu_extract_paths_goals_device(ctx_, dT_, nx_, ny_, nx_, global_res_, d_label_,
+                                              d_gxy, (uint32_t)goals_.size(), tau, d_xy, m,
+                                              (uint32_t)cap, stride, d_out, d_cnt, d_st, nullptr,
+                                              d_snk),
+              "kernel");
+      else
+        check(dymu_extract_paths_device(ctx_, dT_, nx_, ny_, nx_, global_res_, goal_i_, goal_j_,
+                                        tau, d_xy, m, (uint32_t)cap, stride, d_out, d_cnt, d_st,
+                                        nullptr),
+              "kernel");
       cnt.resize(m);
       sts.resize(m);
+      snk.assign(m, 0);
+      if (gs) check(dymu_memcpy_d2h(ctx_, snk.data(), d_snk, sizeof(int32_t) * m), "download");
       check(dymu_memcpy_d2h(ctx_, cnt.data(), d_cnt, sizeof(int32_t) * m), "download");
       check(dymu_memcpy_d2h(ctx_, sts.data(), d_st, sizeof(int32_t) * m), "download");
       double ms = 0.0;
@@ -1963,6 +2039,7 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
                                   32 * cap, 32 * r.width, r.n),
                 "download");
       for (void* p : {(void*)d_xy, (void*)d_cnt, (void*)d_st, (void*)d_out}) dev.release(p);
+      if (d_snk) dev.release(d_snk);
       // host post-pass: z from the elevation with the host's interpolate call and its
       // argument order (nextWaypoint), heading = atan2(-dcy, -dcx) with the host libm
       const unsigned nt = std::min<unsigned>(host_threads(), m);
@@ -1972,6 +2049,7 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
           const uint32_t id = ids[q];
           st[id] = sts[q];
           if (sts[q] == -3 && cap < max_wp) continue;
+          sinks[id] = sts[q] == 1 ? snk[q] : -1;
           const uint64_t c = len[q];
           const double* r = raw.data() + 4 * off[q];
           std::vector<base::Waypoint>& path = out[id];
@@ -1979,7 +2057,7 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
           for (uint64_t k = 0; k < c; ++k, r += 4) {
             base::Waypoint& w = path[k];
             if (sts[q] == 1 && k + 1 == c) {
-              w = sink;
+              w = gs ? gsinks[(size_t)snk[q]] : sink;
               continue;
             }
             if (k == 0) w = starts[id];
@@ -2005,6 +2083,211 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
     pending.swap(again);
     cap = std::min<uint64_t>(cap * 4, max_wp);
   }
+}
+
+// ---- goal sets (extension) ----
+
+// The goal-set entries of the engine C-ABI: null with an engine that predates them
+// (see the path entries above); the solve then fails, labels and paths take the host route.
+#pragma weak dymu_solve_seeds_device
+#pragma weak dymu_goal_labels_device
+#pragma weak dymu_extract_paths_goals_device
+#pragma weak dymu_device_alloc_cached
+
+bool DyMuPathPlanner::goalsOnDevice() const {
+  return &dymu_goal_labels_device && &dymu_extract_paths_goals_device &&
+         &dymu_device_alloc_cached && (uint64_t)nx_ * ny_ < (1ull << 31);
+}
+
+bool DyMuPathPlanner::setGoals(const std::vector<base::Waypoint>& goals,
+                               const std::vector<double>& offsets) {
+  if (goals.empty() || (!offsets.empty() && offsets.size() != goals.size())) return false;
+  std::vector<Goal> gs;
+  for (size_t q = 0; q < goals.size(); ++q) {
+    const double t0 = offsets.empty() ? 0.0 : offsets[q];
+    if (!(t0 >= 0.0) || !(t0 < kInf)) return false;
+    // setGoal's tests (:322-357)
+    const double px = (goals[q].position[0] - global_offset_[0]) / global_res_;
+    const double py = (goals[q].position[1] - global_offset_[1]) / global_res_;
+    if (!(px >= 0) || !(py >= 0)) return false;
+    const unsigned i = grid_u32(px + 0.5), j = grid_u32(py + 0.5);
+    if (i >= nx_ || j >= ny_) return false;
+    if (i == 0 || j == 0 || i + 1 >= nx_ || j + 1 >= ny_) return false;
+    const uint64_t k = idx(i, j);
+    if (is_obstacle_[k] || is_obstacle_[k - nx_] || is_obstacle_[k - 1] || is_obstacle_[k + 1] ||
+        is_obstacle_[k + nx_])
+      return false;
+    gs.push_back(Goal{i, j, goals[q].heading, t0 + 0.0});
+  }
+  goals_.swap(gs);
+  has_goal_ = true;
+  goal_i_ = goals_[0].i;
+  goal_j_ = goals_[0].j;
+  goal_heading_ = goals_[0].heading;
+  solved_ = false;  // no single-goal map is reused under a goal set
+  invalidateLabels();
+  return true;
+}
+
+std::vector<dymu_seed> DyMuPathPlanner::seedList() const {
+  std::vector<dymu_seed> s;
+  if (goals_.empty()) {
+    if (has_goal_) s.push_back(dymu_seed{goal_i_, goal_j_, 0.0});
+  } else {
+    for (const Goal& g : goals_) s.push_back(dymu_seed{g.i, g.j, g.t0});
+  }
+  return s;
+}
+
+base::Waypoint DyMuPathPlanner::sinkWaypoint(size_t k) const {
+  const Goal& g = goals_[k];
+  base::Waypoint w;
+  w.position[0] = global_res_ * (double)g.i;
+  w.position[1] = global_res_ * (double)g.j;
+  w.position[2] = elevation_.empty() ? 0.0 : elevation_[idx(g.i, g.j)];
+  w.heading = g.heading;
+  return w;
+}
+
+// computeEntireTotalCostMap for a goal set: always the cold multi-source solve; the
+// state is a converged full solve's (every finite node CLOSED, no band), and solved_
+// stays false so that no single-goal window reuse is keyed on this map.
+bool DyMuPathPlanner::propagateGoals() {
+  for (const Goal& g : goals_)
+    if (is_obstacle_[idx(g.i, g.j)]) {
+      log_warn("The goal is not valid");
+      return false;
+    }
+  ensureEngine();
+  if (!&dymu_solve_seeds_device)
+    throw std::runtime_error("dymu: the engine has no multi-source solve (dymu_solve_seeds_device)");
+  unsigned i0, i1, j0, j1;
+  (void)syncSpeed(i0, i1, j0, j1);
+  const std::vector<dymu_seed> seeds = seedList();
+  dev_map_current_ = false;
+  solved_ = false;
+  invalidateLabels();
+  const int rc = dymu_solve_seeds_device(ctx_, dF_, dT_, nx_, ny_, nx_, seeds.data(),
+                                         (uint32_t)seeds.size(), nullptr, &stats_);
+  if (rc != DYMU_OK)
+    throw std::runtime_error(std::string("dymu solve failed: ") + dymu_strerror(rc) + " " +
+                             dymu_last_error(ctx_));
+  incremental_ = 0;
+  dev_map_current_ = true;
+  std::fill(blk_ok_.begin(), blk_ok_.end(), 0);
+  blk_missing_ = blk_ok_.size();
+  band_cells_.clear();
+  band_unordered_ = false;
+  band_values_checked_ = true;
+  open_at_limit_.clear();
+  node_state_.clear();
+  propagated_extra_.clear();
+  manual_list_ = false;
+  early_info_ = EarlyExitInfo{};
+  have_start_ = false;
+  closed_limit_ = kInf;
+  return true;
+}
+
+// global_propagated_nodes under a goal set: the finite cells by (total cost, grid index)
+std::vector<uint64_t> DyMuPathPlanner::sortedFinite() {
+  fetchAll();
+  std::vector<std::pair<double, uint64_t>> v;
+  for (uint64_t k = 0; k < total_cost_.size(); ++k)
+    if (total_cost_[k] < kInf) v.emplace_back(total_cost_[k], k);
+  parallel_sort(v);
+  std::vector<uint64_t> out;
+  out.reserve(v.size());
+  for (const auto& e : v) out.push_back(e.second);
+  return out;
+}
+
+void DyMuPathPlanner::dropLabels() {
+  invalidateLabels();
+  if (d_label_ && ctx_) (void)dymu_device_free(ctx_, d_label_);
+  d_label_ = nullptr;
+}
+
+void DyMuPathPlanner::ensureDeviceLabels() {
+  if (d_label_valid_) return;
+  const uint64_t n = (uint64_t)nx_ * ny_;
+  if (!d_label_) {
+    void* p = nullptr;
+    if (dymu_device_alloc_cached(ctx_, sizeof(uint32_t) * n, &p) != DYMU_OK)
+      throw std::runtime_error(std::string("dymu: cannot allocate the label map: ") +
+                               dymu_last_error(ctx_));
+    d_label_ = static_cast<uint32_t*>(p);
+  }
+  const std::vector<dymu_seed> seeds = seedList();
+  const int rc = dymu_goal_labels_device(ctx_, dT_, nx_, ny_, nx_, seeds.data(),
+                                         (uint32_t)seeds.size(), d_label_, nullptr, &label_rounds_);
+  if (rc != DYMU_OK)
+    throw std::runtime_error(std::string("dymu: goal labels failed: ") + dymu_strerror(rc) + " " +
+                             dymu_last_error(ctx_));
+  d_label_valid_ = true;
+}
+
+// The label rule of include/dymu_fim.h on the host mirror: roots first, then the cells
+// in ascending total cost, each taking its parent's label (a parent is strictly lower,
+// so it is labelled by then).
+void DyMuPathPlanner::ensureHostLabels() {
+  if (labels_valid_) return;
+  const uint64_t n = (uint64_t)nx_ * ny_;
+  labels_.assign(n, DYMU_LABEL_NONE);
+  const std::vector<dymu_seed> seeds = seedList();
+  if (seeds.empty()) {
+    labels_valid_ = true;
+    return;
+  }
+  if (ctx_ && dT_ && dev_map_current_ && goalsOnDevice()) {
+    ensureDeviceLabels();
+    if (dymu_memcpy_d2h(ctx_, labels_.data(), d_label_, sizeof(uint32_t) * n) != DYMU_OK)
+      throw std::runtime_error(std::string("dymu: label download failed: ") +
+                               dymu_last_error(ctx_));
+    labels_valid_ = true;
+    return;
+  }
+  label_rounds_ = 0;
+  fetchAll();
+  const double* t = total_cost_.data();
+  std::vector<uint8_t> root(n, 0);
+  for (size_t k = seeds.size(); k-- > 0;) {  // descending: the lowest k is written last
+    const uint64_t c = idx(seeds[k].i, seeds[k].j);
+    if (std::memcmp(&t[c], &seeds[k].t0, sizeof(double)) != 0) continue;  // dominated
+    labels_[c] = (uint32_t)k;
+    root[c] = 1;
+  }
+  std::vector<std::pair<double, uint64_t>> order;
+  for (uint64_t c = 0; c < n; ++c)
+    if (t[c] < kInf && !root[c]) order.emplace_back(t[c], c);
+  parallel_sort(order);
+  for (const auto& e : order) {
+    const uint64_t c = e.second;
+    const unsigned i = (unsigned)(c % nx_), j = (unsigned)(c / nx_);
+    double best = e.first;
+    uint64_t par = n;
+    if (j > 0 && t[c - nx_] < best) { best = t[c - nx_]; par = c - nx_; }
+    if (i > 0 && t[c - 1] < best) { best = t[c - 1]; par = c - 1; }
+    if (i + 1 < nx_ && t[c + 1] < best) { best = t[c + 1]; par = c + 1; }
+    if (j + 1 < ny_ && t[c + nx_] < best) { best = t[c + nx_]; par = c + nx_; }
+    if (par < n) labels_[c] = labels_[par];
+  }
+  labels_valid_ = true;
+}
+
+void DyMuPathPlanner::copyGoalLabels(uint32_t* out) {
+  ensureHostLabels();
+  std::memcpy(out, labels_.data(), sizeof(uint32_t) * labels_.size());
+}
+
+int DyMuPathPlanner::goalLabel(base::Waypoint w) {
+  const double x = w.position[0] - global_offset_[0], y = w.position[1] - global_offset_[1];
+  if (!(x / global_res_ + 0.5 >= 0) || !(y / global_res_ + 0.5 >= 0)) return -1;
+  const int64_t k = nearestIndex(x, y);
+  if (k < 0) return -1;
+  ensureHostLabels();
+  const uint32_t lab = labels_[(uint64_t)k];
+  return lab == DYMU_LABEL_NONE ? -1 : (int)lab;
 }
 
 // :788-795
@@ -2160,6 +2443,7 @@ void DyMuPathPlanner::resetTotalCostMap() {
   manual_list_ = true;
   solved_ = false;
   dev_map_current_ = false;  // the host copy alone was written
+  invalidateLabels();
 }
 
 // the node states of the last solve made explicit, so a caller can change some
@@ -2217,6 +2501,7 @@ void DyMuPathPlanner::propagateGlobalNode(unsigned i, unsigned j) {
     total_cost_[k] = Tn;
     solved_ = false;  // the device map no longer matches the host's
     dev_map_current_ = false;
+    invalidateLabels();
   }
 }
 
@@ -2241,7 +2526,7 @@ uint64_t DyMuPathPlanner::globalPropagatedCount() {
 std::vector<uint64_t> DyMuPathPlanner::globalPropagatedIndices() {
   std::vector<uint64_t> out;
   if (!manual_list_) {
-    out = insertionOrder();
+    out = goals_.empty() ? insertionOrder() : sortedFinite();
     if (!propagated_extra_.empty()) {
       std::vector<uint8_t> extra(total_cost_.size(), 0);
       for (const uint64_t k : propagated_extra_) extra[k] = 1;
@@ -2318,10 +2603,31 @@ void DyMuPathPlanner::resetGlobalNarrowBand() {
   band_unordered_ = false;
   band_values_checked_ = true;
   if (!has_goal_ || nx_ == 0) return;
+  if (!goals_.empty()) {  // every root goal: not dominated, once per cell, at its offset
+    fetchAll();
+    const std::vector<dymu_seed> seeds = seedList();
+    std::vector<std::pair<uint64_t, double>> roots;
+    for (const dymu_seed& sd : seeds) {
+      const uint64_t k = idx(sd.i, sd.j);
+      if (total_cost_[k] < sd.t0) continue;  // dominated by another goal
+      auto it = std::find_if(roots.begin(), roots.end(), [&](const auto& r) { return r.first == k; });
+      if (it == roots.end()) roots.emplace_back(k, sd.t0);
+      else it->second = std::min(it->second, sd.t0);
+    }
+    dev_map_current_ = false;
+    invalidateLabels();
+    for (const auto& r : roots) {
+      total_cost_[r.first] = r.second;
+      band_cells_.push_back(r.first);
+      propagated_extra_.push_back(r.first);
+    }
+    return;
+  }
   const uint64_t k = idx(goal_i_, goal_j_);
   (void)T(k);  // the goal's block in the host mirror before the write
   total_cost_[k] = 0.0;
   dev_map_current_ = false;  // written on the host alone
+  invalidateLabels();
   band_cells_.push_back(k);
   propagated_extra_.push_back(k);  // global_propagated_nodes.push_back(global_goal)
 }
@@ -2342,6 +2648,7 @@ bool DyMuPathPlanner::loadTotalCostMap(const double* Tin) {
   manual_list_ = false;
   solved_ = false;
   dev_map_current_ = false;
+  invalidateLabels();
   if (ctx_ && dT_ && dcells_ == n) {
     if (dymu_memcpy_h2d(ctx_, dT_, total_cost_.data(), sizeof(double) * n) != DYMU_OK)
       throw std::runtime_error(std::string("dymu: total-cost upload failed: ") +

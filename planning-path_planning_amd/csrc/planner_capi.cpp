@@ -21,6 +21,7 @@ struct dymu_planner {
   // the last dymu_planner_get_paths result, kept until it is copied out
   std::vector<std::vector<base::Waypoint>> paths;
   std::vector<int> paths_status;
+  std::vector<int> paths_sinks;  // the goal each of those paths ended on (-1: none)
   dymu_planner(double a, double b, double c, PathPlanning_lib::repairingAproach r)
       : pl(a, b, c, r) {}
 };
@@ -416,7 +417,8 @@ int dymu_planner_get_paths(dymu_planner* p, const double* starts, int n, int max
       std::vector<base::Waypoint> s((size_t)n);
       for (int q = 0; q < n; ++q)
         s[q] = wp(starts[4 * q], starts[4 * q + 1], starts[4 * q + 2], starts[4 * q + 3]);
-      p->paths = p->pl.getPaths(s, &p->paths_status, (unsigned)max_wp, (unsigned)stride);
+      p->paths = p->pl.getPaths(s, &p->paths_status, (unsigned)max_wp, (unsigned)stride,
+                                &p->paths_sinks);
     }
     for (int q = 0; q < n; ++q) {
       if (counts) counts[q] = (int)p->paths[q].size();
@@ -430,6 +432,41 @@ int dymu_planner_get_paths(dymu_planner* p, const double* starts, int n, int max
     }
     return n;
   });
+}
+
+int dymu_planner_set_goals(dymu_planner* p, const double* xyzh, const double* offsets, int n) {
+  if (!p || !xyzh || n <= 0) return DYMU_ERR_ARG;
+  return guarded([&] {
+    std::vector<base::Waypoint> g((size_t)n);
+    for (int q = 0; q < n; ++q)
+      g[q] = wp(xyzh[4 * q], xyzh[4 * q + 1], xyzh[4 * q + 2], xyzh[4 * q + 3]);
+    std::vector<double> off;
+    if (offsets) off.assign(offsets, offsets + n);
+    return (int)p->pl.setGoals(g, off);
+  });
+}
+
+int dymu_planner_goal_count(dymu_planner* p) {
+  if (!p) return DYMU_ERR_ARG;
+  return (int)p->pl.goalCount();
+}
+
+int dymu_planner_get_goal_labels(dymu_planner* p, uint32_t* out) {
+  if (!p || !out) return DYMU_ERR_ARG;
+  return guarded([&] { p->pl.copyGoalLabels(out); return DYMU_OK; });
+}
+
+int dymu_planner_goal_label(dymu_planner* p, double x, double y) {
+  if (!p) return -1;
+  int lab = -1;
+  const int rc = guarded([&] { lab = p->pl.goalLabel(wp(x, y, 0, 0)); return DYMU_OK; });
+  return rc < 0 ? rc : lab;
+}
+
+int dymu_planner_last_path_sinks(dymu_planner* p, int* out, int n) {
+  if (!p || !out || n < 0 || (size_t)n != p->paths_sinks.size()) return DYMU_ERR_ARG;
+  std::copy(p->paths_sinks.begin(), p->paths_sinks.end(), out);
+  return n;
 }
 
 int dymu_planner_last_paths_on_device(dymu_planner* p) {

@@ -104,6 +104,10 @@ _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 _u32, _u64, _i32, _vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p
 
 # name -> (restype, argtypes)
+# dymu_seed (include/dymu_fim.h): a source cell and its start value
+SEED_DTYPE = np.dtype([("i", np.uint32), ("j", np.uint32), ("t0", np.float64)], align=True)
+LABEL_NONE = 0xFFFFFFFF
+
 FIM_SYMBOLS = {
     "dymu_create": (_i32, [ctypes.POINTER(_vp), ctypes.POINTER(DymuOpts)]),
     "dymu_destroy": (_i32, [_vp]),
@@ -167,6 +171,15 @@ FIM_SYMBOLS = {
                                          ctypes.c_double, _vp, _u32, _u32, _u32, _vp, _vp, _vp,
                                          _vp]),
     "dymu_last_paths_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_solve_seeds_device": (_i32, [_vp, _vp, _vp, _u32, _u32, _u64, _vp, _u32, _vp,
+                                       ctypes.POINTER(DymuStats)]),
+    "dymu_goal_labels_device": (_i32, [_vp, _vp, _u32, _u32, _u64, _vp, _u32, _vp, _vp,
+                                       ctypes.POINTER(_u32)]),
+    "dymu_extract_paths_goals_device": (_i32, [_vp, _vp, _u32, _u32, _u64, ctypes.c_double, _vp,
+                                               _vp, _u32, ctypes.c_double, _vp, _u32, _u32, _u32,
+                                               _vp, _vp, _vp, _vp, _vp]),
+    "dymu_last_labels_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_device_alloc_cached": (_i32, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "dymu_memcpy2d_d2h": (_i32, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
                                  ctypes.c_size_t, ctypes.c_size_t]),
     "dymu_memcpy2d_h2d": (_i32, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
@@ -386,9 +399,98 @@ class Engine:
         _check(self._lib.dymu_last_paths_ms(self.ctx, ctypes.byref(ms)), self.ctx)
         return ms.value
 
+    # -- goal sets --
+    @staticmethod
+    def _seeds(seeds) -> np.ndarray:
+        """(i, j[, t0]) rows as an array of dymu_seed."""
+        a = np.zeros(len(seeds), dtype=SEED_DTYPE)
+        for k, s in enumerate(seeds):
+            a[k] = (int(s[0]), int(s[1]), float(s[2]) if len(s) > 2 else 0.0)
+        return a
+
+    def solve_seeds_device(self, dF: int, dT: int, nx: int, ny: int, ld: int, seeds,
+                           stream: int = 0) -> dict:
+        """dymu_solve_seeds_device: the converged multi-source solve of the seeds
+        (i, j[, t0]) into dT."""
+        a = self._seeds(seeds)
+        st = DymuStats()
+        _check(self._lib.dymu_solve_seeds_device(self.ctx, dF, dT, nx, ny, ld, a.ctypes.data,
+                                                 len(a), stream or None, ctypes.byref(st)),
+               self.ctx)
+        return st.as_dict()
+
+    def goal_labels_device(self, dT: int, nx: int, ny: int, ld: int, seeds, d_label: int = 0,
+                           stream: int = 0, download: bool = True):
+        """dymu_goal_labels_device on the device map dT: (labels [ny, nx] uint32, rounds).
+        With d_label (nx * ny words of device memory) the labels stay there as well, and
+        download=False then returns (None, rounds) without the copy to the host."""
+        a = self._seeds(seeds)
+        rounds = _u32()
+        own = 0 if d_label else self.alloc_cached(4 * nx * ny)
+        try:
+            _check(self._lib.dymu_goal_labels_device(self.ctx, dT, nx, ny, ld, a.ctypes.data,
+                                                     len(a), d_label or own, stream or None,
+                                                     ctypes.byref(rounds)), self.ctx)
+            lab = None
+            if download or own:
+                lab = np.empty((ny, nx), dtype=np.uint32)
+                self.d2h(lab, d_label or own)
+        finally:
+            if own:
+                self.free(own)
+        return lab, rounds.value
+
+    def last_labels_ms(self) -> float:
+        """Device time of the last goal_labels_device (first kernel to last)."""
+        ms = ctypes.c_double()
+        _check(self._lib.dymu_last_labels_ms(self.ctx, ctypes.byref(ms)), self.ctx)
+        return ms.value
+
+    def extract_paths_goals(self, dT: int, nx: int, ny: int, ld: int, res: float, d_label: int,
+                            goals_ij, tau: float, starts_xy, max_wp: int, stride: int = 1,
+                            stream: int = 0):
+        """dymu_extract_paths_goals_device: extract_paths with the sink taken from the label
+        map d_label (device) and the goals' cells goals_ij (n_goals, 2): (out, counts,
+        status, sinks [n] int32)."""
+        xy = np.ascontiguousarray(starts_xy, dtype=np.float64).reshape(-1, 2)
+        gxy = res * np.ascontiguousarray(goals_ij, dtype=np.float64).reshape(-1, 2)
+        n = len(xy)
+        out = np.zeros((n, max_wp, 4))
+        cnt = np.zeros(n, dtype=np.int32)
+        st = np.zeros(n, dtype=np.int32)
+        sink = np.full(n, -1, dtype=np.int32)
+        if n == 0:
+            return out, cnt, st, sink
+        ptrs = [self.alloc(xy.nbytes), self.alloc(out.nbytes), self.alloc(4 * n),
+                self.alloc(4 * n), self.alloc(4 * n), self.alloc(gxy.nbytes)]
+        try:
+            self.h2d(ptrs[0], xy)
+            self.h2d(ptrs[5], gxy)
+            _check(self._lib.dymu_extract_paths_goals_device(
+                self.ctx, dT, nx, ny, ld, res, d_label, ptrs[5], len(gxy), tau, ptrs[0], n,
+                max_wp, stride, ptrs[1], ptrs[2], ptrs[3], stream or None, ptrs[4]), self.ctx)
+            if stream:  # d2h is ordered on the context stream only
+                self.last_paths_ms()
+            self.d2h(cnt, ptrs[2])
+            self.d2h(st, ptrs[3])
+            self.d2h(sink, ptrs[4])
+            self.d2h(out, ptrs[1])
+        finally:
+            for p in ptrs:
+                self.free(p)
+        for q in range(n):  # slots past the count were never written
+            out[q, max(cnt[q], 0):] = 0.0
+        return out, cnt, st, sink
+
     def alloc(self, nbytes: int) -> int:
         p = _vp()
         _check(self._lib.dymu_device_alloc(self.ctx, nbytes, ctypes.byref(p)), self.ctx)
+        return p.value
+
+    def alloc_cached(self, nbytes: int) -> int:
+        """Plain (L2-cached) device memory, e.g. for a label map; free() releases it."""
+        p = _vp()
+        _check(self._lib.dymu_device_alloc_cached(self.ctx, nbytes, ctypes.byref(p)), self.ctx)
         return p.value
 
     def free(self, p: int):
@@ -538,6 +640,11 @@ PLANNER_SYMBOLS = {
     "dymu_planner_get_total_cost": (_i32, [_vp, _d, _d, _d, _d, ctypes.POINTER(_d)]),
     "dymu_planner_get_path": (_i32, [_vp, _d, _d, _d, _d, _dp, _i32]),
     "dymu_planner_get_paths": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dymu_planner_set_goals": (_i32, [_vp, _vp, _vp, _i32]),
+    "dymu_planner_goal_count": (_i32, [_vp]),
+    "dymu_planner_get_goal_labels": (_i32, [_vp, _vp]),
+    "dymu_planner_goal_label": (_i32, [_vp, _d, _d]),
+    "dymu_planner_last_path_sinks": (_i32, [_vp, _vp, _i32]),
     "dymu_planner_last_paths_on_device": (_i32, [_vp]),
     "dymu_planner_last_paths_kernel_ms": (_i32, [_vp, ctypes.POINTER(_d)]),
     "dymu_planner_get_locomotion_mode": (_i32, [_vp, _d, _d, _d, _d, ctypes.c_char_p, _i32]),
@@ -656,6 +763,7 @@ class Planner:
             raise DymuError(rc, "dymu_planner_create")
         self.h = h
         self.nx = self.ny = 0
+        self._sinks = np.zeros(0, dtype=np.int32)
         if device >= 0:
             o = DymuOpts(device, 0, 0, 0, 0)
             _check(self._lib.dymu_planner_set_engine_options(self.h, ctypes.byref(o)))
@@ -703,6 +811,41 @@ class Planner:
 
     def setGoal(self, w) -> bool:
         return _b(self._lib.dymu_planner_set_goal(self.h, *self._wp(w)))
+
+    def setGoals(self, goals, offsets=None) -> bool:
+        """DyMuPathPlanner::setGoals: several goals (x, y[, z, heading]) at once, each with
+        an optional offset >= 0.  False (and nothing changed) if any is rejected."""
+        g = np.ascontiguousarray([self._wp(w) for w in goals], dtype=np.float64).reshape(-1, 4)
+        off = None
+        if offsets is not None:
+            off = np.ascontiguousarray(offsets, dtype=np.float64).ravel()
+            if len(off) != len(g):
+                return False
+        if len(g) == 0:
+            return False
+        return _b(self._lib.dymu_planner_set_goals(
+            self.h, g.ctypes.data, None if off is None else off.ctypes.data, len(g)))
+
+    def goalCount(self) -> int:
+        return _b_int(self._lib.dymu_planner_goal_count(self.h))
+
+    def goalLabels(self) -> np.ndarray:
+        """The nearest-goal label of every node, [ny, nx] uint32 (LABEL_NONE: none)."""
+        out = np.empty((self.ny, self.nx), dtype=np.uint32)
+        _check(self._lib.dymu_planner_get_goal_labels(self.h, out.ctypes.data))
+        return out
+
+    def goalLabel(self, w) -> int:
+        """The label of the node nearest w, -1 for none."""
+        x, y, _, _ = self._wp(w)
+        rc = self._lib.dymu_planner_goal_label(self.h, x, y)
+        if rc < -1:
+            raise DymuError(rc)
+        return rc
+
+    def lastPathSinks(self) -> np.ndarray:
+        """The goal each path of the last getPaths ended on (-1 where status != 1)."""
+        return self._sinks.copy()
 
     def computeTotalCostMap(self, w) -> bool:
         return _b(self._lib.dymu_planner_compute_total_cost_map(self.h, *self._wp(w)))
@@ -754,6 +897,9 @@ class Planner:
         st = np.zeros(max(n, 1), dtype=np.int32)
         _b_int(self._lib.dymu_planner_get_paths(self.h, s.ctypes.data, n, max_wp, stride, None,
                                                 cnt.ctypes.data, st.ctypes.data))
+        self._sinks = np.full(n, -1, dtype=np.int32)
+        if n:
+            _b_int(self._lib.dymu_planner_last_path_sinks(self.h, self._sinks.ctypes.data, n))
         buf = np.empty((max(int(cnt[:n].sum()), 1), 4))
         _b_int(self._lib.dymu_planner_get_paths(self.h, None, n, 0, 0, buf.ctypes.data, None,
                                                 None))
