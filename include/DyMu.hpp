@@ -339,6 +339,35 @@ class DyMuPathPlanner {
   void copyGoalLabels(uint32_t* out);
   int goalLabel(base::Waypoint w);
   uint32_t lastLabelRounds() const { return label_rounds_; }
+  // Batched total-cost maps: one map per goal, all on the current speed,
+  // solved together in one pass sequence (dymu_solve_batch_device: the maps are planes of
+  // one stacked domain) and kept on the device.  Every goal is validated as setGoal
+  // validates its one; the speed is synchronised as a solve does.  Needs the device
+  // engine: without one it returns false.  Any failure returns false and changes nothing.
+  // The batch is state of its own: the goal / goal set, the single total-cost map and what
+  // is derived from it (getTotalCostMatrix, getPath, getPaths, the labels), current_path and
+  // lastSolveKind() are not touched.  It is dropped by initGlobalLayer, setEngineOptions
+  // and the next speed synchronisation that finds a change (batchCount() is then 0 and the
+  // accessors below return false).
+  bool computeTotalCostMaps(const std::vector<base::Waypoint>& goals);
+  unsigned batchCount() const { return (unsigned)batch_goals_.size(); }
+  const dymu_stats& lastBatchStats() const { return batch_stats_; }
+  // plane b (ny*nx, row-major) raw (+inf unreachable) or as getTotalCostMatrix (-1)
+  bool copyBatchTotalCost(unsigned b, double* out, bool raw);
+  // out[b * points.size() + m] = what getTotalCost(points[m]) returns on map b (the
+  // offset removed on entry, as getTotalCost does), evaluated on the device
+  bool getTotalCosts(const std::vector<base::Waypoint>& points, std::vector<double>& out);
+  // computeTotalCostMaps(goals) and getTotalCosts(targets, out) in one call: the
+  // goals x targets traverse-cost matrix
+  bool costMatrix(const std::vector<base::Waypoint>& goals,
+                  const std::vector<base::Waypoint>& targets, std::vector<double>& out);
+  // getPaths on map b with goal b as the sink (always on the device; sinks are 0).
+  // Throws std::invalid_argument for b >= batchCount().
+  std::vector<std::vector<base::Waypoint>> getPathsTo(unsigned b,
+                                                      const std::vector<base::Waypoint>& starts,
+                                                      std::vector<int>* status = nullptr,
+                                                      unsigned max_wp = 1u << 20,
+                                                      unsigned stride = 1);
   // whether the last getPaths ran on the device, and its kernel time (HIP events, ms)
   bool lastPathsOnDevice() const { return last_paths_device_; }
   double lastPathsKernelMs() const { return last_paths_kernel_ms_; }
@@ -429,9 +458,33 @@ class DyMuPathPlanner {
   base::Waypoint nextWaypoint(base::Waypoint& wPos, double tau) const;
   int descend(base::Waypoint wPos, std::vector<base::Waypoint>& path, uint64_t max_wp,
               unsigned stride, int* sink = nullptr) const;
+  // target: another device map of this grid and its sink (getPathsTo) in place of dT_
+  // and the goal / goal set
+  struct PathTarget {
+    const double* map;
+    unsigned gi, gj;
+    double heading;
+  };
   void pathsOnDevice(const std::vector<base::Waypoint>& starts,
                      std::vector<std::vector<base::Waypoint>>& out, std::vector<int>& st,
-                     std::vector<int>& sinks, unsigned max_wp, unsigned stride);
+                     std::vector<int>& sinks, unsigned max_wp, unsigned stride,
+                     const PathTarget* target = nullptr);
+  // the batch (computeTotalCostMaps): its goals and the solved stack, plane b at
+  // dT_batch_ + b * dymu_batch_plane_rows(ny_) * nx_ (pitch nx_)
+  struct BatchGoal {
+    unsigned i, j;
+    double heading;
+  };
+  std::vector<BatchGoal> batch_goals_;
+  double* dT_batch_ = nullptr;
+  dymu_stats batch_stats_{};
+  void dropBatch();
+  // goal cell of w by setGoal's tests; false if setGoal would reject it
+  bool goalCell(const base::Waypoint& w, unsigned& i, unsigned& j) const;
+  // a speed change a batch solve synchronised while dT_ still holds the map of the
+  // old speed: its box joins what the next single-goal solve finds changed
+  bool pend_ = false, pend_dec_ = true;
+  unsigned pend_i0_ = 0, pend_i1_ = 0, pend_j0_ = 0, pend_j1_ = 0;
   // goal sets: empty = the single goal of setGoal
   struct Goal {
     unsigned i, j;

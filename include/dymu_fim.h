@@ -234,6 +234,50 @@ int dymu_extract_paths_goals_device(dymu_ctx* ctx, const double* dT, uint32_t nx
  * DYMU_ERR_STATE before the first one. */
 int dymu_last_labels_ms(dymu_ctx* ctx, double* ms);
 
+/* ---- batched solves: many maps in one pass sequence ----
+ * A batch is B planes of nx x ny cells stacked into ONE domain of nx x (B * P) cells with
+ * pitch ld, where P = dymu_batch_plane_rows(ny) = 16 * ceil((ny + 1) / 16) is the plane
+ * pitch in rows: plane b, row j lives at stacked row b * P + j.  Rows ny .. P-1 of every
+ * plane (at least one, and every plane starts on a tile boundary of the 8- and the
+ * 16-cell tiles) are wall rows: F = +inf there, hence T = +inf after a solve.  The update
+ * ignores a +inf neighbour, so the planes cannot influence each other, while their fronts
+ * advance in the same passes: the pass count stays about that of one map and each pass
+ * does B times the work.  A stack costs 16 * B * nx * P bytes for F and T together.
+ * A plane is an ordinary map at dT_stack + b * P * ld (pitch ld): dymu_extract_paths_device,
+ * dymu_goal_labels_device and the copy helpers work on it unchanged.
+ * dymu_batch_plane_rows returns 0 where P does not fit in uint32_t (ny >= 2^32 - 16). */
+uint32_t dymu_batch_plane_rows(uint32_t ny);
+/* A seed of a batch: cell (i, j) of plane `plane` with start value t0 (as dymu_seed). */
+typedef struct dymu_batch_seed {
+  uint32_t plane, i, j, reserved;
+  double t0;
+} dymu_batch_seed;
+/* The stacked speed: plane b of dF_stack <- the nx x ny map at src + b * src_plane_stride
+ * (device, pitch src_ld; src_plane_stride = 0: one shared map replicated B times), every
+ * wall row +inf.  Asynchronous on `stream`.  DYMU_ERR_ARG: B = 0, ld or src_ld < nx,
+ * B * P not fitting in uint32_t. */
+int dymu_stack_speed_device(dymu_ctx* ctx, const double* src, uint64_t src_ld,
+                            uint64_t src_plane_stride, uint32_t nx, uint32_t ny, uint32_t B,
+                            double* dF_stack, uint64_t ld, void* stream);
+/* The cold multi-source solve (dymu_solve_seeds_device) of the whole stack: every plane
+ * converges to the map its own seeds give on its own speed.  seeds: HOST array; several
+ * seeds with offsets per plane are allowed (a batch of goal sets).  deterministic and
+ * exact_sqrt as for any solve; stats are those of the stacked domain.  DYMU_ERR_ARG: B = 0,
+ * ld < nx, a seed with plane >= B or off its plane, t0 negative, NaN or infinite, a plane
+ * without a seed, B * P not fitting in uint32_t.  Blocks until converged. */
+int dymu_solve_batch_device(dymu_ctx* ctx, const double* dF_stack, double* dT_stack, uint32_t nx,
+                            uint32_t ny, uint32_t B, uint64_t ld, const dymu_batch_seed* seeds,
+                            uint32_t n_seeds, void* stream, dymu_stats* stats);
+/* DyMuPathPlanner::getTotalCost on the device: d_out[b * M + m] (device) = what the
+ * planner returns for point d_xy[2m], d_xy[2m+1] (device; grid-local metres) on plane b
+ * taken as a converged map of resolution res -- the nearest node (or +inf) where a corner
+ * of the point's cell is off the grid, the nearest node where a corner is not finite, else
+ * the reference's bilinear expression; bit-identical to the host's on the same values.
+ * Asynchronous on `stream`. */
+int dymu_gather_costs_device(dymu_ctx* ctx, const double* dT_stack, uint32_t nx, uint32_t ny,
+                             uint32_t B, uint64_t ld, double res, const double* d_xy, uint32_t M,
+                             double* d_out, void* stream);
+
 /* ---- row-slab domains (multi-GPU sharding; also single-GPU virtual slabs) ----
  * A rank owns rows [row0, row0+nrows) of an nx-wide global grid.  T points at
  * its first owned row; with ghost_lo the row above it (T - ld) holds the

@@ -94,6 +94,32 @@ int dymu_planner_last_path_sinks(dymu_planner* p, int* out, int n);
 int dymu_planner_last_paths_on_device(dymu_planner* p);
 /* its kernel time (HIP events, ms; 0 on the host route) */
 int dymu_planner_last_paths_kernel_ms(dymu_planner* p, double* ms);
+/* ---- batched total-cost maps (DyMuPathPlanner::computeTotalCostMaps) ----
+ * One map per goal (n x (x, y, z, heading)) on the current speed, solved together and
+ * kept on the device, next to -- not instead of -- the single goal's map.  1 = solved,
+ * 0 = rejected (a goal dymu_planner_set_goal would reject, or no device engine: nothing
+ * changed). */
+int dymu_planner_compute_total_cost_maps(dymu_planner* p, const double* goals_xyzh, int n);
+/* maps in the batch (0: none, or dropped by a speed change / a new grid) */
+int dymu_planner_batch_count(dymu_planner* p);
+/* map b (ny*nx, row-major): raw != 0 +inf for unreachable cells, else -1.  1 = copied,
+ * 0 = no such map. */
+int dymu_planner_copy_batch_total_cost(dymu_planner* p, uint32_t b, double* out, int raw);
+/* out[b * n + m] = dymu_planner_get_total_cost of point m (n x (x, y)) on map b, for
+ * every map of the batch (out: batch_count * n doubles).  1 = written, 0 = no batch. */
+int dymu_planner_get_total_costs(dymu_planner* p, const double* points_xy, int n, double* out);
+/* both of the above in one call: out (n_goals * n_targets) = the traverse-cost matrix */
+int dymu_planner_cost_matrix(dymu_planner* p, const double* goals_xyzh, int n_goals,
+                             const double* targets_xy, int n_targets, double* out);
+/* dymu_planner_get_paths on map b with goal b as the sink: same arguments, same
+ * two-call protocol, same status values.  DYMU_ERR_ARG for b >= batch_count. */
+int dymu_planner_get_paths_to(dymu_planner* p, uint32_t b, const double* starts_xyzh, int n,
+                              int max_wp, int stride, double* out_xyzh, int* counts, int* status);
+/* goalI() / goalJ(): the single goal's cell (goal 0 of a goal set); 1 = written, 0 = no
+ * goal set yet */
+int dymu_planner_goal_cell(dymu_planner* p, uint32_t* i, uint32_t* j);
+/* statistics of the last batch solve (those of the stacked domain) */
+int dymu_planner_last_batch_stats(dymu_planner* p, dymu_stats* out);
 /* getLocomotionMode (:788-795) into buf (NUL-terminated) */
 int dymu_planner_get_locomotion_mode(dymu_planner* p, double x, double y, double z, double heading,
                                      char* buf, int buflen);

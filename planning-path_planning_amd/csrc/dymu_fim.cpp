@@ -1624,6 +1624,84 @@ int dymu_solve_seeds_device(dymu_ctx* c, const double* dF, double* dT, uint32_t 
   return solve_seeds_core(c, dF, dT, nx, ny, ld, seeds, n_seeds, pick_stream(c, stream), stats);
 }
 
+// ---- batched solves (batch_kernels.hip) ----
+
+uint32_t dymu_batch_plane_rows(uint32_t ny) {
+  return (uint32_t)(16ull * (((uint64_t)ny + 1 + 15) / 16));
+}
+
+namespace {
+// the stack's rows B * P when the arguments describe a stack the engine can address
+bool batch_rows(uint32_t nx, uint32_t ny, uint32_t B, uint64_t ld, uint32_t* rows) {
+  if (nx == 0 || ny == 0 || B == 0 || ld < nx) return false;
+  const uint64_t r = (uint64_t)B * (16ull * (((uint64_t)ny + 16) / 16));  // B * P in 64 bits
+  if (r > 0xFFFFFFFFull) return false;
+  *rows = (uint32_t)r;
+  return true;
+}
+}  // namespace
+
+int dymu_stack_speed_device(dymu_ctx* c, const double* src, uint64_t src_ld,
+                            uint64_t src_plane_stride, uint32_t nx, uint32_t ny, uint32_t B,
+                            double* dF_stack, uint64_t ld, void* stream) {
+  uint32_t rows = 0;
+  if (!c || !src || !dF_stack || src_ld < nx || !batch_rows(nx, ny, B, ld, &rows))
+    return DYMU_ERR_ARG;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, launch_stack_speed(src, src_ld, src_plane_stride, nx, ny, B, dymu_batch_plane_rows(ny),
+                             dF_stack, ld, pick_stream(c, stream)));
+  return DYMU_OK;
+}
+
+int dymu_solve_batch_device(dymu_ctx* c, const double* dF_stack, double* dT_stack, uint32_t nx,
+                            uint32_t ny, uint32_t B, uint64_t ld, const dymu_batch_seed* seeds,
+                            uint32_t n_seeds, void* stream, dymu_stats* stats) {
+  uint32_t rows = 0;
+  if (!c || !dF_stack || !dT_stack || !seeds || n_seeds == 0 || n_seeds >= (1u << 31) ||
+      !batch_rows(nx, ny, B, ld, &rows))
+    return DYMU_ERR_ARG;
+  const uint32_t P = dymu_batch_plane_rows(ny);
+  // the seeds on stacked rows; every plane needs one (an unseeded plane would stay +inf)
+  std::vector<dymu_seed> s(n_seeds);
+  std::vector<uint8_t> seeded(B, 0);
+  for (uint32_t k = 0; k < n_seeds; ++k) {
+    const dymu_batch_seed& b = seeds[k];
+    if (b.plane >= B || b.i >= nx || b.j >= ny || !(b.t0 >= 0.0) || !(b.t0 < __builtin_inf()))
+      return DYMU_ERR_ARG;
+    seeded[b.plane] = 1;
+    s[k] = dymu_seed{b.i, b.plane * P + b.j, b.t0};
+  }
+  for (uint32_t b = 0; b < B; ++b)
+    if (!seeded[b]) return DYMU_ERR_ARG;
+  HIPC(c, hipSetDevice(c->device));
+  // The per-pass relax target is the one any solve of an nx x rows domain gets
+  // (dom_begin); DYMU_BATCH_TARGET_PER_CU (tiles per CU, development) overrides it for
+  // this entry point alone -- the measurements of DESIGN.md s5.7 found no better value.
+  const uint32_t saved = c->prio_target;
+  if (saved == 0)
+    if (const char* kv = std::getenv("DYMU_BATCH_TARGET_PER_CU")) {
+      const long v = std::atol(kv);
+      if (v > 0 && v < 4096) c->prio_target = (uint32_t)c->cu_count * (uint32_t)v;
+    }
+  const int rc = solve_seeds_core(c, dF_stack, dT_stack, nx, rows, ld, s.data(), n_seeds,
+                                  pick_stream(c, stream), stats);
+  c->prio_target = saved;
+  return rc;
+}
+
+int dymu_gather_costs_device(dymu_ctx* c, const double* dT_stack, uint32_t nx, uint32_t ny,
+                             uint32_t B, uint64_t ld, double res, const double* d_xy, uint32_t M,
+                             double* d_out, void* stream) {
+  uint32_t rows = 0;
+  if (!c || !dT_stack || !batch_rows(nx, ny, B, ld, &rows)) return DYMU_ERR_ARG;
+  if (!(res > 0) || !(res < HUGE_VAL) || (M && (!d_xy || !d_out))) return DYMU_ERR_ARG;
+  if (M == 0) return DYMU_OK;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, launch_gather_costs(dT_stack, ld, nx, ny, B, dymu_batch_plane_rows(ny), res, d_xy, M,
+                              d_out, pick_stream(c, stream)));
+  return DYMU_OK;
+}
+
 int dymu_goal_labels_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
                             const dymu_seed* seeds, uint32_t n_seeds, uint32_t* d_label,
                             void* stream, uint32_t* rounds) {

@@ -361,6 +361,19 @@ hipError_t launch_label_jump(uint32_t* L, uint32_t n, uint32_t* cnt, uint32_t ro
                              hipStream_t st);
 hipError_t launch_label_strip(uint32_t* L, uint32_t n, hipStream_t st);
 
+// batched solves (batch_kernels.hip): `planes` maps of nx x ny stacked at
+// a plane pitch of P rows (dymu_batch_plane_rows), rows ny .. P-1 of each being +inf walls
+// dst (pitch ld, planes * P rows) <- plane b from src + b * src_plane_stride (pitch src_ld;
+// stride 0: one map for all planes), every wall row +inf
+hipError_t launch_stack_speed(const double* src, uint64_t src_ld, uint64_t src_plane_stride,
+                              uint32_t nx, uint32_t ny, uint32_t planes, uint32_t P, double* dst,
+                              uint64_t ld, hipStream_t st);
+// out[b * M + m] = DyMuPathPlanner::getTotalCost of point xy[m] (grid-local metres) on
+// plane b of the solved stack T, bit-identical to the host's on the same values
+hipError_t launch_gather_costs(const double* T, uint64_t ld, uint32_t nx, uint32_t ny,
+                               uint32_t planes, uint32_t P, double res, const double* xy,
+                               uint32_t M, double* out, hipStream_t st);
+
 hipError_t launch_prio_init(const double* F, int64_t ld, int64_t nx, int64_t ny,
                            unsigned long long* keys, uint64_t nkeys, uint32_t* hist, uint64_t nhist,
                            unsigned long long* minkey, double* base, double* delta, double kappa,

@@ -60,6 +60,7 @@ void release_engine(dymu_ctx*& ctx, double*& dF, double*& dT, void*& reg, uint64
 
 DyMuPathPlanner::~DyMuPathPlanner() {
   dropLabels();
+  dropBatch();
   release_engine(ctx_, dF_, dT_, registered_, dcells_);
 }
 
@@ -69,6 +70,7 @@ void DyMuPathPlanner::setEngineOptions(const dymu_opts& o) {
   // device buffers go, so T(), getPath and the matrix getters keep working
   if (ctx_ && dT_ && blk_missing_) fetchAll();
   dropLabels();
+  dropBatch();
   release_engine(ctx_, dF_, dT_, registered_, dcells_);
   dev_map_current_ = false;
   solved_ = false;
@@ -110,6 +112,8 @@ bool DyMuPathPlanner::initGlobalLayer(double globalres, double localres, unsigne
   has_goal_ = false;
   goals_.clear();
   dropLabels();
+  dropBatch();
+  pend_ = false;
   current_path.clear();
   // a new grid: new device buffers and an empty total-cost map (every node
   // OPEN at +inf, as the globalNode constructor leaves it)
@@ -521,6 +525,7 @@ void DyMuPathPlanner::ensureEngine() {
     if (dT_) (void)dymu_device_free(ctx_, dT_);
     dF_ = dT_ = nullptr;
     dropLabels();
+    dropBatch();
     dcells_ = 0;
     dev_map_current_ = false;
     void *f = nullptr, *t = nullptr;
@@ -718,7 +723,15 @@ bool DyMuPathPlanner::closedCell(uint64_t k) const {
 bool DyMuPathPlanner::propagate(bool early, unsigned si, unsigned sj) {
   ensureEngine();
   unsigned i0, i1, j0, j1;
-  const bool changed = syncSpeed(i0, i1, j0, j1);
+  bool changed = syncSpeed(i0, i1, j0, j1);
+  if (changed) dropBatch();  // its maps are those of the old speed
+  if (pend_) {  // a change a batch solve synchronised: dT_ has not seen it yet
+    i0 = std::min(i0, pend_i0_), i1 = std::max(i1, pend_i1_);
+    j0 = std::min(j0, pend_j0_), j1 = std::max(j1, pend_j1_);
+    decrease_only_ = decrease_only_ && pend_dec_;
+    changed = true;
+    pend_ = false;
+  }
   const uint64_t n = (uint64_t)nx_ * ny_;
   int rc = DYMU_ERR_STATE;
   if (!early && solved_ && solved_gi_ == goal_i_ && solved_gj_ == goal_j_) {
@@ -1923,7 +1936,8 @@ struct DeviceScratch {
 void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
                                     std::vector<std::vector<base::Waypoint>>& out,
                                     std::vector<int>& st, std::vector<int>& sinks,
-                                    unsigned max_wp, unsigned stride) {
+                                    unsigned max_wp, unsigned stride,
+                                    const PathTarget* target) {
   constexpr uint64_t kOutBytes = 4ull << 30;  // device output of one batch, at most
   const size_t n = starts.size();
   const double tau = std::min(0.4, risk_distance_);
@@ -1932,13 +1946,15 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
       throw std::runtime_error(std::string("dymu: getPaths ") + what + " failed: " +
                                dymu_strerror(rc) + " " + dymu_last_error(ctx_));
   };
+  const double* map = target ? target->map : dT_;
+  const unsigned gi = target ? target->gi : goal_i_, gj = target ? target->gj : goal_j_;
   base::Waypoint sink;
-  sink.position[0] = global_res_ * (double)goal_i_ + global_offset_[0];
-  sink.position[1] = global_res_ * (double)goal_j_ + global_offset_[1];
-  sink.position[2] = elevation_[idx(goal_i_, goal_j_)];
-  sink.heading = goal_heading_;
+  sink.position[0] = global_res_ * (double)gi + global_offset_[0];
+  sink.position[1] = global_res_ * (double)gj + global_offset_[1];
+  sink.position[2] = elevation_[idx(gi, gj)];
+  sink.heading = target ? target->heading : goal_heading_;
   // a goal set: the label map and the goals' sinks on the device, one sink per path back
-  const bool gs = !goals_.empty();
+  const bool gs = !target && !goals_.empty();
   std::vector<base::Waypoint> gsinks;
   std::vector<int32_t> snk;
   double* d_gxy = nullptr;
@@ -1994,9 +2010,8 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
                                               d_snk),
               "kernel");
       else
-        check(dymu_extract_paths_device(ctx_, dT_, nx_, ny_, nx_, global_res_, goal_i_, goal_j_,
-                                        tau, d_xy, m, (uint32_t)cap, stride, d_out, d_cnt, d_st,
-                                        nullptr),
+        check(dymu_extract_paths_device(ctx_, map, nx_, ny_, nx_, global_res_, gi, gj, tau, d_xy,
+                                        m, (uint32_t)cap, stride, d_out, d_cnt, d_st, nullptr),
               "kernel");
       cnt.resize(m);
       sts.resize(m);
@@ -2162,7 +2177,8 @@ bool DyMuPathPlanner::propagateGoals() {
   if (!&dymu_solve_seeds_device)
     throw std::runtime_error("dymu: the engine has no multi-source solve (dymu_solve_seeds_device)");
   unsigned i0, i1, j0, j1;
-  (void)syncSpeed(i0, i1, j0, j1);
+  if (syncSpeed(i0, i1, j0, j1)) dropBatch();
+  pend_ = false;  // a cold solve, and solved_ stays false: no window is reused after it
   const std::vector<dymu_seed> seeds = seedList();
   dev_map_current_ = false;
   solved_ = false;
@@ -2656,6 +2672,160 @@ bool DyMuPathPlanner::loadTotalCostMap(const double* Tin) {
     dev_map_current_ = true;
   }
   return true;
+}
+
+// ---- batched total-cost maps (extension) ----
+
+// The batch entries of the engine C-ABI: null with an engine that predates them (see the
+// path entries above); computeTotalCostMaps then returns false.
+#pragma weak dymu_batch_plane_rows
+#pragma weak dymu_stack_speed_device
+#pragma weak dymu_solve_batch_device
+#pragma weak dymu_gather_costs_device
+
+void DyMuPathPlanner::dropBatch() {
+  if (dT_batch_ && ctx_) (void)dymu_device_free(ctx_, dT_batch_);
+  dT_batch_ = nullptr;
+  batch_goals_.clear();
+  batch_stats_ = dymu_stats{};
+}
+
+// setGoal's tests (:322-357)
+bool DyMuPathPlanner::goalCell(const base::Waypoint& w, unsigned& i, unsigned& j) const {
+  const double px = (w.position[0] - global_offset_[0]) / global_res_;
+  const double py = (w.position[1] - global_offset_[1]) / global_res_;
+  if (!(px >= 0) || !(py >= 0)) return false;
+  i = grid_u32(px + 0.5), j = grid_u32(py + 0.5);
+  if (i >= nx_ || j >= ny_) return false;
+  if (i == 0 || j == 0 || i + 1 >= nx_ || j + 1 >= ny_) return false;
+  const uint64_t k = idx(i, j);
+  return !(is_obstacle_[k] || is_obstacle_[k - nx_] || is_obstacle_[k - 1] || is_obstacle_[k + 1] ||
+           is_obstacle_[k + nx_]);
+}
+
+bool DyMuPathPlanner::computeTotalCostMaps(const std::vector<base::Waypoint>& goals) {
+  if (goals.empty() || goals.size() > 0xffffffffull || nx_ == 0 || ny_ == 0) return false;
+  if (!&dymu_batch_plane_rows || !&dymu_stack_speed_device || !&dymu_solve_batch_device ||
+      !&dymu_gather_costs_device)
+    return false;
+  std::vector<BatchGoal> bg;
+  std::vector<dymu_batch_seed> seeds;
+  for (const base::Waypoint& w : goals) {
+    unsigned i = 0, j = 0;
+    if (!goalCell(w, i, j)) return false;
+    bg.push_back(BatchGoal{i, j, w.heading});
+    seeds.push_back(dymu_batch_seed{(uint32_t)seeds.size(), i, j, 0u, 0.0});
+  }
+  const uint32_t B = (uint32_t)bg.size();
+  const uint64_t P = dymu_batch_plane_rows(ny_);
+  if (P == 0 || (uint64_t)B * P > 0xffffffffull) return false;
+  double *f = nullptr, *t = nullptr;
+  try {
+    ensureEngine();
+    unsigned i0, i1, j0, j1;
+    if (syncSpeed(i0, i1, j0, j1)) {
+      // the batch at hand is that of the old speed; dT_ keeps the old speed's map, so the
+      // changed box waits for the next single-goal solve (propagate)
+      dropBatch();
+      pend_i0_ = pend_ ? std::min(pend_i0_, i0) : i0;
+      pend_i1_ = pend_ ? std::max(pend_i1_, i1) : i1;
+      pend_j0_ = pend_ ? std::min(pend_j0_, j0) : j0;
+      pend_j1_ = pend_ ? std::max(pend_j1_, j1) : j1;
+      pend_dec_ = (pend_ ? pend_dec_ : true) && decrease_only_;
+      pend_ = true;
+    }
+  } catch (const std::exception&) {
+    return false;  // no device engine
+  }
+  const uint64_t bytes = sizeof(double) * (uint64_t)B * P * nx_;
+  void *pf = nullptr, *pt = nullptr;
+  dymu_stats st{};
+  int rc = dymu_device_alloc(ctx_, bytes, &pf);
+  if (rc == DYMU_OK) rc = dymu_device_alloc(ctx_, bytes, &pt);
+  f = static_cast<double*>(pf);
+  t = static_cast<double*>(pt);
+  if (rc == DYMU_OK) rc = dymu_stack_speed_device(ctx_, dF_, nx_, 0, nx_, ny_, B, f, nx_, nullptr);
+  if (rc == DYMU_OK)
+    rc = dymu_solve_batch_device(ctx_, f, t, nx_, ny_, B, nx_, seeds.data(), B, nullptr, &st);
+  if (f) (void)dymu_device_free(ctx_, f);  // the solved stack alone stays resident
+  if (rc != DYMU_OK) {
+    if (t) (void)dymu_device_free(ctx_, t);
+    return false;
+  }
+  dropBatch();
+  dT_batch_ = t;
+  batch_goals_.swap(bg);
+  batch_stats_ = st;
+  return true;
+}
+
+bool DyMuPathPlanner::copyBatchTotalCost(unsigned b, double* out, bool raw) {
+  if (b >= batch_goals_.size() || !out || !ctx_ || !dT_batch_) return false;
+  const uint64_t n = (uint64_t)nx_ * ny_;
+  const double* plane = dT_batch_ + (uint64_t)b * dymu_batch_plane_rows(ny_) * nx_;
+  if (dymu_memcpy_d2h(ctx_, out, plane, sizeof(double) * n) != DYMU_OK)
+    throw std::runtime_error(std::string("dymu: batch download failed: ") + dymu_last_error(ctx_));
+  if (!raw)
+    for (uint64_t k = 0; k < n; ++k)
+      if (out[k] == kInf) out[k] = -1.0;
+  return true;
+}
+
+bool DyMuPathPlanner::getTotalCosts(const std::vector<base::Waypoint>& points,
+                                    std::vector<double>& out) {
+  if (batch_goals_.empty() || !ctx_ || !dT_batch_ || points.size() > 0xffffffffull) return false;
+  const uint32_t B = (uint32_t)batch_goals_.size(), M = (uint32_t)points.size();
+  std::vector<double> res((uint64_t)B * M);
+  if (M) {
+    std::vector<double> xy(2 * (size_t)M);
+    for (uint32_t m = 0; m < M; ++m) {
+      xy[2 * m] = points[m].position[0] - global_offset_[0];
+      xy[2 * m + 1] = points[m].position[1] - global_offset_[1];
+    }
+    auto check = [&](int rc, const char* what) {
+      if (rc != DYMU_OK)
+        throw std::runtime_error(std::string("dymu: getTotalCosts ") + what + " failed: " +
+                                 dymu_strerror(rc) + " " + dymu_last_error(ctx_));
+    };
+    DeviceScratch dev(ctx_);
+    double* d_xy = dev.alloc<double>(xy.size());
+    double* d_out = dev.alloc<double>(res.size());
+    check(dymu_memcpy_h2d(ctx_, d_xy, xy.data(), sizeof(double) * xy.size()), "upload");
+    check(dymu_gather_costs_device(ctx_, dT_batch_, nx_, ny_, B, nx_, global_res_, d_xy, M, d_out,
+                                   nullptr),
+          "kernel");
+    check(dymu_memcpy_d2h(ctx_, res.data(), d_out, sizeof(double) * res.size()), "download");
+  }
+  out.swap(res);
+  return true;
+}
+
+bool DyMuPathPlanner::costMatrix(const std::vector<base::Waypoint>& goals,
+                                 const std::vector<base::Waypoint>& targets,
+                                 std::vector<double>& out) {
+  return computeTotalCostMaps(goals) && getTotalCosts(targets, out);
+}
+
+std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getPathsTo(
+    unsigned b, const std::vector<base::Waypoint>& starts, std::vector<int>* status,
+    unsigned max_wp, unsigned stride) {
+  if (max_wp == 0 || stride == 0) throw std::invalid_argument("getPathsTo: max_wp, stride >= 1");
+  if (b >= batch_goals_.size() || !ctx_ || !dT_batch_ || starts.size() > 0xffffffffull)
+    throw std::invalid_argument("getPathsTo: no such map in the batch");
+  const size_t n = starts.size();
+  std::vector<std::vector<base::Waypoint>> out(n);
+  std::vector<int> st(n, -1), sk(n, -1);
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  if (n) {
+    const BatchGoal& g = batch_goals_[b];
+    const PathTarget tgt{dT_batch_ + (uint64_t)b * dymu_batch_plane_rows(ny_) * nx_, g.i, g.j,
+                         g.heading};
+    pathsOnDevice(starts, out, st, sk, max_wp, stride, &tgt);
+    last_paths_device_ = true;
+  }
+  if (status) status->swap(st);
+  return out;
 }
 
 }  // namespace PathPlanning_lib

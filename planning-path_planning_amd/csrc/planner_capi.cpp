@@ -434,6 +434,89 @@ int dymu_planner_get_paths(dymu_planner* p, const double* starts, int n, int max
   });
 }
 
+namespace {
+std::vector<base::Waypoint> wps(const double* a, int n, int width) {
+  std::vector<base::Waypoint> v((size_t)n);
+  for (int q = 0; q < n; ++q)
+    v[q] = width == 4 ? wp(a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3])
+                      : wp(a[2 * q], a[2 * q + 1], 0, 0);
+  return v;
+}
+}  // namespace
+
+int dymu_planner_compute_total_cost_maps(dymu_planner* p, const double* xyzh, int n) {
+  if (!p || !xyzh || n <= 0) return DYMU_ERR_ARG;
+  return guarded([&] { return (int)p->pl.computeTotalCostMaps(wps(xyzh, n, 4)); });
+}
+
+int dymu_planner_batch_count(dymu_planner* p) {
+  if (!p) return DYMU_ERR_ARG;
+  return (int)p->pl.batchCount();
+}
+
+int dymu_planner_copy_batch_total_cost(dymu_planner* p, uint32_t b, double* out, int raw) {
+  if (!p || !out) return DYMU_ERR_ARG;
+  return guarded([&] { return (int)p->pl.copyBatchTotalCost(b, out, raw != 0); });
+}
+
+int dymu_planner_get_total_costs(dymu_planner* p, const double* xy, int n, double* out) {
+  if (!p || n < 0 || (n > 0 && (!xy || !out))) return DYMU_ERR_ARG;
+  return guarded([&] {
+    std::vector<double> v;
+    if (!p->pl.getTotalCosts(wps(xy, n, 2), v)) return 0;
+    if (!v.empty()) std::memcpy(out, v.data(), sizeof(double) * v.size());
+    return 1;
+  });
+}
+
+int dymu_planner_cost_matrix(dymu_planner* p, const double* goals_xyzh, int n_goals,
+                             const double* targets_xy, int n_targets, double* out) {
+  if (!p || !goals_xyzh || n_goals <= 0 || n_targets < 0 || (n_targets > 0 && (!targets_xy || !out)))
+    return DYMU_ERR_ARG;
+  return guarded([&] {
+    std::vector<double> v;
+    if (!p->pl.costMatrix(wps(goals_xyzh, n_goals, 4), wps(targets_xy, n_targets, 2), v)) return 0;
+    if (!v.empty()) std::memcpy(out, v.data(), sizeof(double) * v.size());
+    return 1;
+  });
+}
+
+int dymu_planner_get_paths_to(dymu_planner* p, uint32_t b, const double* starts, int n, int max_wp,
+                              int stride, double* out, int* counts, int* status) {
+  if (!starts) return dymu_planner_get_paths(p, nullptr, n, max_wp, stride, out, counts, status);
+  if (!p || n < 0 || max_wp <= 0 || stride <= 0 || b >= p->pl.batchCount()) return DYMU_ERR_ARG;
+  const int rc = guarded([&] {
+    p->paths = p->pl.getPathsTo(b, wps(starts, n, 4), &p->paths_status, (unsigned)max_wp,
+                                (unsigned)stride);
+    p->paths_sinks.assign((size_t)n, 0);
+    for (int q = 0; q < n; ++q)
+      if (p->paths_status[q] != 1) p->paths_sinks[q] = -1;
+    return DYMU_OK;
+  });
+  if (rc != DYMU_OK) return rc;
+  // counts / status / the packed copy as dymu_planner_get_paths' second half does them
+  for (int q = 0; q < n; ++q) {
+    if (counts) counts[q] = (int)p->paths[q].size();
+    if (status) status[q] = p->paths_status[q];
+  }
+  if (out) return dymu_planner_get_paths(p, nullptr, n, 0, 0, out, nullptr, nullptr);
+  return n;
+}
+
+int dymu_planner_goal_cell(dymu_planner* p, uint32_t* i, uint32_t* j) {
+  if (!p || !i || !j) return DYMU_ERR_ARG;
+  if (!p->pl.hasGoal()) return 0;
+  *i = p->pl.goalI();
+  *j = p->pl.goalJ();
+  return 1;
+}
+
+int dymu_planner_last_batch_stats(dymu_planner* p, dymu_stats* out) {
+  if (!p || !out) return DYMU_ERR_ARG;
+  *out = p->pl.lastBatchStats();
+  return DYMU_OK;
+}
+
 int dymu_planner_set_goals(dymu_planner* p, const double* xyzh, const double* offsets, int n) {
   if (!p || !xyzh || n <= 0) return DYMU_ERR_ARG;
   return guarded([&] {

@@ -107,6 +107,9 @@ _u32, _u64, _i32, _vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c
 # dymu_seed (include/dymu_fim.h): a source cell and its start value
 SEED_DTYPE = np.dtype([("i", np.uint32), ("j", np.uint32), ("t0", np.float64)], align=True)
 LABEL_NONE = 0xFFFFFFFF
+# dymu_batch_seed: a seed of plane `plane` of a batch
+BATCH_SEED_DTYPE = np.dtype([("plane", np.uint32), ("i", np.uint32), ("j", np.uint32),
+                             ("reserved", np.uint32), ("t0", np.float64)], align=True)
 
 FIM_SYMBOLS = {
     "dymu_create": (_i32, [ctypes.POINTER(_vp), ctypes.POINTER(DymuOpts)]),
@@ -179,6 +182,12 @@ FIM_SYMBOLS = {
                                                _vp, _u32, ctypes.c_double, _vp, _u32, _u32, _u32,
                                                _vp, _vp, _vp, _vp, _vp]),
     "dymu_last_labels_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_batch_plane_rows": (_u32, [_u32]),
+    "dymu_stack_speed_device": (_i32, [_vp, _vp, _u64, _u64, _u32, _u32, _u32, _vp, _u64, _vp]),
+    "dymu_solve_batch_device": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _u32, _vp,
+                                       ctypes.POINTER(DymuStats)]),
+    "dymu_gather_costs_device": (_i32, [_vp, _vp, _u32, _u32, _u32, _u64, ctypes.c_double, _vp,
+                                        _u32, _vp, _vp]),
     "dymu_device_alloc_cached": (_i32, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "dymu_memcpy2d_d2h": (_i32, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
                                  ctypes.c_size_t, ctypes.c_size_t]),
@@ -482,6 +491,48 @@ class Engine:
             out[q, max(cnt[q], 0):] = 0.0
         return out, cnt, st, sink
 
+    # -- batched solves --
+    def stack_speed(self, src: int, src_ld: int, src_plane_stride: int, nx: int, ny: int,
+                    B: int, dF_stack: int, ld: int, stream: int = 0):
+        """dymu_stack_speed_device: the stacked speed of B planes (B * batch_plane_rows(ny)
+        rows of pitch ld) from the maps at src + b * src_plane_stride (0: one shared map),
+        wall rows +inf."""
+        _check(self._lib.dymu_stack_speed_device(self.ctx, src, src_ld, src_plane_stride, nx,
+                                                 ny, B, dF_stack, ld, stream or None), self.ctx)
+
+    def solve_batch_device(self, dF_stack: int, dT_stack: int, nx: int, ny: int, B: int,
+                           ld: int, seeds, stream: int = 0) -> dict:
+        """dymu_solve_batch_device: every plane of the stack converged from its own seeds
+        (plane, i, j[, t0]) in one pass sequence."""
+        a = np.zeros(len(seeds), dtype=BATCH_SEED_DTYPE)
+        for k, s in enumerate(seeds):
+            a[k] = (int(s[0]), int(s[1]), int(s[2]), 0, float(s[3]) if len(s) > 3 else 0.0)
+        st = DymuStats()
+        _check(self._lib.dymu_solve_batch_device(self.ctx, dF_stack, dT_stack, nx, ny, B, ld,
+                                                 a.ctypes.data, len(a), stream or None,
+                                                 ctypes.byref(st)), self.ctx)
+        return st.as_dict()
+
+    def gather_costs(self, dT_stack: int, nx: int, ny: int, B: int, ld: int, res: float,
+                     points_xy, stream: int = 0) -> np.ndarray:
+        """dymu_gather_costs_device for host points (M, 2) in grid-local metres: [B, M], the
+        planner's getTotalCost of every point on every plane of the solved stack."""
+        xy = np.ascontiguousarray(points_xy, dtype=np.float64).reshape(-1, 2)
+        M = len(xy)
+        out = np.zeros((B, M))
+        if M == 0:
+            return out
+        ptrs = [self.alloc(xy.nbytes), self.alloc(out.nbytes)]
+        try:
+            self.h2d(ptrs[0], xy)
+            _check(self._lib.dymu_gather_costs_device(self.ctx, dT_stack, nx, ny, B, ld, res,
+                                                      ptrs[0], M, ptrs[1], None), self.ctx)
+            self.d2h(out, ptrs[1])
+        finally:
+            for p in ptrs:
+                self.free(p)
+        return out
+
     def alloc(self, nbytes: int) -> int:
         p = _vp()
         _check(self._lib.dymu_device_alloc(self.ctx, nbytes, ctypes.byref(p)), self.ctx)
@@ -613,6 +664,11 @@ def slab_rows(ny: int, nranks: int, rank: int):
     return r0.value, n.value
 
 
+def batch_plane_rows(ny: int) -> int:
+    """The plane pitch in rows of a batch of ny-row maps: 16 * ceil((ny + 1) / 16)."""
+    return int(load_fim().dymu_batch_plane_rows(ny))
+
+
 def device_count() -> int:
     return load_fim().dymu_device_count()
 
@@ -647,6 +703,14 @@ PLANNER_SYMBOLS = {
     "dymu_planner_last_path_sinks": (_i32, [_vp, _vp, _i32]),
     "dymu_planner_last_paths_on_device": (_i32, [_vp]),
     "dymu_planner_last_paths_kernel_ms": (_i32, [_vp, ctypes.POINTER(_d)]),
+    "dymu_planner_compute_total_cost_maps": (_i32, [_vp, _vp, _i32]),
+    "dymu_planner_batch_count": (_i32, [_vp]),
+    "dymu_planner_copy_batch_total_cost": (_i32, [_vp, _u32, _dp, _i32]),
+    "dymu_planner_get_total_costs": (_i32, [_vp, _vp, _i32, _vp]),
+    "dymu_planner_cost_matrix": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp]),
+    "dymu_planner_get_paths_to": (_i32, [_vp, _u32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dymu_planner_last_batch_stats": (_i32, [_vp, ctypes.POINTER(DymuStats)]),
+    "dymu_planner_goal_cell": (_i32, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "dymu_planner_get_locomotion_mode": (_i32, [_vp, _d, _d, _d, _d, ctypes.c_char_p, _i32]),
     "dymu_planner_set_hazard_density": (_i32, [_vp, _dp]),
     "dymu_planner_set_trafficability": (_i32, [_vp, _dp]),
@@ -726,7 +790,10 @@ def load_planner() -> ctypes.CDLL:
         if not os.path.exists(path):
             raise DymuError(-5, f"planner library missing: {path} (run __graft_entry__.build())")
         lib = ctypes.CDLL(path)
+        ab_build = "DYMU_LIBDIR" in os.environ  # an older A/B build may lack newer symbols
         for name, (res, args) in PLANNER_SYMBOLS.items():
+            if ab_build and not hasattr(lib, name):
+                continue
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -905,6 +972,86 @@ class Planner:
                                                 None))
         ends = np.cumsum(cnt[:n])
         return [buf[e - c:e].copy() for e, c in zip(ends, cnt[:n])], st[:n].copy()
+
+    # -- batched total-cost maps (DyMuPathPlanner::computeTotalCostMaps) --
+    def computeTotalCostMaps(self, goals) -> bool:
+        """One total-cost map per goal (x, y[, z, heading]) on the current speed, solved
+        together and kept on the device next to the single goal's map.  False (nothing
+        changed) if a goal is rejected or there is no device engine."""
+        g = np.ascontiguousarray([self._wp(w) for w in goals], dtype=np.float64).reshape(-1, 4)
+        if len(g) == 0:
+            return False
+        return _b(self._lib.dymu_planner_compute_total_cost_maps(self.h, g.ctypes.data, len(g)))
+
+    def batchCount(self) -> int:
+        return _b_int(self._lib.dymu_planner_batch_count(self.h))
+
+    def batchTotalCost(self, b: int, raw: bool = True):
+        """Map b of the batch, [ny, nx] (+inf unreachable; raw=False: -1), or None."""
+        out = np.empty((self.ny, self.nx))
+        if b < 0 or not _b(self._lib.dymu_planner_copy_batch_total_cost(self.h, b, out, int(raw))):
+            return None
+        return out
+
+    @staticmethod
+    def _xy(points) -> np.ndarray:
+        return np.ascontiguousarray([(float(w[0]), float(w[1])) for w in points],
+                                    dtype=np.float64).reshape(-1, 2)
+
+    def getTotalCosts(self, points):
+        """[batchCount, len(points)]: getTotalCost of every point on every map of the batch
+        (evaluated on the device), or None without a batch."""
+        xy = self._xy(points)
+        out = np.zeros((self.batchCount(), len(xy)))
+        if not _b(self._lib.dymu_planner_get_total_costs(self.h, xy.ctypes.data, len(xy),
+                                                         out.ctypes.data)):
+            return None
+        return out
+
+    def costMatrix(self, goals, targets):
+        """computeTotalCostMaps(goals) and getTotalCosts(targets) in one call: the
+        [len(goals), len(targets)] traverse-cost matrix, or None on failure."""
+        g = np.ascontiguousarray([self._wp(w) for w in goals], dtype=np.float64).reshape(-1, 4)
+        xy = self._xy(targets)
+        if len(g) == 0:
+            return None
+        out = np.zeros((len(g), len(xy)))
+        if not _b(self._lib.dymu_planner_cost_matrix(self.h, g.ctypes.data, len(g),
+                                                     xy.ctypes.data, len(xy), out.ctypes.data)):
+            return None
+        return out
+
+    def getPathsTo(self, b: int, starts, max_wp: int = 1 << 20, stride: int = 1):
+        """getPaths on map b of the batch, with goal b as the sink: (paths, status)."""
+        s = np.ascontiguousarray([self._wp(w) for w in starts], dtype=np.float64).reshape(-1, 4)
+        n = len(s)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        _b_int(self._lib.dymu_planner_get_paths_to(self.h, b, s.ctypes.data, n, max_wp, stride,
+                                                   None, cnt.ctypes.data, st.ctypes.data))
+        buf = np.empty((max(int(cnt[:n].sum()), 1), 4))
+        _b_int(self._lib.dymu_planner_get_paths_to(self.h, b, None, n, 0, 0, buf.ctypes.data,
+                                                   None, None))
+        ends = np.cumsum(cnt[:n])
+        return [buf[e - c:e].copy() for e, c in zip(ends, cnt[:n])], st[:n].copy()
+
+    def goalCell(self):
+        """(goalI(), goalJ()): the single goal's cell (goal 0 of a goal set), or None."""
+        i, j = _u32(), _u32()
+        if not _b(self._lib.dymu_planner_goal_cell(self.h, ctypes.byref(i), ctypes.byref(j))):
+            return None
+        return i.value, j.value
+
+    def goalI(self) -> int:
+        return self.goalCell()[0]
+
+    def goalJ(self) -> int:
+        return self.goalCell()[1]
+
+    def lastBatchStats(self) -> dict:
+        st = DymuStats()
+        _check(self._lib.dymu_planner_last_batch_stats(self.h, ctypes.byref(st)))
+        return st.as_dict()
 
     def lastPathsOnDevice(self) -> bool:
         """Whether the last getPaths ran on the device (else on the host threads)."""
