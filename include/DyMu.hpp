@@ -323,10 +323,11 @@ class DyMuPathPlanner {
   // setGoal validates its one; offsets must be finite and >= 0, as many as the goals or
   // none.  Any failure returns false and changes nothing.  setGoal clears the set.
   // With a set active computeEntireTotalCostMap and computeTotalCostMap run one cold
-  // multi-source solve of the whole map (dymu_solve_seeds_device; no early exit, no
-  // windowed reuse), getPath / computeGlobalPath / getPaths end at the goal the label
-  // map names for the cell the path is in, and computeLocalPlanning / repairPath with
-  // more than one goal return false / -1.  globalGoal(), goalI(), goalJ() report goal 0.
+  // multi-source solve of the whole map (dymu_solve_seeds_device; no early exit, and no
+  // windowed reuse unless trackSpeedChanges is on), getPath / computeGlobalPath / getPaths
+  // end at the goal the label map names for the cell the path is in, and
+  // computeLocalPlanning / repairPath with more than one goal return false / -1.
+  // globalGoal(), goalI(), goalJ() report goal 0.
   bool setGoals(const std::vector<base::Waypoint>& goals, const std::vector<double>& offsets = {});
   unsigned goalCount() const {
     return !has_goal_ ? 0u : goals_.empty() ? 1u : (unsigned)goals_.size();
@@ -352,6 +353,25 @@ class DyMuPathPlanner {
   bool computeTotalCostMaps(const std::vector<base::Waypoint>& goals);
   unsigned batchCount() const { return (unsigned)batch_goals_.size(); }
   const dymu_stats& lastBatchStats() const { return batch_stats_; }
+  // Windowed re-propagation of the batch and of a goal set's map; off by
+  // default, and with it off every call behaves as described above.  With it on:
+  //  - a speed synchronisation that finds a change keeps the batch and remembers the
+  //    changed box; computeTotalCostMaps with the held goals (same cells, same order) then
+  //    re-propagates every plane from that box (dymu_update_batch_window_device) when it
+  //    covers at most a quarter of the grid, does nothing when no change is pending, and
+  //    solves cold otherwise; the batch readers (getTotalCosts, copyBatchTotalCost,
+  //    getPathsTo) bring the batch up to date first, so none returns a map of the old speed;
+  //  - computeEntireTotalCostMap under a goal set re-propagates the map from the changed
+  //    box (dymu_update_seeds_window_device) when the device holds the converged map of
+  //    the same goals and offsets, reuses it when nothing changed (lastSolveKind() 1 / 2).
+  // initGlobalLayer, setEngineOptions, a changed goal or goal set, loadTotalCostMap,
+  // resetTotalCostMap and an early-exit solve forget the goal set's map.  With an engine
+  // that lacks the update entries the calls behave as with tracking off.
+  void trackSpeedChanges(bool on);
+  bool tracksSpeedChanges() const { return track_; }
+  // How the last computeTotalCostMaps (or the reader that refreshed the batch) ran:
+  // 0 cold solve, 1 windowed re-propagation, 2 batch reused
+  int lastBatchSolveKind() const { return batch_kind_; }
   // plane b (ny*nx, row-major) raw (+inf unreachable) or as getTotalCostMatrix (-1)
   bool copyBatchTotalCost(unsigned b, double* out, bool raw);
   // out[b * points.size() + m] = what getTotalCost(points[m]) returns on map b (the
@@ -485,6 +505,21 @@ class DyMuPathPlanner {
   // old speed: its box joins what the next single-goal solve finds changed
   bool pend_ = false, pend_dec_ = true;
   unsigned pend_i0_ = 0, pend_i1_ = 0, pend_j0_ = 0, pend_j1_ = 0;
+  // trackSpeedChanges: the same bookkeeping for the batch (the box its planes have not
+  // seen yet), and the seed list whose converged map dT_ holds (empty: none)
+  bool track_ = false;
+  int batch_kind_ = 0;
+  bool bpend_ = false, bpend_dec_ = true;
+  unsigned bpend_i0_ = 0, bpend_i1_ = 0, bpend_j0_ = 0, bpend_j1_ = 0;
+  std::vector<dymu_seed> gs_seeds_;
+  // a synchronised change of the box [i0, i1) x [j0, j1): drops the batch, or keeps it
+  // with the box pending (tracking on)
+  void batchSpeedChanged(unsigned i0, unsigned i1, unsigned j0, unsigned j1);
+  // the cold solve of a batch from the current dF_; installs it on success
+  bool solveBatchCold(std::vector<BatchGoal>& bg);
+  // the held batch brought to the current dF_ (windowed where the pending box allows,
+  // else cold); false: it could not be and was dropped
+  bool refreshBatch();
   // goal sets: empty = the single goal of setGoal
   struct Goal {
     unsigned i, j;

@@ -451,6 +451,46 @@ int dymu_update_window_device(dymu_ctx* ctx, const double* dF, double* dT, uint3
  * out[1] tiles visited by them, out[2] cells invalidated (the dependency cone of
  * the window's speed increases; 0s for decrease-only updates), out[3] reserved. */
 int dymu_last_update_stats(dymu_ctx* ctx, uint64_t out[4]);
+/* ---- windowed updates of seeded maps and of stacks ----
+ * dymu_update_window_device for a seed list: dT holds the converged multi-source map of
+ * `seeds` (dymu_solve_seeds_device) under the old speed, dF the new speed, changed only
+ * inside the window; the result is the fixed point dymu_solve_seeds_device reaches on
+ * the new speed.  theta = min(old T over the window and its 1-cell ring); cells below it
+ * keep their value, every other finite cell is reset -- a seed cell to the smallest t0
+ * given for it (a seed is a boundary value, not a goal at 0: a dominated seed in the
+ * reset region comes back as min(t0, what propagates)), any other cell to +inf -- and
+ * re-propagated from the kept region's boundary and the seeds.  decrease_only != 0 as for
+ * dymu_update_window_device: nothing is reset, the window's tiles are queued.  Always
+ * the theta reset (DYMU_RAISE is not consulted: the raise front is single-goal).
+ * dymu_last_update_stats afterwards: out[0] = out[1] = 0, out[2] = the cells whose finite
+ * old value was at or above theta (0 for decrease_only).  seeds: HOST array.  The window
+ * is clipped to the grid.  DYMU_ERR_ARG, before any device work: a null pointer, ld < nx,
+ * dymu_solve_seeds_device's seed rules, w or h = 0, i0 >= nx, j0 >= ny. */
+int dymu_update_seeds_window_device(dymu_ctx* ctx, const double* dF, double* dT, uint32_t nx,
+                                    uint32_t ny, uint64_t ld, const dymu_seed* seeds,
+                                    uint32_t n_seeds, uint32_t i0, uint32_t j0, uint32_t w,
+                                    uint32_t h, int decrease_only, void* stream,
+                                    dymu_stats* stats);
+/* A changed window [i0, i0+w) x [j0, j0+h) of plane `plane` of a batch. */
+typedef struct dymu_batch_window {
+  uint32_t plane, i0, j0, w, h, reserved;
+} dymu_batch_window;
+/* The same for the stack of dymu_solve_batch_device (same layout, same seeds), whose
+ * speed changed only inside `windows` (HOST array; any number per plane, none included;
+ * each clipped to its plane).  The planes are independent, so theta is taken per plane
+ * -- the minimum over all of the plane's windows and their rings -- and keys that
+ * plane's queued tiles; a plane without a window is not read beyond its theta slot and
+ * not written: its map stays bit for bit.  decrease_only != 0 promises it for every
+ * window.  dymu_last_update_stats: out[2] = the reset cells summed over the planes, each
+ * counted against its own plane's theta.  DYMU_ERR_ARG, before any device work: a null
+ * pointer, B = 0, ld < nx, dymu_solve_batch_device's seed rules (a plane without a seed
+ * included), B * P not fitting in uint32_t, n_windows = 0, a window with plane >= B,
+ * w or h = 0, i0 >= nx or j0 >= ny.  Blocks until converged. */
+int dymu_update_batch_window_device(dymu_ctx* ctx, const double* dF_stack, double* dT_stack,
+                                    uint32_t nx, uint32_t ny, uint32_t B, uint64_t ld,
+                                    const dymu_batch_seed* seeds, uint32_t n_seeds,
+                                    const dymu_batch_window* windows, uint32_t n_windows,
+                                    int decrease_only, void* stream, dymu_stats* stats);
 /* Host-buffer form: requires that the previous dymu_solve / dymu_resolve_window
  * on this context solved the same grid size and goal (DYMU_ERR_STATE otherwise);
  * only the window of F is uploaded, the whole new T is written to T_out. */

@@ -120,6 +120,13 @@ int dymu_planner_get_paths_to(dymu_planner* p, uint32_t b, const double* starts_
 int dymu_planner_goal_cell(dymu_planner* p, uint32_t* i, uint32_t* j);
 /* statistics of the last batch solve (those of the stacked domain) */
 int dymu_planner_last_batch_stats(dymu_planner* p, dymu_stats* out);
+/* DyMuPathPlanner::trackSpeedChanges (off by default): with it on a
+ * synchronised speed change keeps the batch and the goal set's map, and the next
+ * compute_total_cost_maps of the same goals / compute_entire_total_cost_map under the
+ * same goal set re-propagates them from the changed box instead of solving cold. */
+int dymu_planner_track_speed_changes(dymu_planner* p, int on);
+/* lastBatchSolveKind(): 0 cold solve, 1 windowed re-propagation, 2 batch reused */
+int dymu_planner_last_batch_solve_kind(dymu_planner* p);
 /* getLocomotionMode (:788-795) into buf (NUL-terminated) */
 int dymu_planner_get_locomotion_mode(dymu_planner* p, double x, double y, double z, double heading,
                                      char* buf, int buflen);

@@ -148,6 +148,9 @@ struct dymu_ctx {
   // update's raise passes, raise visits, cells invalidated
   int raise = 0;
   uint64_t last_update[4] = {0, 0, 0, 0};
+  // theta per plane of the seeded / stacked windowed update (update_planes_core)
+  unsigned long long* d_theta = nullptr;
+  uint32_t theta_cap = 0;
 
   // profiling
   int profiling = 0;
@@ -1189,6 +1192,126 @@ int solve_seeds_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uin
   return converge_auto(c, st, stats);
 }
 
+// ---- windowed re-propagation of seeded maps and stacks ----
+// dT: `planes` converged maps of nx x ny cells at a plane pitch of P rows (one plain map:
+// planes = 1, P = ny) under the old speed; dF: the new speed, changed only inside
+// `wins` (plane-local, clipped, checked by the callers like the seeds, which are on
+// stacked rows).  theta per plane, the reset with the seeds min-written back (or, for
+// decrease_only, the windows' tiles), list 0 keyed by its plane's theta and binned from
+// those keys, then the unchanged passes.  Seeds and windows share ONE reservation of
+// the pinned transfer buffer: a second ensure_xfer may move it under the first.
+int update_planes_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t ny,
+                       uint32_t planes, uint32_t P, uint64_t ld, const dymu_seed* seeds,
+                       uint32_t n_seeds, const BatchWindow* wins, uint32_t n_wins,
+                       bool decrease_only, hipStream_t st, dymu_stats* stats) {
+  std::memset(c->last_update, 0, sizeof c->last_update);
+  const uint32_t rows = planes * P;  // fits (callers)
+  HIPC(c, hipStreamSynchronize(st));  // no earlier kernel still uses the transfer buffer
+  const uint64_t seed_bytes = sizeof(GoalSeed) * (uint64_t)n_seeds;
+  int rc = ensure_xfer(c, seed_bytes + sizeof(BatchWindow) * (uint64_t)n_wins);
+  if (rc) return rc;
+  GoalSeed* hs = static_cast<GoalSeed*>(c->h_xfer);
+  for (uint32_t k = 0; k < n_seeds; ++k) hs[k] = GoalSeed{seeds[k].i, seeds[k].j, seeds[k].t0 + 0.0};
+  std::memcpy(static_cast<char*>(c->h_xfer) + seed_bytes, wins, sizeof(BatchWindow) * (size_t)n_wins);
+  const GoalSeed* d_seeds = static_cast<const GoalSeed*>(c->d_xfer);
+  const BatchWindow* d_wins =
+      reinterpret_cast<const BatchWindow*>(static_cast<const char*>(c->d_xfer) + seed_bytes);
+  uint64_t max_cells = 0;
+  for (uint32_t k = 0; k < n_wins; ++k)
+    max_cells = std::max<uint64_t>(
+        max_cells, (uint64_t)(wins[k].i1 - wins[k].i0 + 2) * (wins[k].j1 - wins[k].j0 + 2));
+  if (c->theta_cap < planes) {
+    if (c->d_theta) (void)hipFree(c->d_theta);
+    c->d_theta = nullptr;
+    c->theta_cap = 0;
+    HIPC(c, hipMalloc(&c->d_theta, sizeof(unsigned long long) * (uint64_t)planes));
+    c->theta_cap = planes;
+  }
+  rc = dom_begin(c, dF, dT, nx, rows, ld, 0, 0, -1, -1, st, /*cold=*/false);
+  if (rc) return rc;
+  auto& D = c->dom;
+  unsigned long long* n_reset = c->d_scratch + 5;
+  PlaneUpdateArgs u{};
+  u.T = dT;
+  u.F = dF;
+  u.ld = (int64_t)ld;
+  u.nx = nx;
+  u.ny = ny;
+  u.P = P;
+  u.rows = rows;
+  u.theta = c->d_theta;
+  u.win = d_wins;
+  u.n_win = n_wins;
+  u.list = D.lists[0];
+  u.counts = D.counts[0];
+  u.shard_cap = D.ntiles;
+  u.tile_epoch = c->d_tile_epoch;
+  u.epoch = D.eb + 1;  // the epoch of list 0 (dom_launch: eb + p + 2 for list p + 1)
+  u.tw = (uint32_t)tile_w(D.variant);
+  u.th = (uint32_t)tile_h(D.variant);
+  u.ntx = (uint32_t)D.a.ntx;
+  u.keys = is_prio(D.variant) ? prio_keys(c, 0) : nullptr;
+  u.n_reset = n_reset;
+  hipError_t e = launch_fill_u64(c->d_theta, planes, 0x7FF0000000000000ull, st);  // +inf bits
+  if (e == hipSuccess) e = launch_store_u64(n_reset, 0ull, st);
+  if (e == hipSuccess)
+    e = launch_windows_min(dT, (int64_t)ld, nx, ny, P, d_wins, n_wins, max_cells, c->d_theta, st);
+  if (e == hipSuccess && decrease_only) e = launch_seed_windows(u, max_cells, st);
+  if (e == hipSuccess && !decrease_only) {
+    e = launch_reset_planes(u, st);
+    SeedArgs a{};  // the seeds back at their t0, their tiles queued (key: min t0 in the tile)
+    a.seeds = d_seeds;
+    a.n = n_seeds;
+    a.T = dT;
+    a.ld = (int64_t)ld;
+    a.nx = nx;
+    a.ny = rows;
+    a.tw = u.tw;
+    a.th = u.th;
+    a.ntx = u.ntx;
+    a.list = u.list;
+    a.counts = u.counts;
+    a.shard_cap = u.shard_cap;
+    a.tile_epoch = u.tile_epoch;
+    a.epoch = u.epoch;
+    a.keys = u.keys;  // no histogram here: list 0 is binned below, the edge columns rebuilt
+    if (e == hipSuccess) e = launch_seed_goals(a, st);
+  }
+  if (e == hipSuccess && is_prio(D.variant)) {
+    // the keys differ between planes: list 0's histogram from its final keys against
+    // base = the smallest theta, as the pass that reads it classifies its tiles
+    e = launch_theta_min_state(c->d_theta, planes, prio_minkey(c, 0), prio_base(c, 0), st);
+    if (e == hipSuccess)
+      e = launch_rehist(D.lists[0], D.counts[0], D.ntiles, prio_keys(c, 0), prio_base(c, 0),
+                        prio_delta(c), prio_hist(c, 0), c->d_hist + (uint64_t)4 * kShards * kBins,
+                        st);
+  }
+  if (e == hipSuccess && D.a.ec)  // the reset and the seeds wrote T
+    e = launch_ec_rebuild(dT, ld, nx, rows, D.a.ec, (uint32_t)D.a.ntx, 0, D.ntiles, st);
+  if (e != hipSuccess) {
+    dom_retire(c);
+    return fail_hip(c, e, "windowed update seeding");
+  }
+  rc = converge_auto(c, st, stats);
+  if (rc) return rc;
+  if (!decrease_only) {
+    unsigned long long h = 0;
+    HIPC(c, hipMemcpyAsync(&h, n_reset, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPC(c, hipStreamSynchronize(st));
+    c->last_update[2] = h;
+  }
+  return DYMU_OK;
+}
+
+// a window clipped to [0, nx) x [0, ny) (64-bit sums); false: an empty or off-grid one
+bool clip_window(uint32_t plane, uint32_t i0, uint32_t j0, uint32_t w, uint32_t h, uint32_t nx,
+                 uint32_t ny, BatchWindow* out) {
+  if (w == 0 || h == 0 || i0 >= nx || j0 >= ny) return false;
+  *out = BatchWindow{plane, i0, j0, (uint32_t)std::min<uint64_t>((uint64_t)i0 + w, nx),
+                     (uint32_t)std::min<uint64_t>((uint64_t)j0 + h, ny), 0u};
+  return true;
+}
+
 int goal_labels_core(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
                      const dymu_seed* seeds, uint32_t n_seeds, uint32_t* d_label, hipStream_t st,
                      uint32_t* rounds) {
@@ -1374,6 +1497,7 @@ int dymu_destroy(dymu_ctx* c) {
   if (c->d_ec) (void)hipFree(c->d_ec);
   if (c->d_lut) (void)hipFree(c->d_lut);
   if (c->d_scratch) (void)hipFree(c->d_scratch);
+  if (c->d_theta) (void)hipFree(c->d_theta);
   if (c->d_xchg) (void)hipFree(c->d_xchg);
   if (c->d_stats) (void)hipFree(c->d_stats);
   if (c->d_F) (void)hipFree(c->d_F);
@@ -1700,6 +1824,59 @@ int dymu_gather_costs_device(dymu_ctx* c, const double* dT_stack, uint32_t nx, u
   HIPC(c, launch_gather_costs(dT_stack, ld, nx, ny, B, dymu_batch_plane_rows(ny), res, d_xy, M,
                               d_out, pick_stream(c, stream)));
   return DYMU_OK;
+}
+
+/* ---- windowed updates of seeded maps and of stacks ---- */
+
+int dymu_update_seeds_window_device(dymu_ctx* c, const double* dF, double* dT, uint32_t nx,
+                                    uint32_t ny, uint64_t ld, const dymu_seed* seeds,
+                                    uint32_t n_seeds, uint32_t i0, uint32_t j0, uint32_t w,
+                                    uint32_t h, int decrease_only, void* stream,
+                                    dymu_stats* stats) {
+  if (!c || !dF || !dT || !seeds || nx == 0 || ny == 0 || ld < nx || n_seeds == 0 ||
+      n_seeds >= (1u << 31))
+    return DYMU_ERR_ARG;
+  for (uint32_t k = 0; k < n_seeds; ++k) {
+    const dymu_seed& s = seeds[k];
+    if (s.i >= nx || s.j >= ny || !(s.t0 >= 0.0) || !(s.t0 < __builtin_inf())) return DYMU_ERR_ARG;
+  }
+  BatchWindow win;
+  if (!clip_window(0, i0, j0, w, h, nx, ny, &win)) return DYMU_ERR_ARG;
+  HIPC(c, hipSetDevice(c->device));
+  return update_planes_core(c, dF, dT, nx, ny, 1, ny, ld, seeds, n_seeds, &win, 1,
+                            decrease_only != 0, pick_stream(c, stream), stats);
+}
+
+int dymu_update_batch_window_device(dymu_ctx* c, const double* dF_stack, double* dT_stack,
+                                    uint32_t nx, uint32_t ny, uint32_t B, uint64_t ld,
+                                    const dymu_batch_seed* seeds, uint32_t n_seeds,
+                                    const dymu_batch_window* windows, uint32_t n_windows,
+                                    int decrease_only, void* stream, dymu_stats* stats) {
+  uint32_t rows = 0;
+  if (!c || !dF_stack || !dT_stack || !seeds || n_seeds == 0 || n_seeds >= (1u << 31) ||
+      !windows || n_windows == 0 || n_windows >= (1u << 31) || !batch_rows(nx, ny, B, ld, &rows))
+    return DYMU_ERR_ARG;
+  const uint32_t P = dymu_batch_plane_rows(ny);
+  std::vector<dymu_seed> s(n_seeds);
+  std::vector<uint8_t> seeded(B, 0);
+  for (uint32_t k = 0; k < n_seeds; ++k) {
+    const dymu_batch_seed& b = seeds[k];
+    if (b.plane >= B || b.i >= nx || b.j >= ny || !(b.t0 >= 0.0) || !(b.t0 < __builtin_inf()))
+      return DYMU_ERR_ARG;
+    seeded[b.plane] = 1;
+    s[k] = dymu_seed{b.i, b.plane * P + b.j, b.t0};
+  }
+  for (uint32_t b = 0; b < B; ++b)
+    if (!seeded[b]) return DYMU_ERR_ARG;
+  std::vector<BatchWindow> wv(n_windows);
+  for (uint32_t k = 0; k < n_windows; ++k) {
+    const dymu_batch_window& q = windows[k];
+    if (q.plane >= B || !clip_window(q.plane, q.i0, q.j0, q.w, q.h, nx, ny, &wv[k]))
+      return DYMU_ERR_ARG;
+  }
+  HIPC(c, hipSetDevice(c->device));
+  return update_planes_core(c, dF_stack, dT_stack, nx, ny, B, P, ld, s.data(), n_seeds, wv.data(),
+                            n_windows, decrease_only != 0, pick_stream(c, stream), stats);
 }
 
 int dymu_goal_labels_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,

@@ -246,6 +246,45 @@ hipError_t launch_seed_window(const UpdateArgs& a, uint32_t i0, uint32_t j0, uin
 hipError_t launch_theta_state(const unsigned long long* theta_bits, unsigned long long* minkey0,
                               double* base0, hipStream_t st);
 
+// windowed re-propagation of seeded maps and of stacks of planes (update_kernels.hip,
+// DESIGN.md s5.8): planes of nx x ny cells at a plane pitch of P rows (one plain map:
+// one plane, P = ny), theta per plane
+struct BatchWindow {  // plane-local [i0, i1) x [j0, j1), clipped to the plane
+  uint32_t plane, i0, j0, i1, j1, pad;
+};
+struct PlaneUpdateArgs {
+  double* T;
+  const double* F;
+  int64_t ld;
+  uint32_t nx, ny, P, rows;         // rows = planes * P
+  const unsigned long long* theta;  // per plane (double bits; +inf: no window)
+  const BatchWindow* win;           // device-readable
+  uint32_t n_win;
+  uint32_t* list;    // list 0 (kShards x shard_cap)
+  uint32_t* counts;  // its kShards counters
+  uint32_t shard_cap;
+  uint32_t* tile_epoch;
+  uint32_t epoch;
+  uint32_t tw, th, ntx;
+  unsigned long long* keys;     // priority kernels: keys of list 0, else null
+  unsigned long long* n_reset;  // += finite cells at or above their plane's theta
+};
+hipError_t launch_fill_u64(unsigned long long* p, uint32_t n, unsigned long long v,
+                           hipStream_t st);
+// theta[plane] = min(theta[plane], min T over each of the plane's windows and its 1-cell
+// ring, clipped to the plane); max_cells: the largest window's cells (grid sizing)
+hipError_t launch_windows_min(const double* T, int64_t ld, uint32_t nx, uint32_t ny, uint32_t P,
+                              const BatchWindow* win, uint32_t n_win, uint64_t max_cells,
+                              unsigned long long* theta, hipStream_t st);
+// every finite cell at or above its plane's theta <- +inf; the tiles where such a cell
+// of finite speed touches a kept finite cell into list 0 with key theta[plane]
+hipError_t launch_reset_planes(const PlaneUpdateArgs& a, hipStream_t st);
+// decrease-only: the tiles that intersect each window into list 0, key theta[plane]
+hipError_t launch_seed_windows(const PlaneUpdateArgs& a, uint64_t max_cells, hipStream_t st);
+// list 0's minkey / histogram origin <- min over the planes' theta (0 if none is finite)
+hipError_t launch_theta_min_state(const unsigned long long* theta, uint32_t planes,
+                                  unsigned long long* minkey0, double* base0, hipStream_t st);
+
 // raise front of a windowed update with speed increases (update_kernels.hip): one
 // pass over the listed 16x16 tiles; every cell whose converged value is no longer
 // supported by the update of its current neighbours under the new speed (u >

@@ -73,7 +73,7 @@ void DyMuPathPlanner::setEngineOptions(const dymu_opts& o) {
   dropBatch();
   release_engine(ctx_, dF_, dT_, registered_, dcells_);
   dev_map_current_ = false;
-  solved_ = false;
+  solved_ = false, gs_seeds_.clear();
   speed_valid_ = false;
   markDirty(0, ny_);
 }
@@ -94,7 +94,7 @@ bool DyMuPathPlanner::initGlobalLayer(double globalres, double localres, unsigne
   local_->reset(res_ratio_);
   local_agent_ = -1;
   reconnecting_index = 0;
-  solved_ = false;
+  solved_ = false, gs_seeds_.clear();
   nx_ = num_nodes_X;
   ny_ = num_nodes_Y;
   global_offset_ = offset;
@@ -437,6 +437,7 @@ bool DyMuPathPlanner::setGoal(base::Waypoint wGoal) {
   goal_j_ = j;
   goal_heading_ = wGoal.heading;
   goals_.clear();
+  gs_seeds_.clear();
   invalidateLabels();
   return true;
 }
@@ -517,7 +518,7 @@ void DyMuPathPlanner::ensureEngine() {
       throw std::runtime_error(std::string("dymu: cannot create the HIP engine: ") +
                                dymu_strerror(rc));
     }
-    solved_ = false;
+    solved_ = false, gs_seeds_.clear();
     speed_valid_ = false;
   }
   if (dcells_ != n) {
@@ -537,7 +538,7 @@ void DyMuPathPlanner::ensureEngine() {
     dF_ = static_cast<double*>(f);
     dT_ = static_cast<double*>(t);
     dcells_ = n;
-    solved_ = false;
+    solved_ = false, gs_seeds_.clear();
     speed_valid_ = false;
     // page-lock the host mirror for full-rate downloads (optional: pageable works)
     if (registered_) (void)dymu_host_unregister(ctx_, registered_);
@@ -724,7 +725,7 @@ bool DyMuPathPlanner::propagate(bool early, unsigned si, unsigned sj) {
   ensureEngine();
   unsigned i0, i1, j0, j1;
   bool changed = syncSpeed(i0, i1, j0, j1);
-  if (changed) dropBatch();  // its maps are those of the old speed
+  if (changed) batchSpeedChanged(i0, i1, j0, j1);  // its maps are those of the old speed
   if (pend_) {  // a change a batch solve synchronised: dT_ has not seen it yet
     i0 = std::min(i0, pend_i0_), i1 = std::max(i1, pend_i1_);
     j0 = std::min(j0, pend_j0_), j1 = std::max(j1, pend_j1_);
@@ -749,7 +750,7 @@ bool DyMuPathPlanner::propagate(bool early, unsigned si, unsigned sj) {
   dev_map_current_ = false;  // until the engine call below succeeds
   invalidateLabels();
   if (rc != DYMU_OK) {
-    solved_ = false;
+    solved_ = false, gs_seeds_.clear();
     rc = early ? dymu_solve_until_device(ctx_, dF_, dT_, nx_, ny_, nx_, goal_i_, goal_j_, si, sj,
                                          nullptr, &t_closed, &stats_)
                : dymu_solve_device(ctx_, dF_, dT_, nx_, ny_, nx_, goal_i_, goal_j_, nullptr,
@@ -781,7 +782,7 @@ bool DyMuPathPlanner::propagate(bool early, unsigned si, unsigned sj) {
   }
   // early exit: the reference's CLOSED set is {T <= t_closed}; the band gets its
   // tentative values; every other cell +inf.  dT_ is no longer a converged map.
-  solved_ = false;
+  solved_ = false, gs_seeds_.clear();
   closed_limit_ = t_closed;
   const auto t0 = std::chrono::steady_clock::now();
   const uint64_t g = idx(goal_i_, goal_j_), s = idx(si, sj);
@@ -1447,7 +1448,7 @@ bool DyMuPathPlanner::exactEarlyExit(unsigned si, unsigned sj, const int64_t box
     if (!node_state_[kg]) band_cells_.push_back(kg);  // the reference's band vector, in order
   propagated_extra_.swap(r.order);
   manual_list_ = true;
-  solved_ = false;
+  solved_ = false, gs_seeds_.clear();
   return r.band > 0;  // :399-407
 }
 
@@ -2108,6 +2109,10 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
 #pragma weak dymu_goal_labels_device
 #pragma weak dymu_extract_paths_goals_device
 #pragma weak dymu_device_alloc_cached
+// ... and the windowed updates of seeded maps and stacks: without them
+// trackSpeedChanges changes nothing
+#pragma weak dymu_update_seeds_window_device
+#pragma weak dymu_update_batch_window_device
 
 bool DyMuPathPlanner::goalsOnDevice() const {
   return &dymu_goal_labels_device && &dymu_extract_paths_goals_device &&
@@ -2139,7 +2144,8 @@ bool DyMuPathPlanner::setGoals(const std::vector<base::Waypoint>& goals,
   goal_i_ = goals_[0].i;
   goal_j_ = goals_[0].j;
   goal_heading_ = goals_[0].heading;
-  solved_ = false;  // no single-goal map is reused under a goal set
+  solved_ = false;  // no single-goal map is reused under a goal set (gs_seeds_: compared
+                    // with the new list by propagateGoals)
   invalidateLabels();
   return true;
 }
@@ -2164,9 +2170,12 @@ base::Waypoint DyMuPathPlanner::sinkWaypoint(size_t k) const {
   return w;
 }
 
-// computeEntireTotalCostMap for a goal set: always the cold multi-source solve; the
-// state is a converged full solve's (every finite node CLOSED, no band), and solved_
-// stays false so that no single-goal window reuse is keyed on this map.
+// computeEntireTotalCostMap for a goal set: the cold multi-source solve -- always,
+// unless trackSpeedChanges is on and dT_ holds the converged map of the same seed list:
+// then the map is re-propagated from the changed box (at most a quarter of the grid,
+// propagate's rule) or reused.  The state is a converged full solve's (every finite
+// node CLOSED, no band), and solved_ stays false so that no single-goal window reuse is
+// keyed on this map.
 bool DyMuPathPlanner::propagateGoals() {
   for (const Goal& g : goals_)
     if (is_obstacle_[idx(g.i, g.j)]) {
@@ -2177,18 +2186,46 @@ bool DyMuPathPlanner::propagateGoals() {
   if (!&dymu_solve_seeds_device)
     throw std::runtime_error("dymu: the engine has no multi-source solve (dymu_solve_seeds_device)");
   unsigned i0, i1, j0, j1;
-  if (syncSpeed(i0, i1, j0, j1)) dropBatch();
-  pend_ = false;  // a cold solve, and solved_ stays false: no window is reused after it
+  bool changed = syncSpeed(i0, i1, j0, j1);
+  if (changed) batchSpeedChanged(i0, i1, j0, j1);
+  if (pend_) {  // a change a batch solve synchronised: dT_ has not seen it yet
+    i0 = std::min(i0, pend_i0_), i1 = std::max(i1, pend_i1_);
+    j0 = std::min(j0, pend_j0_), j1 = std::max(j1, pend_j1_);
+    decrease_only_ = decrease_only_ && pend_dec_;
+    changed = true;
+    pend_ = false;  // and solved_ stays false: no single-goal window is reused after this
+  }
   const std::vector<dymu_seed> seeds = seedList();
+  // trackSpeedChanges: dT_ holds the converged map of this very seed list
+  const bool held = track_ && &dymu_update_seeds_window_device && dev_map_current_ &&
+                    gs_seeds_.size() == seeds.size() &&
+                    std::equal(seeds.begin(), seeds.end(), gs_seeds_.begin(),
+                               [](const dymu_seed& a, const dymu_seed& b) {
+                                 return a.i == b.i && a.j == b.j && a.t0 == b.t0;
+                               });
+  if (held && !changed) {
+    incremental_ = 2;
+    return true;
+  }
+  int rc = DYMU_ERR_STATE;
   dev_map_current_ = false;
-  solved_ = false;
+  solved_ = false, gs_seeds_.clear();
   invalidateLabels();
-  const int rc = dymu_solve_seeds_device(ctx_, dF_, dT_, nx_, ny_, nx_, seeds.data(),
-                                         (uint32_t)seeds.size(), nullptr, &stats_);
-  if (rc != DYMU_OK)
-    throw std::runtime_error(std::string("dymu solve failed: ") + dymu_strerror(rc) + " " +
-                             dymu_last_error(ctx_));
-  incremental_ = 0;
+  if (held && (uint64_t)(i1 - i0) * (j1 - j0) * 4 <= (uint64_t)nx_ * ny_) {
+    rc = dymu_update_seeds_window_device(ctx_, dF_, dT_, nx_, ny_, nx_, seeds.data(),
+                                         (uint32_t)seeds.size(), i0, j0, i1 - i0, j1 - j0,
+                                         decrease_only_ ? 1 : 0, nullptr, &stats_);
+    if (rc == DYMU_OK) incremental_ = 1;
+  }
+  if (rc != DYMU_OK) {
+    rc = dymu_solve_seeds_device(ctx_, dF_, dT_, nx_, ny_, nx_, seeds.data(),
+                                 (uint32_t)seeds.size(), nullptr, &stats_);
+    if (rc != DYMU_OK)
+      throw std::runtime_error(std::string("dymu solve failed: ") + dymu_strerror(rc) + " " +
+                               dymu_last_error(ctx_));
+    incremental_ = 0;
+  }
+  gs_seeds_ = seeds;
   dev_map_current_ = true;
   std::fill(blk_ok_.begin(), blk_ok_.end(), 0);
   blk_missing_ = blk_ok_.size();
@@ -2457,7 +2494,7 @@ void DyMuPathPlanner::resetTotalCostMap() {
   node_state_.assign(total_cost_.size(), 0);
   propagated_extra_.clear();
   manual_list_ = true;
-  solved_ = false;
+  solved_ = false, gs_seeds_.clear();
   dev_map_current_ = false;  // the host copy alone was written
   invalidateLabels();
 }
@@ -2515,7 +2552,7 @@ void DyMuPathPlanner::propagateGlobalNode(unsigned i, unsigned j) {
       band_cells_.push_back(k);  // insertion order, as the reference's vector
     }
     total_cost_[k] = Tn;
-    solved_ = false;  // the device map no longer matches the host's
+    solved_ = false, gs_seeds_.clear();  // the device map no longer matches the host's
     dev_map_current_ = false;
     invalidateLabels();
   }
@@ -2662,7 +2699,7 @@ bool DyMuPathPlanner::loadTotalCostMap(const double* Tin) {
   node_state_.clear();
   propagated_extra_.clear();
   manual_list_ = false;
-  solved_ = false;
+  solved_ = false, gs_seeds_.clear();
   dev_map_current_ = false;
   invalidateLabels();
   if (ctx_ && dT_ && dcells_ == n) {
@@ -2683,11 +2720,37 @@ bool DyMuPathPlanner::loadTotalCostMap(const double* Tin) {
 #pragma weak dymu_solve_batch_device
 #pragma weak dymu_gather_costs_device
 
+// trackSpeedChanges: a pending box is re-propagated through the batch when it covers at
+// most 1 / kBatchWindowDiv of the grid (propagate's rule; DESIGN.md s5.8 has the
+// measurements it rests on), else the batch is solved cold
+constexpr uint64_t kBatchWindowDiv = 4;
+
 void DyMuPathPlanner::dropBatch() {
   if (dT_batch_ && ctx_) (void)dymu_device_free(ctx_, dT_batch_);
   dT_batch_ = nullptr;
   batch_goals_.clear();
   batch_stats_ = dymu_stats{};
+  batch_kind_ = 0;
+  bpend_ = false;
+}
+
+void DyMuPathPlanner::trackSpeedChanges(bool on) {
+  track_ = on;
+  if (!on && bpend_) dropBatch();  // untracked, a batch never outlives a change
+}
+
+void DyMuPathPlanner::batchSpeedChanged(unsigned i0, unsigned i1, unsigned j0, unsigned j1) {
+  if (!dT_batch_) return;
+  if (!track_ || !&dymu_update_batch_window_device) {
+    dropBatch();
+    return;
+  }
+  bpend_i0_ = bpend_ ? std::min(bpend_i0_, i0) : i0;
+  bpend_i1_ = bpend_ ? std::max(bpend_i1_, i1) : i1;
+  bpend_j0_ = bpend_ ? std::min(bpend_j0_, j0) : j0;
+  bpend_j1_ = bpend_ ? std::max(bpend_j1_, j1) : j1;
+  bpend_dec_ = (bpend_ ? bpend_dec_ : true) && decrease_only_;
+  bpend_ = true;
 }
 
 // setGoal's tests (:322-357)
@@ -2709,24 +2772,21 @@ bool DyMuPathPlanner::computeTotalCostMaps(const std::vector<base::Waypoint>& go
       !&dymu_gather_costs_device)
     return false;
   std::vector<BatchGoal> bg;
-  std::vector<dymu_batch_seed> seeds;
   for (const base::Waypoint& w : goals) {
     unsigned i = 0, j = 0;
     if (!goalCell(w, i, j)) return false;
     bg.push_back(BatchGoal{i, j, w.heading});
-    seeds.push_back(dymu_batch_seed{(uint32_t)seeds.size(), i, j, 0u, 0.0});
   }
-  const uint32_t B = (uint32_t)bg.size();
   const uint64_t P = dymu_batch_plane_rows(ny_);
-  if (P == 0 || (uint64_t)B * P > 0xffffffffull) return false;
-  double *f = nullptr, *t = nullptr;
+  if (P == 0 || (uint64_t)bg.size() * P > 0xffffffffull) return false;
   try {
     ensureEngine();
     unsigned i0, i1, j0, j1;
     if (syncSpeed(i0, i1, j0, j1)) {
-      // the batch at hand is that of the old speed; dT_ keeps the old speed's map, so the
-      // changed box waits for the next single-goal solve (propagate)
-      dropBatch();
+      // the batch at hand is that of the old speed (dropped, or kept with the box pending:
+      // trackSpeedChanges); dT_ keeps the old speed's map, so the changed box waits for
+      // the next single-goal solve (propagate)
+      batchSpeedChanged(i0, i1, j0, j1);
       pend_i0_ = pend_ ? std::min(pend_i0_, i0) : i0;
       pend_i1_ = pend_ ? std::max(pend_i1_, i1) : i1;
       pend_j0_ = pend_ ? std::min(pend_j0_, j0) : j0;
@@ -2737,6 +2797,32 @@ bool DyMuPathPlanner::computeTotalCostMaps(const std::vector<base::Waypoint>& go
   } catch (const std::exception&) {
     return false;  // no device engine
   }
+  // trackSpeedChanges: the held batch of these very goals is reused, or re-propagated
+  // from the pending box where that box is small enough (refreshBatch)
+  if (track_ && dT_batch_ && bg.size() == batch_goals_.size() &&
+      std::equal(bg.begin(), bg.end(), batch_goals_.begin(),
+                 [](const BatchGoal& a, const BatchGoal& b) { return a.i == b.i && a.j == b.j; })) {
+    if (!bpend_) {
+      batch_goals_.swap(bg);  // the headings given now
+      batch_kind_ = 2;
+      return true;
+    }
+    if ((uint64_t)(bpend_i1_ - bpend_i0_) * (bpend_j1_ - bpend_j0_) * kBatchWindowDiv <=
+        (uint64_t)nx_ * ny_) {
+      if (!refreshBatch()) return false;
+      batch_goals_.swap(bg);
+      return true;
+    }
+  }
+  return solveBatchCold(bg);
+}
+
+bool DyMuPathPlanner::solveBatchCold(std::vector<BatchGoal>& bg) {
+  const uint32_t B = (uint32_t)bg.size();
+  const uint64_t P = dymu_batch_plane_rows(ny_);
+  std::vector<dymu_batch_seed> seeds;
+  for (const BatchGoal& g : bg) seeds.push_back(dymu_batch_seed{(uint32_t)seeds.size(), g.i, g.j, 0u, 0.0});
+  double *f = nullptr, *t = nullptr;
   const uint64_t bytes = sizeof(double) * (uint64_t)B * P * nx_;
   void *pf = nullptr, *pt = nullptr;
   dymu_stats st{};
@@ -2759,8 +2845,48 @@ bool DyMuPathPlanner::computeTotalCostMaps(const std::vector<base::Waypoint>& go
   return true;
 }
 
+// The held batch on the current speed.  A pending box of at most 1 / kBatchWindowDiv of
+// the grid: F re-stacked from dF_ (temporary) and every plane re-propagated from the box
+// in one call; a larger box, or an update that fails: the cold solve of the same goals.
+bool DyMuPathPlanner::refreshBatch() {
+  if (!bpend_) return true;
+  if (!ctx_ || !dT_batch_) return false;
+  const uint32_t B = (uint32_t)batch_goals_.size();
+  const uint64_t P = dymu_batch_plane_rows(ny_);
+  if (&dymu_update_batch_window_device &&
+      (uint64_t)(bpend_i1_ - bpend_i0_) * (bpend_j1_ - bpend_j0_) * kBatchWindowDiv <=
+          (uint64_t)nx_ * ny_) {
+    std::vector<dymu_batch_seed> seeds;
+    std::vector<dymu_batch_window> wins;
+    for (uint32_t b = 0; b < B; ++b) {
+      seeds.push_back(dymu_batch_seed{b, batch_goals_[b].i, batch_goals_[b].j, 0u, 0.0});
+      wins.push_back(dymu_batch_window{b, bpend_i0_, bpend_j0_, bpend_i1_ - bpend_i0_,
+                                       bpend_j1_ - bpend_j0_, 0u});
+    }
+    void* pf = nullptr;
+    dymu_stats st{};
+    int rc = dymu_device_alloc(ctx_, sizeof(double) * (uint64_t)B * P * nx_, &pf);
+    double* f = static_cast<double*>(pf);
+    if (rc == DYMU_OK) rc = dymu_stack_speed_device(ctx_, dF_, nx_, 0, nx_, ny_, B, f, nx_, nullptr);
+    if (rc == DYMU_OK)
+      rc = dymu_update_batch_window_device(ctx_, f, dT_batch_, nx_, ny_, B, nx_, seeds.data(), B,
+                                           wins.data(), B, bpend_dec_ ? 1 : 0, nullptr, &st);
+    if (f) (void)dymu_device_free(ctx_, f);
+    if (rc == DYMU_OK) {
+      bpend_ = false;
+      batch_stats_ = st;
+      batch_kind_ = 1;
+      return true;
+    }
+  }
+  std::vector<BatchGoal> bg = batch_goals_;
+  if (solveBatchCold(bg)) return true;
+  dropBatch();  // its planes are those of an older speed
+  return false;
+}
+
 bool DyMuPathPlanner::copyBatchTotalCost(unsigned b, double* out, bool raw) {
-  if (b >= batch_goals_.size() || !out || !ctx_ || !dT_batch_) return false;
+  if (b >= batch_goals_.size() || !out || !ctx_ || !dT_batch_ || !refreshBatch()) return false;
   const uint64_t n = (uint64_t)nx_ * ny_;
   const double* plane = dT_batch_ + (uint64_t)b * dymu_batch_plane_rows(ny_) * nx_;
   if (dymu_memcpy_d2h(ctx_, out, plane, sizeof(double) * n) != DYMU_OK)
@@ -2774,6 +2900,7 @@ bool DyMuPathPlanner::copyBatchTotalCost(unsigned b, double* out, bool raw) {
 bool DyMuPathPlanner::getTotalCosts(const std::vector<base::Waypoint>& points,
                                     std::vector<double>& out) {
   if (batch_goals_.empty() || !ctx_ || !dT_batch_ || points.size() > 0xffffffffull) return false;
+  if (!refreshBatch()) return false;
   const uint32_t B = (uint32_t)batch_goals_.size(), M = (uint32_t)points.size();
   std::vector<double> res((uint64_t)B * M);
   if (M) {
@@ -2810,7 +2937,8 @@ std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getPathsTo(
     unsigned b, const std::vector<base::Waypoint>& starts, std::vector<int>* status,
     unsigned max_wp, unsigned stride) {
   if (max_wp == 0 || stride == 0) throw std::invalid_argument("getPathsTo: max_wp, stride >= 1");
-  if (b >= batch_goals_.size() || !ctx_ || !dT_batch_ || starts.size() > 0xffffffffull)
+  if (b >= batch_goals_.size() || !ctx_ || !dT_batch_ || starts.size() > 0xffffffffull ||
+      !refreshBatch())
     throw std::invalid_argument("getPathsTo: no such map in the batch");
   const size_t n = starts.size();
   std::vector<std::vector<base::Waypoint>> out(n);

@@ -517,6 +517,17 @@ int dymu_planner_last_batch_stats(dymu_planner* p, dymu_stats* out) {
   return DYMU_OK;
 }
 
+int dymu_planner_track_speed_changes(dymu_planner* p, int on) {
+  if (!p) return DYMU_ERR_ARG;
+  p->pl.trackSpeedChanges(on != 0);
+  return DYMU_OK;
+}
+
+int dymu_planner_last_batch_solve_kind(dymu_planner* p) {
+  if (!p) return DYMU_ERR_ARG;
+  return p->pl.lastBatchSolveKind();
+}
+
 int dymu_planner_set_goals(dymu_planner* p, const double* xyzh, const double* offsets, int n) {
   if (!p || !xyzh || n <= 0) return DYMU_ERR_ARG;
   return guarded([&] {

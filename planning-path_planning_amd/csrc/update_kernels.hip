@@ -290,6 +290,135 @@ __global__ void k_theta_state(const unsigned long long* theta_bits, unsigned lon
   }
 }
 
+// ---- seeded maps and stacks of planes ----
+// The argument at the top of this file holds per plane of a stack (the planes are
+// independent: the wall rows between them are +inf) and for any boundary condition:
+// theta_b = min old T over plane b's windows and their rings; a cell of plane b below
+// theta_b keeps its value, every other finite cell is reset to +inf -- a seed cell
+// too, which the seed kernels (goal_kernels.hip) then min-write back to its t0: a
+// seed is a boundary value, so a dominated seed (old T < t0) inside the reset region
+// comes back as min(t0, what propagates).  theta_b keys plane b's queued tiles.
+
+// theta[w.plane] = min over window w grown by its ring, clipped to the plane's rows
+// [0, ny): windows by blockIdx.y, a window's cells by blockIdx.x
+__global__ __launch_bounds__(256) void k_windows_min(const double* T, int64_t ld, uint32_t nx,
+                                                     uint32_t ny, uint32_t P,
+                                                     const BatchWindow* win, uint32_t n_win,
+                                                     unsigned long long* theta) {
+  __shared__ unsigned long long s_min;
+  for (uint32_t q = blockIdx.y; q < n_win; q += gridDim.y) {  // block-uniform
+    const BatchWindow bw = win[q];
+    if (bw.i0 >= bw.i1 || bw.j0 >= bw.j1 || bw.i1 > nx || bw.j1 > ny) continue;  // (host-checked)
+    const uint32_t i0 = bw.i0 > 0 ? bw.i0 - 1 : 0, j0 = bw.j0 > 0 ? bw.j0 - 1 : 0;
+    const uint32_t i1 = bw.i1 < nx ? bw.i1 + 1 : nx, j1 = bw.j1 < ny ? bw.j1 + 1 : ny;
+    if (threadIdx.x == 0) s_min = kInfBits;
+    __syncthreads();
+    const uint64_t w = i1 - i0, n = w * (uint64_t)(j1 - j0);
+    const int64_t row0 = (int64_t)bw.plane * P + j0;
+    unsigned long long m = kInfBits;
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n;
+         c += (uint64_t)gridDim.x * blockDim.x) {
+      const unsigned long long b = dbits(T[(row0 + (int64_t)(c / w)) * ld + (i0 + c % w)]);
+      m = b < m ? b : m;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long x = __shfl_xor(m, o);
+      m = x < m ? x : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m != kInfBits) atomicMin(&s_min, m);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_min != kInfBits) atomicMin(&theta[bw.plane], s_min);
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ void plane_queue(const PlaneUpdateArgs& a, uint32_t tile,
+                                            unsigned long long key, uint32_t shard) {
+  if (a.keys) atomicMin(&a.keys[tile], key);
+  if (atomicMax(&a.tile_epoch[tile], a.epoch) < a.epoch) {
+    const uint32_t pos = atomicAdd(&a.counts[shard], 1u);
+    a.list[(uint64_t)shard * a.shard_cap + pos] = tile;
+  }
+}
+
+// k_reset_seed over the stacked rows with theta per plane (plane = row / P) and no
+// exempt cell; a plane whose theta is +inf (no window, or windows over +inf cells
+// only) is neither read nor written.  *n_reset += the finite cells at or above their
+// plane's theta.  The neighbour test's race is k_reset_seed's: kept cells are never
+// written.  Rows ny .. P-1 of a plane are walls (+inf): never kept, never visited.
+__global__ __launch_bounds__(256) void k_reset_planes(PlaneUpdateArgs a) {
+  const uint64_t n = (uint64_t)a.nx * a.rows;
+  const uint32_t shard = blockIdx.x % kShards;
+  unsigned long long cnt = 0;
+  for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n;
+       c += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t j = (uint32_t)(c / a.nx), i = (uint32_t)(c % a.nx);
+    const uint32_t plane = j / a.P, jl = j - plane * a.P;
+    if (jl >= a.ny) continue;
+    const unsigned long long tb = a.theta[plane];
+    if (tb == kInfBits) continue;
+    const double theta = __longlong_as_double((long long)tb);
+    const int64_t k = (int64_t)j * a.ld + i;
+    const double old = a.T[k];
+    if (!(old >= theta)) continue;  // kept
+    if (old < __builtin_inf()) {
+      a.T[k] = __builtin_inf();
+      ++cnt;
+    }
+    if (!(a.F[k] < __builtin_inf())) continue;  // obstacle: never updated
+    bool seed = false;
+    if (jl > 0) seed |= a.T[k - a.ld] < theta;
+    if (i > 0) seed |= a.T[k - 1] < theta;
+    if (i + 1 < a.nx) seed |= a.T[k + 1] < theta;
+    if (jl + 1 < a.ny) seed |= a.T[k + a.ld] < theta;
+    if (seed) plane_queue(a, (j / a.th) * a.ntx + (i / a.tw), tb, shard);
+  }
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(a.n_reset, cnt);
+}
+
+// k_seed_window for every window of the list, key = its plane's theta
+__global__ __launch_bounds__(256) void k_seed_windows(PlaneUpdateArgs a) {
+  const uint32_t shard = (blockIdx.x + blockIdx.y) % kShards;
+  for (uint32_t q = blockIdx.y; q < a.n_win; q += gridDim.y) {
+    const BatchWindow bw = a.win[q];
+    if (bw.i0 >= bw.i1 || bw.j0 >= bw.j1 || bw.i1 > a.nx || bw.j1 > a.ny) continue;
+    const uint64_t r0 = (uint64_t)bw.plane * a.P + bw.j0, r1 = (uint64_t)bw.plane * a.P + bw.j1;
+    const uint32_t tx0 = bw.i0 / a.tw, tx1 = (bw.i1 + a.tw - 1) / a.tw;
+    const uint32_t ty0 = (uint32_t)(r0 / a.th), ty1 = (uint32_t)((r1 + a.th - 1) / a.th);
+    const uint32_t w = tx1 - tx0;
+    const uint64_t n = (uint64_t)w * (ty1 - ty0);
+    const unsigned long long tb = a.theta[bw.plane];
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n;
+         c += (uint64_t)gridDim.x * blockDim.x)
+      plane_queue(a, (ty0 + (uint32_t)(c / w)) * a.ntx + (tx0 + (uint32_t)(c % w)), tb, shard);
+  }
+}
+
+// list 0's minkey and histogram origin: the smallest theta of the stack
+__global__ __launch_bounds__(256) void k_theta_min_state(const unsigned long long* theta,
+                                                         uint32_t planes,
+                                                         unsigned long long* minkey0,
+                                                         double* base0) {
+  __shared__ unsigned long long s_min;
+  if (threadIdx.x == 0) s_min = kInfBits;
+  __syncthreads();
+  unsigned long long m = kInfBits;
+  for (uint32_t b = threadIdx.x; b < planes; b += blockDim.x) m = theta[b] < m ? theta[b] : m;
+  if (m != kInfBits) atomicMin(&s_min, m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    *minkey0 = s_min;
+    const double th = __longlong_as_double((long long)s_min);
+    *base0 = th < __builtin_inf() ? th : 0.0;
+  }
+}
+
+__global__ void k_fill_u64(unsigned long long* p, uint32_t n, unsigned long long v) {
+  for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x)
+    p[k] = v;
+}
+
 // ---- early exit of computeTotalCostMap (reference :364-408) ----
 
 __global__ void k_probe(const double* T, int64_t ld, ProbeCells cells,
@@ -523,6 +652,57 @@ hipError_t launch_cone_seed(const UpdateArgs& a, unsigned long long* theta_bits,
 hipError_t launch_theta_state(const unsigned long long* theta_bits, unsigned long long* minkey0,
                               double* base0, hipStream_t st) {
   hipLaunchKernelGGL(k_theta_state, dim3(1), dim3(64), 0, st, theta_bits, minkey0, base0);
+  return hipGetLastError();
+}
+
+hipError_t launch_fill_u64(unsigned long long* p, uint32_t n, unsigned long long v,
+                           hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  uint32_t b = (n + 255u) / 256u;
+  if (b > 1024u) b = 1024u;
+  hipLaunchKernelGGL(k_fill_u64, dim3(b), dim3(256), 0, st, p, n, v);
+  return hipGetLastError();
+}
+
+// windows by blockIdx.y; a window's cells / tiles by blockIdx.x: many small windows (a
+// batch: one per plane) and one large one (a quarter of a grid) both fill the device
+static dim3 window_grid(uint32_t n_win, uint64_t per_window) {
+  uint32_t gy = n_win < 4096u ? n_win : 4096u;
+  uint64_t gx = (per_window + 255) / 256;
+  const uint64_t cap = 8192u / gy ? 8192u / gy : 1u;
+  if (gx > cap) gx = cap;
+  if (gx == 0) gx = 1;
+  return dim3((unsigned)gx, gy);
+}
+
+hipError_t launch_windows_min(const double* T, int64_t ld, uint32_t nx, uint32_t ny, uint32_t P,
+                              const BatchWindow* win, uint32_t n_win, uint64_t max_cells,
+                              unsigned long long* theta, hipStream_t st) {
+  if (n_win == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_windows_min, window_grid(n_win, max_cells), dim3(256), 0, st, T, ld, nx, ny,
+                     P, win, n_win, theta);
+  return hipGetLastError();
+}
+
+hipError_t launch_reset_planes(const PlaneUpdateArgs& a, hipStream_t st) {
+  uint64_t b = ((uint64_t)a.nx * a.rows + 255) / 256;
+  if (b > 8192) b = 8192;
+  if (b == 0) b = 1;
+  hipLaunchKernelGGL(k_reset_planes, dim3((unsigned)b), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_seed_windows(const PlaneUpdateArgs& a, uint64_t max_cells, hipStream_t st) {
+  if (a.n_win == 0) return hipSuccess;
+  // at most one tile per 64 cells of a window, plus the partial tiles around it
+  hipLaunchKernelGGL(k_seed_windows, window_grid(a.n_win, max_cells / 64 + 256), dim3(256), 0, st,
+                     a);
+  return hipGetLastError();
+}
+
+hipError_t launch_theta_min_state(const unsigned long long* theta, uint32_t planes,
+                                  unsigned long long* minkey0, double* base0, hipStream_t st) {
+  hipLaunchKernelGGL(k_theta_min_state, dim3(1), dim3(256), 0, st, theta, planes, minkey0, base0);
   return hipGetLastError();
 }
 

@@ -110,6 +110,10 @@ LABEL_NONE = 0xFFFFFFFF
 # dymu_batch_seed: a seed of plane `plane` of a batch
 BATCH_SEED_DTYPE = np.dtype([("plane", np.uint32), ("i", np.uint32), ("j", np.uint32),
                              ("reserved", np.uint32), ("t0", np.float64)], align=True)
+# dymu_batch_window: a changed window of plane `plane` of a batch
+BATCH_WINDOW_DTYPE = np.dtype([("plane", np.uint32), ("i0", np.uint32), ("j0", np.uint32),
+                               ("w", np.uint32), ("h", np.uint32), ("reserved", np.uint32)],
+                              align=True)
 
 FIM_SYMBOLS = {
     "dymu_create": (_i32, [ctypes.POINTER(_vp), ctypes.POINTER(DymuOpts)]),
@@ -188,6 +192,11 @@ FIM_SYMBOLS = {
                                        ctypes.POINTER(DymuStats)]),
     "dymu_gather_costs_device": (_i32, [_vp, _vp, _u32, _u32, _u32, _u64, ctypes.c_double, _vp,
                                         _u32, _vp, _vp]),
+    "dymu_update_seeds_window_device": (_i32, [_vp, _vp, _vp, _u32, _u32, _u64, _vp, _u32, _u32,
+                                               _u32, _u32, _u32, _i32, _vp,
+                                               ctypes.POINTER(DymuStats)]),
+    "dymu_update_batch_window_device": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _u32,
+                                               _vp, _u32, _i32, _vp, ctypes.POINTER(DymuStats)]),
     "dymu_device_alloc_cached": (_i32, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "dymu_memcpy2d_d2h": (_i32, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
                                  ctypes.c_size_t, ctypes.c_size_t]),
@@ -513,6 +522,38 @@ class Engine:
                                                  ctypes.byref(st)), self.ctx)
         return st.as_dict()
 
+    # -- windowed updates of seeded maps and stacks --
+    def update_seeds_window_device(self, dF: int, dT: int, nx: int, ny: int, ld: int, seeds,
+                                   i0: int, j0: int, w: int, h: int,
+                                   decrease_only: bool = False, stream: int = 0) -> dict:
+        """dymu_update_seeds_window_device: dT, the converged map of the seeds (i, j[, t0])
+        under the old speed, brought to the new speed dF, changed only inside the window."""
+        a = self._seeds(seeds)
+        st = DymuStats()
+        _check(self._lib.dymu_update_seeds_window_device(
+            self.ctx, dF, dT, nx, ny, ld, a.ctypes.data if len(a) else None, len(a), i0, j0, w,
+            h, int(bool(decrease_only)), stream or None, ctypes.byref(st)), self.ctx)
+        return st.as_dict()
+
+    def update_batch_window_device(self, dF_stack: int, dT_stack: int, nx: int, ny: int, B: int,
+                                   ld: int, seeds, windows, decrease_only: bool = False,
+                                   stream: int = 0) -> dict:
+        """dymu_update_batch_window_device: the solved stack of solve_batch_device (same
+        seeds (plane, i, j[, t0])) brought to the new stacked speed, changed only inside
+        the windows (plane, i0, j0, w, h) -- any number per plane, none included."""
+        a = np.zeros(len(seeds), dtype=BATCH_SEED_DTYPE)
+        for k, s in enumerate(seeds):
+            a[k] = (int(s[0]), int(s[1]), int(s[2]), 0, float(s[3]) if len(s) > 3 else 0.0)
+        wn = np.zeros(len(windows), dtype=BATCH_WINDOW_DTYPE)
+        for k, q in enumerate(windows):
+            wn[k] = (int(q[0]), int(q[1]), int(q[2]), int(q[3]), int(q[4]), 0)
+        st = DymuStats()
+        _check(self._lib.dymu_update_batch_window_device(
+            self.ctx, dF_stack, dT_stack, nx, ny, B, ld, a.ctypes.data if len(a) else None,
+            len(a), wn.ctypes.data if len(wn) else None, len(wn), int(bool(decrease_only)),
+            stream or None, ctypes.byref(st)), self.ctx)
+        return st.as_dict()
+
     def gather_costs(self, dT_stack: int, nx: int, ny: int, B: int, ld: int, res: float,
                      points_xy, stream: int = 0) -> np.ndarray:
         """dymu_gather_costs_device for host points (M, 2) in grid-local metres: [B, M], the
@@ -710,6 +751,8 @@ PLANNER_SYMBOLS = {
     "dymu_planner_cost_matrix": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp]),
     "dymu_planner_get_paths_to": (_i32, [_vp, _u32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dymu_planner_last_batch_stats": (_i32, [_vp, ctypes.POINTER(DymuStats)]),
+    "dymu_planner_track_speed_changes": (_i32, [_vp, _i32]),
+    "dymu_planner_last_batch_solve_kind": (_i32, [_vp]),
     "dymu_planner_goal_cell": (_i32, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "dymu_planner_get_locomotion_mode": (_i32, [_vp, _d, _d, _d, _d, ctypes.c_char_p, _i32]),
     "dymu_planner_set_hazard_density": (_i32, [_vp, _dp]),
@@ -1052,6 +1095,15 @@ class Planner:
         st = DymuStats()
         _check(self._lib.dymu_planner_last_batch_stats(self.h, ctypes.byref(st)))
         return st.as_dict()
+
+    def trackSpeedChanges(self, on: bool = True):
+        """Keep the batch and a goal set's map across synchronised speed changes and
+        re-propagate them from the changed box; off by default."""
+        _check(self._lib.dymu_planner_track_speed_changes(self.h, int(bool(on))))
+
+    def lastBatchSolveKind(self) -> int:
+        """0 cold batch solve, 1 windowed re-propagation, 2 batch reused."""
+        return _b_int(self._lib.dymu_planner_last_batch_solve_kind(self.h))
 
     def lastPathsOnDevice(self) -> bool:
         """Whether the last getPaths ran on the device (else on the host threads)."""
