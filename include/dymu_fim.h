@@ -134,7 +134,8 @@ int dymu_early_exit_mask(dymu_ctx* ctx, const double* dF, double* dT, uint32_t n
 /* *count = the number of cells of dT whose value is bitwise `value` (the early
  * exit's tie test: cells of exactly t_closed other than the last one the
  * reference closes make its CLOSED set depend on its insertion order).
- * Synchronises `stream`. */
+ * Synchronises `stream`.  DYMU_ERR_ARG (here and in dymu_find_equal): a null pointer,
+ * nx or ny = 0, ld < nx. */
 int dymu_count_equal(dymu_ctx* ctx, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
                      double value, uint64_t* count, void* stream);
 /* dymu_count_equal that also lists the cells: *count = their number, idx (host,

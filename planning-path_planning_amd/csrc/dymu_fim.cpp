@@ -1577,7 +1577,7 @@ int dymu_early_exit_mask(dymu_ctx* c, const double* dF, double* dT, uint32_t nx,
 
 int dymu_count_equal(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
                      double value, uint64_t* count, void* stream) {
-  if (!c || !dT || !count || ld < nx) return DYMU_ERR_ARG;
+  if (!c || !dT || !count || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
   HIPC(c, hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, stream);
   unsigned long long* cnt = c->d_scratch + 4;
@@ -1591,7 +1591,7 @@ int dymu_count_equal(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, ui
 
 int dymu_find_equal(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
                     double value, uint64_t* idx, uint64_t cap, uint64_t* count, void* stream) {
-  if (!c || !dT || !count || ld < nx || (cap && !idx)) return DYMU_ERR_ARG;
+  if (!c || !dT || !count || nx == 0 || ny == 0 || ld < nx || (cap && !idx)) return DYMU_ERR_ARG;
   HIPC(c, hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, stream);
   HIPC(c, hipStreamSynchronize(st));  // no earlier kernel still uses the transfer buffer

@@ -361,6 +361,24 @@ class Engine:
                                          cap, ctypes.byref(n), None), self.ctx)
         return n.value, idx[:min(n.value, cap)]
 
+    def count_equal(self, dT: int, nx: int, ny: int, ld: int, value: float) -> int:
+        """The number of cells whose value is bitwise `value` (dymu_count_equal)."""
+        n = _u64()
+        _check(self._lib.dymu_count_equal(self.ctx, dT, nx, ny, ld, float(value),
+                                          ctypes.byref(n), None), self.ctx)
+        return n.value
+
+    def early_exit_mask(self, dF: int, dT: int, nx: int, ny: int, ld: int, tc: float, cap: int):
+        """dymu_early_exit_mask on the device map dT: (n_band, indices j * nx + i of the
+        first min(n_band, cap) band cells, in no particular order).  cap = 0 passes no
+        buffer: the map is masked and only the count comes back."""
+        idx = np.zeros(cap, dtype=np.uint64)
+        n = _u64()
+        _check(self._lib.dymu_early_exit_mask(self.ctx, dF, dT, nx, ny, ld, float(tc),
+                                              idx.ctypes.data if cap else None, cap,
+                                              ctypes.byref(n), None), self.ctx)
+        return n.value, idx[:min(n.value, cap)]
+
     def scatter(self, dT: int, nx: int, ld: int, idx: np.ndarray, vals: np.ndarray):
         """T[idx // nx, idx % nx] = vals on the device (dymu_scatter)."""
         idx = np.ascontiguousarray(idx, dtype=np.uint64)

@@ -142,7 +142,7 @@ int dymu_early_exit_mask(dymu_ctx* c, const double* F, double* T, uint32_t nx, u
 int dymu_count_equal(dymu_ctx* c, const double* T, uint32_t nx, uint32_t ny, uint64_t ld,
                      double v, uint64_t* count, void* s) {
   (void)s;
-  if (!c || !count) return DYMU_ERR_ARG;
+  if (!c || !count || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
   uint64_t n = 0;
   for (uint32_t j = 0; j < ny; ++j)
     for (uint32_t i = 0; i < nx; ++i) n += memcmp(&T[(uint64_t)j * ld + i], &v, sizeof v) == 0;
@@ -152,7 +152,7 @@ int dymu_count_equal(dymu_ctx* c, const double* T, uint32_t nx, uint32_t ny, uin
 int dymu_find_equal(dymu_ctx* c, const double* T, uint32_t nx, uint32_t ny, uint64_t ld,
                     double v, uint64_t* idx, uint64_t cap, uint64_t* count, void* s) {
   (void)s;
-  if (!c || !count || (cap && !idx)) return DYMU_ERR_ARG;
+  if (!c || !count || nx == 0 || ny == 0 || ld < nx || (cap && !idx)) return DYMU_ERR_ARG;
   uint64_t n = 0;
   for (uint32_t j = 0; j < ny; ++j)
     for (uint32_t i = 0; i < nx; ++i)
