@@ -381,6 +381,25 @@ class DyMuPathPlanner {
   // goals x targets traverse-cost matrix
   bool costMatrix(const std::vector<base::Waypoint>& goals,
                   const std::vector<base::Waypoint>& targets, std::vector<double>& out);
+  // costMatrix with an early exit: same arguments, same output, but the
+  // batch solve (dymu_solve_batch_until_device) stops once every cell getTotalCost may
+  // read for a target is final in every map -- the matrix is that of costMatrix, the work
+  // that of the region the targets span.  Worth it when the targets lie near the goals;
+  // with a target at the far end of a map the solve runs about as long as the cold batch
+  // and pays for its checks on top (DESIGN.md s5.9 has the measured price).  A target
+  // whose cell is unreachable at finite speed makes the solve run to convergence.
+  // The stack it leaves is a TRUNCATED batch: batchLevel() is the level up to which its
+  // maps are final, batchCount() counts its planes and lastBatchStats() reports the solve.
+  // A truncated batch is never read and never reused: getTotalCosts, copyBatchTotalCost
+  // and getPathsTo first complete it with the cold solve of the held goals
+  // (lastBatchSolveKind() is then 0 and batchLevel() +inf), computeTotalCostMaps with the
+  // same goals solves cold with or without trackSpeedChanges, and a synchronised speed
+  // change drops it.  Without a device engine, or with an engine that lacks the entry, it
+  // returns false and changes nothing.
+  bool costMatrixUntil(const std::vector<base::Waypoint>& goals,
+                       const std::vector<base::Waypoint>& targets, std::vector<double>& out);
+  // +inf for a complete batch and with no batch
+  double batchLevel() const { return batch_level_; }
   // getPaths on map b with goal b as the sink (always on the device; sinks are 0).
   // Throws std::invalid_argument for b >= batchCount().
   std::vector<std::vector<base::Waypoint>> getPathsTo(unsigned b,
@@ -498,7 +517,15 @@ class DyMuPathPlanner {
   std::vector<BatchGoal> batch_goals_;
   double* dT_batch_ = nullptr;
   dymu_stats batch_stats_{};
+  // costMatrixUntil's truncated batch: the level up to which its planes are final
+  // (+inf: a complete batch, or none)
+  double batch_level_ = __builtin_inf();
   void dropBatch();
+  // computeTotalCostMaps' preamble: the goals validated into bg, the engine made, the
+  // speed synchronised (a change found is passed on as there); false: rejected
+  bool prepareBatch(const std::vector<base::Waypoint>& goals, std::vector<BatchGoal>& bg);
+  // getTotalCost of every point on every plane of the held stack, as it stands
+  void gatherBatch(const std::vector<base::Waypoint>& points, std::vector<double>& out);
   // goal cell of w by setGoal's tests; false if setGoal would reject it
   bool goalCell(const base::Waypoint& w, unsigned& i, unsigned& j) const;
   // a speed change a batch solve synchronised while dT_ still holds the map of the

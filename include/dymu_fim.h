@@ -279,6 +279,45 @@ int dymu_gather_costs_device(dymu_ctx* ctx, const double* dT_stack, uint32_t nx,
                              uint32_t B, uint64_t ld, double res, const double* d_xy, uint32_t M,
                              double* d_out, void* stream);
 
+/* ---- early exit on target cells for seeded and batched solves ----
+ * The cold solves of dymu_solve_seeds_device / dymu_solve_batch_device with a stop test
+ * over a list of target cells (HOST array, like the seeds).  A target COUNTS when its
+ * speed is finite; a target on a +inf-speed cell is final from the start (its value is
+ * +inf by definition) and is ignored.  (This differs from dymu_solve_until_device's
+ * five-cell probe, where an obstacle among the start's neighbours reads +inf and makes
+ * the solve run to the end.)  The solve returns at the first check at which the smallest
+ * key of any queued tile exceeds t = max T over all counting targets of all planes, or
+ * when the domain has converged; *t_closed = t.  On return every cell of every plane
+ * whose converged value is <= *t_closed holds that value (dymu_solve_until_device's
+ * contract); other cells hold upper bounds or +inf.  t_plane (host, B doubles, or NULL):
+ * t_plane[b] = the maximum over plane b's counting targets -- +inf when one of them is
+ * unreachable, 0.0 for a plane with none (such a plane imposes no condition);
+ * t_plane[b] <= *t_closed.  A finite-speed target that is unreachable in its plane keeps
+ * the whole stack running to convergence: *t_closed = +inf and the result is the full
+ * solve's.  Runs a priority kernel (4 or 5) whatever dymu_opts.kernel says;
+ * deterministic and exact_sqrt as for any solve; dymu_opts.passes_per_check > 0 checks
+ * every that many passes, 0 checks after 16 passes and then every 16.
+ * A plane is an ordinary map: dymu_early_exit_mask on plane b with level t_plane[b] (or
+ * *t_closed, for everything known final) cuts it back to the reference's exit state.
+ * DYMU_ERR_ARG, before any device work: a null pointer (t_plane excepted), n_targets = 0,
+ * a target with plane >= B or off its plane, and every argument rule of the solve
+ * extended.  Block until the exit. */
+typedef struct dymu_cell {
+  uint32_t i, j;
+} dymu_cell;
+typedef struct dymu_batch_cell {
+  uint32_t plane, i, j, reserved;
+} dymu_batch_cell;
+int dymu_solve_seeds_until_device(dymu_ctx* ctx, const double* dF, double* dT, uint32_t nx,
+                                  uint32_t ny, uint64_t ld, const dymu_seed* seeds,
+                                  uint32_t n_seeds, const dymu_cell* targets, uint32_t n_targets,
+                                  void* stream, double* t_closed, dymu_stats* stats);
+int dymu_solve_batch_until_device(dymu_ctx* ctx, const double* dF_stack, double* dT_stack,
+                                  uint32_t nx, uint32_t ny, uint32_t B, uint64_t ld,
+                                  const dymu_batch_seed* seeds, uint32_t n_seeds,
+                                  const dymu_batch_cell* targets, uint32_t n_targets, void* stream,
+                                  double* t_closed, double* t_plane, dymu_stats* stats);
+
 /* ---- row-slab domains (multi-GPU sharding; also single-GPU virtual slabs) ----
  * A rank owns rows [row0, row0+nrows) of an nx-wide global grid.  T points at
  * its first owned row; with ghost_lo the row above it (T - ld) holds the

@@ -111,6 +111,18 @@ int dymu_planner_get_total_costs(dymu_planner* p, const double* points_xy, int n
 /* both of the above in one call: out (n_goals * n_targets) = the traverse-cost matrix */
 int dymu_planner_cost_matrix(dymu_planner* p, const double* goals_xyzh, int n_goals,
                              const double* targets_xy, int n_targets, double* out);
+/* DyMuPathPlanner::costMatrixUntil: dymu_planner_cost_matrix whose batch
+ * solve stops once the cells the targets read are final in every map -- the same matrix
+ * for less work when the targets lie near the goals.  It leaves a TRUNCATED batch:
+ * dymu_planner_batch_level is finite, and the batch readers (get_total_costs,
+ * copy_batch_total_cost, get_paths_to) and compute_total_cost_maps of the same goals
+ * first complete it with the cold solve.  0 (nothing changed) also without a device
+ * engine or with an engine that lacks the entry. */
+int dymu_planner_cost_matrix_until(dymu_planner* p, const double* goals_xyzh, int n_goals,
+                                   const double* targets_xy, int n_targets, double* out);
+/* batchLevel(): the level up to which the held batch's maps are final; +inf for a
+ * complete batch and with no batch */
+int dymu_planner_batch_level(dymu_planner* p, double* level);
 /* dymu_planner_get_paths on map b with goal b as the sink: same arguments, same
  * two-call protocol, same status values.  DYMU_ERR_ARG for b >= batch_count. */
 int dymu_planner_get_paths_to(dymu_planner* p, uint32_t b, const double* starts_xyzh, int n,

@@ -10,6 +10,8 @@
 // every plane of a solved stack: the host's tests in the host's order and its bilinear
 // expression operation by operation, built with -ffp-contract=off like the host code,
 // so the values are bit-identical to the host's on the same T.
+// k_probe_targets is the stop test of the early exit on target cells: the
+// largest value among the targets of finite speed, per plane and over the whole stack.
 #include "fim_kernels.h"
 
 namespace dymu {
@@ -73,7 +75,84 @@ __global__ __launch_bounds__(256) void k_gather_costs(const double* __restrict__
   }
 }
 
+// ---- early exit on target cells ----
+// The stop test's inputs: the largest value among the counting targets (finite speed) of
+// every plane and of the whole stack, as bit patterns -- T >= 0, so bit order is value
+// order and +inf wins.  A wave takes 64 consecutive targets per step; they are sorted by
+// plane, so it mostly holds one plane: the lanes of the first live lane's plane reduce
+// with shuffles and that lane makes the plane's one atomic, until no lane is live.  The
+// stack-wide maximum stays in registers over the steps and goes through LDS: one atomic
+// per workgroup on out[0], and the grid is capped (kProbeBlocks), so that word sees at
+// most that many however long the list is.  A value of 0 needs no atomic (out is zeroed).
+// T is read only after the target is proven inside its plane; the index is 64-bit (s5.3).
+constexpr uint32_t kProbeBlocks = 256;
+constexpr uint32_t kNoPlane = 0xFFFFFFFFu;
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long m) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(m, off, 64);
+    m = o > m ? o : m;
+  }
+  return m;
+}
+
+__global__ __launch_bounds__(256) void k_probe_targets(
+    const double* __restrict__ F, const double* __restrict__ T, uint64_t ld, uint32_t nx,
+    uint32_t ny, uint32_t planes, uint32_t P, const ProbeTarget* __restrict__ tg, uint32_t n,
+    const unsigned long long* __restrict__ minkey, unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long s_max;
+  if (threadIdx.x == 0) s_max = 0ull;
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63u;
+  unsigned long long all = 0ull;
+  // n < 2^31 and the stride is at most 2^16: base never wraps
+  for (uint32_t base = blockIdx.x * 256u; base < n; base += gridDim.x * 256u) {
+    const uint32_t k = base + threadIdx.x;
+    uint32_t plane = kNoPlane;
+    unsigned long long v = 0ull;
+    if (k < n) {
+      const ProbeTarget t = tg[k];
+      if (t.plane < planes && t.i < nx && t.j < ny) {  // rejected on the host otherwise
+        const uint64_t idx = ((uint64_t)t.plane * P + t.j) * ld + t.i;
+        if (F[idx] < kInfD) {  // a counting target
+          plane = t.plane;
+          v = (unsigned long long)__double_as_longlong(T[idx]);
+        }
+      }
+    }
+    all = v > all ? v : all;
+    unsigned long long live = __ballot(plane != kNoPlane);  // wave-uniform
+    while (live) {
+      const int lead = __ffsll((long long)live) - 1;
+      const uint32_t pl = __shfl(plane, lead, 64);
+      const bool mine = plane == pl;
+      const unsigned long long m = wave_max_u64(mine ? v : 0ull);
+      if ((int)lane == lead && m) atomicMax(&out[2 + pl], m);
+      live &= ~__ballot(mine);
+    }
+  }
+  all = wave_max_u64(all);
+  if (lane == 0u && all) atomicMax(&s_max, all);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s_max) atomicMax(&out[0], s_max);
+    if (blockIdx.x == 0) out[1] = minkey ? *minkey : 0x7FF0000000000000ull;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_probe_targets(const double* F, const double* T, uint64_t ld, uint32_t nx,
+                                uint32_t ny, uint32_t planes, uint32_t P, const ProbeTarget* tg,
+                                uint32_t n, const unsigned long long* minkey,
+                                unsigned long long* out, hipStream_t st) {
+  uint32_t b = (n + 255u) / 256u;
+  if (b > kProbeBlocks) b = kProbeBlocks;
+  if (b == 0) b = 1;  // out[1] is written even without a target
+  hipLaunchKernelGGL(k_probe_targets, dim3(b), dim3(256), 0, st, F, T, ld, nx, ny, planes, P, tg, n,
+                     minkey, out);
+  return hipGetLastError();
+}
 
 hipError_t launch_stack_speed(const double* src, uint64_t src_ld, uint64_t src_plane_stride,
                               uint32_t nx, uint32_t ny, uint32_t planes, uint32_t P, double* dst,

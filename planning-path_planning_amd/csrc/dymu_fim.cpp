@@ -151,6 +151,12 @@ struct dymu_ctx {
   // theta per plane of the seeded / stacked windowed update (update_planes_core)
   unsigned long long* d_theta = nullptr;
   uint32_t theta_cap = 0;
+  // early exit on target cells (converge_targets): 2 + planes words the
+  // probe kernel fills (max T, min key, max T per plane), and the passes between two
+  // checks once the first first_batch passes have run (DYMU_UNTIL_BATCH overrides)
+  unsigned long long* d_until = nullptr;
+  uint32_t until_cap = 0;
+  uint64_t until_batch = 16;
 
   // profiling
   int profiling = 0;
@@ -1115,6 +1121,80 @@ int resolve_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_
   return converge_auto(c, st, stats);
 }
 
+// ---- early exit on target cells (batch_kernels.hip) ----
+static_assert(sizeof(dymu_batch_cell) == sizeof(ProbeTarget) &&
+                  offsetof(dymu_batch_cell, j) == offsetof(ProbeTarget, j),
+              "dymu_batch_cell is ProbeTarget");
+// The targets of one call: tg (host, sorted by plane, each inside its plane) on a stack of
+// `planes` maps of ny rows at a plane pitch of P rows (one plain map: planes = 1, P = ny).
+struct UntilTargets {
+  const ProbeTarget* tg;
+  uint32_t n, ny, planes, P;
+  double* t_closed;  // required
+  double* t_plane;   // host [planes], or null
+};
+
+// converge() with the stop test over a target list: K passes, the probe (its words zeroed
+// by a fill kernel first), two words read back, compare.  The solve ends at the first check
+// at which every queued tile's key exceeds the largest value among the counting targets
+// (then no pass can lower a value at or below it any more), or with nothing queued.
+// K: passes_per_check when given, else first_batch passes before the first check and
+// until_batch between the later ones -- no doubling to 64: the passes run behind the
+// deciding one are the overshoot this entry exists to avoid.
+int converge_targets(dymu_ctx* c, hipStream_t st, dymu_stats* stats, const UntilTargets& u,
+                     const ProbeTarget* d_tg) {
+  HIPC(c, hipEventRecord(c->ev0, st));
+  const bool fixed = c->opts.passes_per_check > 0;
+  uint64_t K = fixed ? (uint64_t)c->opts.passes_per_check : c->first_batch;
+  const uint32_t words = u.planes + 2u;
+  double tmax = __builtin_inf();
+  for (;;) {
+    int rc = dom_launch(c, K, st);
+    if (rc == DYMU_OK) {
+      auto& D = c->dom;
+      hipError_t e = launch_fill_u64(c->d_until, words, 0ull, st);
+      if (e == hipSuccess)
+        e = launch_probe_targets(D.a.F, D.a.T, (uint64_t)D.a.ld, D.a.nx, u.ny, u.planes, u.P, d_tg,
+                                 u.n, prio_minkey(c, D.p % 3), c->d_until, st);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(c->h_probe, c->d_until, 2 * sizeof(unsigned long long),
+                           hipMemcpyDeviceToHost, st);
+      if (e != hipSuccess) rc = fail_hip(c, e, "target probe");
+    }
+    if (rc == DYMU_OK) {
+      uint64_t pending = 0;
+      rc = dom_pending(c, st, &pending);  // synchronises: the probe words are here too
+      if (rc == DYMU_OK) {
+        double kmin;
+        std::memcpy(&tmax, &c->h_probe[0], sizeof tmax);
+        std::memcpy(&kmin, &c->h_probe[1], sizeof kmin);
+        if (kmin > tmax || pending == 0) break;
+      }
+    }
+    if (rc == DYMU_OK && c->dom.p >= c->dom.max_passes) {
+      c->last_error = "pass cap reached before convergence";
+      rc = DYMU_ERR_NOT_CONVERGED;
+    }
+    if (rc) {
+      dom_retire(c);
+      return rc;
+    }
+    if (!fixed) K = c->until_batch;
+  }
+  HIPC(c, hipEventRecord(c->ev1, st));
+  HIPC(c, hipEventSynchronize(c->ev1));
+  float ms = 0.f;
+  HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  *u.t_closed = tmax;
+  if (u.t_plane) {  // the words of the last probe; the stream is idle
+    std::vector<unsigned long long> h(u.planes);
+    HIPC(c, hipMemcpy(h.data(), c->d_until + 2, sizeof(unsigned long long) * u.planes,
+                      hipMemcpyDeviceToHost));
+    std::memcpy(u.t_plane, h.data(), sizeof(double) * u.planes);
+  }
+  return dom_finish(c, st, stats, ms);
+}
+
 // ---- goal sets (goal_kernels.hip) ----
 static_assert(sizeof(dymu_seed) == sizeof(GoalSeed) && offsetof(dymu_seed, t0) == offsetof(GoalSeed, t0),
               "dymu_seed is GoalSeed");
@@ -1123,8 +1203,10 @@ constexpr uint32_t kLabelRounds = 64;  // pointer-jumping rounds: ~log2 of the l
 // The seeds checked and copied into the pinned transfer buffer, where the kernels read
 // them in place (ensure_xfer; the stream is drained first); *tmin = the smallest t0.
 // t0 + 0.0 turns a -0.0 into +0.0, so that the values' bit patterns order like them.
+// extra: bytes reserved behind the seeds in the same buffer (a second ensure_xfer could
+// move it under the first, s5.8).
 int stage_seeds(dymu_ctx* c, uint32_t nx, uint32_t ny, const dymu_seed* seeds, uint32_t n,
-                hipStream_t st, const GoalSeed** d_seeds, double* tmin) {
+                hipStream_t st, const GoalSeed** d_seeds, double* tmin, uint64_t extra = 0) {
   if (!seeds || n == 0 || n >= (1u << 31)) return DYMU_ERR_ARG;
   double m = __builtin_inf();
   for (uint32_t k = 0; k < n; ++k) {
@@ -1133,7 +1215,7 @@ int stage_seeds(dymu_ctx* c, uint32_t nx, uint32_t ny, const dymu_seed* seeds, u
     m = std::min(m, s.t0);
   }
   HIPC(c, hipStreamSynchronize(st));  // no earlier kernel still uses the transfer buffer
-  int rc = ensure_xfer(c, sizeof(GoalSeed) * (uint64_t)n);
+  int rc = ensure_xfer(c, sizeof(GoalSeed) * (uint64_t)n + extra);
   if (rc) return rc;
   GoalSeed* h = static_cast<GoalSeed*>(c->h_xfer);
   for (uint32_t k = 0; k < n; ++k) h[k] = GoalSeed{seeds[k].i, seeds[k].j, seeds[k].t0 + 0.0};
@@ -1145,15 +1227,31 @@ int stage_seeds(dymu_ctx* c, uint32_t nx, uint32_t ny, const dymu_seed* seeds, u
 // A cold domain without a goal, every seed min-written into T and its tile queued in
 // list 0 (priority kernels: key = the tile's smallest seed value, binned against
 // base = min t0), then the unchanged passes to convergence.
+// until: the early exit on target cells (s5.9) -- the targets staged behind the seeds, a
+// priority kernel whatever the options say (need_keys), and converge_targets' stop test.
 int solve_seeds_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t ny,
                      uint64_t ld, const dymu_seed* seeds, uint32_t n, hipStream_t st,
-                     dymu_stats* stats) {
+                     dymu_stats* stats, const UntilTargets* until = nullptr) {
   if (!dF || !dT || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
   const GoalSeed* d_seeds = nullptr;
   double tmin = 0.0;
-  int rc = stage_seeds(c, nx, ny, seeds, n, st, &d_seeds, &tmin);
+  const uint64_t tg_bytes = until ? sizeof(ProbeTarget) * (uint64_t)until->n : 0;
+  int rc = stage_seeds(c, nx, ny, seeds, n, st, &d_seeds, &tmin, tg_bytes);
   if (rc) return rc;
-  rc = dom_begin(c, dF, dT, nx, ny, ld, 0, 0, -1, -1, st);
+  const ProbeTarget* d_tg = nullptr;
+  if (until) {
+    const uint64_t off = sizeof(GoalSeed) * (uint64_t)n;  // a multiple of 16
+    std::memcpy(static_cast<char*>(c->h_xfer) + off, until->tg, (size_t)tg_bytes);
+    d_tg = reinterpret_cast<const ProbeTarget*>(static_cast<const char*>(c->d_xfer) + off);
+    if (c->until_cap < until->planes + 2u) {
+      if (c->d_until) (void)hipFree(c->d_until);
+      c->d_until = nullptr;
+      c->until_cap = 0;
+      HIPC(c, hipMalloc(&c->d_until, sizeof(unsigned long long) * ((uint64_t)until->planes + 2)));
+      c->until_cap = until->planes + 2u;
+    }
+  }
+  rc = dom_begin(c, dF, dT, nx, ny, ld, 0, 0, -1, -1, st, true, /*need_keys=*/until != nullptr);
   if (rc) return rc;
   auto& D = c->dom;
   SeedArgs a{};
@@ -1189,6 +1287,7 @@ int solve_seeds_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uin
     dom_retire(c);
     return fail_hip(c, e, "goal seeding");
   }
+  if (until) return converge_targets(c, st, stats, *until, d_tg);
   return converge_auto(c, st, stats);
 }
 
@@ -1420,6 +1519,8 @@ int dymu_create(dymu_ctx** out, const dymu_opts* opts) {
   if (const char* kv = std::getenv("DYMU_DETERMINISTIC")) c->opts.deterministic = std::atoi(kv);
   if (const char* kv = std::getenv("DYMU_MAX_BATCH"))
     c->max_batch = (uint64_t)std::min(64, std::max(1, std::atoi(kv)));
+  if (const char* kv = std::getenv("DYMU_UNTIL_BATCH"))
+    c->until_batch = (uint64_t)std::min(64, std::max(1, std::atoi(kv)));
   if (e == hipSuccess) {
     for (int v = 3; v <= 5; ++v) c->occupancy[v] = pass_blocks_per_cu(v);
   }
@@ -1498,6 +1599,7 @@ int dymu_destroy(dymu_ctx* c) {
   if (c->d_lut) (void)hipFree(c->d_lut);
   if (c->d_scratch) (void)hipFree(c->d_scratch);
   if (c->d_theta) (void)hipFree(c->d_theta);
+  if (c->d_until) (void)hipFree(c->d_until);
   if (c->d_xchg) (void)hipFree(c->d_xchg);
   if (c->d_stats) (void)hipFree(c->d_stats);
   if (c->d_F) (void)hipFree(c->d_F);
@@ -1777,9 +1879,13 @@ int dymu_stack_speed_device(dymu_ctx* c, const double* src, uint64_t src_ld,
   return DYMU_OK;
 }
 
-int dymu_solve_batch_device(dymu_ctx* c, const double* dF_stack, double* dT_stack, uint32_t nx,
-                            uint32_t ny, uint32_t B, uint64_t ld, const dymu_batch_seed* seeds,
-                            uint32_t n_seeds, void* stream, dymu_stats* stats) {
+namespace {
+// dymu_solve_batch_device; with targets (any order, checked here, sorted by plane for the
+// probe's waves) dymu_solve_batch_until_device
+int solve_batch(dymu_ctx* c, const double* dF_stack, double* dT_stack, uint32_t nx, uint32_t ny,
+                uint32_t B, uint64_t ld, const dymu_batch_seed* seeds, uint32_t n_seeds,
+                void* stream, dymu_stats* stats, const dymu_batch_cell* targets = nullptr,
+                uint32_t n_targets = 0, double* t_closed = nullptr, double* t_plane = nullptr) {
   uint32_t rows = 0;
   if (!c || !dF_stack || !dT_stack || !seeds || n_seeds == 0 || n_seeds >= (1u << 31) ||
       !batch_rows(nx, ny, B, ld, &rows))
@@ -1797,6 +1903,21 @@ int dymu_solve_batch_device(dymu_ctx* c, const double* dF_stack, double* dT_stac
   }
   for (uint32_t b = 0; b < B; ++b)
     if (!seeded[b]) return DYMU_ERR_ARG;
+  std::vector<ProbeTarget> tg;
+  UntilTargets until{};
+  if (targets) {
+    std::vector<uint32_t> at(B + 1ull, 0u);  // counting sort by plane (stable)
+    for (uint32_t k = 0; k < n_targets; ++k) {
+      const dymu_batch_cell& q = targets[k];
+      if (q.plane >= B || q.i >= nx || q.j >= ny) return DYMU_ERR_ARG;
+      ++at[q.plane + 1ull];
+    }
+    for (uint32_t b = 0; b < B; ++b) at[b + 1ull] += at[b];
+    tg.resize(n_targets);
+    for (uint32_t k = 0; k < n_targets; ++k)
+      tg[at[targets[k].plane]++] = ProbeTarget{targets[k].plane, targets[k].i, targets[k].j, 0u};
+    until = UntilTargets{tg.data(), n_targets, ny, B, P, t_closed, t_plane};
+  }
   HIPC(c, hipSetDevice(c->device));
   // The per-pass relax target is the one any solve of an nx x rows domain gets
   // (dom_begin); DYMU_BATCH_TARGET_PER_CU (tiles per CU, development) overrides it for
@@ -1808,9 +1929,47 @@ int dymu_solve_batch_device(dymu_ctx* c, const double* dF_stack, double* dT_stac
       if (v > 0 && v < 4096) c->prio_target = (uint32_t)c->cu_count * (uint32_t)v;
     }
   const int rc = solve_seeds_core(c, dF_stack, dT_stack, nx, rows, ld, s.data(), n_seeds,
-                                  pick_stream(c, stream), stats);
+                                  pick_stream(c, stream), stats, targets ? &until : nullptr);
   c->prio_target = saved;
   return rc;
+}
+}  // namespace
+
+int dymu_solve_batch_device(dymu_ctx* c, const double* dF_stack, double* dT_stack, uint32_t nx,
+                            uint32_t ny, uint32_t B, uint64_t ld, const dymu_batch_seed* seeds,
+                            uint32_t n_seeds, void* stream, dymu_stats* stats) {
+  return solve_batch(c, dF_stack, dT_stack, nx, ny, B, ld, seeds, n_seeds, stream, stats);
+}
+
+/* ---- early exit on target cells ---- */
+
+int dymu_solve_batch_until_device(dymu_ctx* c, const double* dF_stack, double* dT_stack,
+                                  uint32_t nx, uint32_t ny, uint32_t B, uint64_t ld,
+                                  const dymu_batch_seed* seeds, uint32_t n_seeds,
+                                  const dymu_batch_cell* targets, uint32_t n_targets, void* stream,
+                                  double* t_closed, double* t_plane, dymu_stats* stats) {
+  if (!c || !targets || n_targets == 0 || n_targets >= (1u << 31) || !t_closed)
+    return DYMU_ERR_ARG;
+  return solve_batch(c, dF_stack, dT_stack, nx, ny, B, ld, seeds, n_seeds, stream, stats, targets,
+                     n_targets, t_closed, t_plane);
+}
+
+int dymu_solve_seeds_until_device(dymu_ctx* c, const double* dF, double* dT, uint32_t nx,
+                                  uint32_t ny, uint64_t ld, const dymu_seed* seeds,
+                                  uint32_t n_seeds, const dymu_cell* targets, uint32_t n_targets,
+                                  void* stream, double* t_closed, dymu_stats* stats) {
+  if (!c || !dF || !dT || !seeds || !targets || n_targets == 0 || n_targets >= (1u << 31) ||
+      !t_closed)
+    return DYMU_ERR_ARG;
+  std::vector<ProbeTarget> tg(n_targets);
+  for (uint32_t k = 0; k < n_targets; ++k) {
+    if (targets[k].i >= nx || targets[k].j >= ny) return DYMU_ERR_ARG;
+    tg[k] = ProbeTarget{0u, targets[k].i, targets[k].j, 0u};
+  }
+  const UntilTargets until{tg.data(), n_targets, ny, 1u, ny, t_closed, nullptr};
+  HIPC(c, hipSetDevice(c->device));
+  return solve_seeds_core(c, dF, dT, nx, ny, ld, seeds, n_seeds, pick_stream(c, stream), stats,
+                          &until);
 }
 
 int dymu_gather_costs_device(dymu_ctx* c, const double* dT_stack, uint32_t nx, uint32_t ny,

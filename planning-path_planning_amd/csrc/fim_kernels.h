@@ -413,6 +413,20 @@ hipError_t launch_gather_costs(const double* T, uint64_t ld, uint32_t nx, uint32
                                uint32_t planes, uint32_t P, double res, const double* xy,
                                uint32_t M, double* out, hipStream_t st);
 
+// early exit on target cells (batch_kernels.hip)
+struct ProbeTarget {  // dymu_batch_cell's layout: cell (i, j) of plane `plane`
+  uint32_t plane, i, j, pad;
+};
+// The stop test's inputs over `n` targets (device-readable, sorted by plane) of a stack of
+// `planes` maps at a plane pitch of P rows (one plain map: one plane, P = ny).  A target
+// counts when its speed is finite.  out (2 + planes words, zeroed before the launch):
+// out[0] = bits of max T over the counting targets, out[1] = *minkey, out[2 + b] = bits of
+// max T over plane b's counting targets (0: none).
+hipError_t launch_probe_targets(const double* F, const double* T, uint64_t ld, uint32_t nx,
+                                uint32_t ny, uint32_t planes, uint32_t P, const ProbeTarget* tg,
+                                uint32_t n, const unsigned long long* minkey,
+                                unsigned long long* out, hipStream_t st);
+
 hipError_t launch_prio_init(const double* F, int64_t ld, int64_t nx, int64_t ny,
                            unsigned long long* keys, uint64_t nkeys, uint32_t* hist, uint64_t nhist,
                            unsigned long long* minkey, double* base, double* delta, double kappa,

@@ -2719,6 +2719,7 @@ bool DyMuPathPlanner::loadTotalCostMap(const double* Tin) {
 #pragma weak dymu_stack_speed_device
 #pragma weak dymu_solve_batch_device
 #pragma weak dymu_gather_costs_device
+#pragma weak dymu_solve_batch_until_device
 
 // trackSpeedChanges: a pending box is re-propagated through the batch when it covers at
 // most 1 / kBatchWindowDiv of the grid (propagate's rule; DESIGN.md s5.8 has the
@@ -2731,6 +2732,7 @@ void DyMuPathPlanner::dropBatch() {
   batch_goals_.clear();
   batch_stats_ = dymu_stats{};
   batch_kind_ = 0;
+  batch_level_ = kInf;
   bpend_ = false;
 }
 
@@ -2741,7 +2743,8 @@ void DyMuPathPlanner::trackSpeedChanges(bool on) {
 
 void DyMuPathPlanner::batchSpeedChanged(unsigned i0, unsigned i1, unsigned j0, unsigned j1) {
   if (!dT_batch_) return;
-  if (!track_ || !&dymu_update_batch_window_device) {
+  // a truncated batch (costMatrixUntil) is never carried across a change
+  if (!track_ || !&dymu_update_batch_window_device || batch_level_ < kInf) {
     dropBatch();
     return;
   }
@@ -2766,12 +2769,12 @@ bool DyMuPathPlanner::goalCell(const base::Waypoint& w, unsigned& i, unsigned& j
            is_obstacle_[k + nx_]);
 }
 
-bool DyMuPathPlanner::computeTotalCostMaps(const std::vector<base::Waypoint>& goals) {
+bool DyMuPathPlanner::prepareBatch(const std::vector<base::Waypoint>& goals,
+                                   std::vector<BatchGoal>& bg) {
   if (goals.empty() || goals.size() > 0xffffffffull || nx_ == 0 || ny_ == 0) return false;
   if (!&dymu_batch_plane_rows || !&dymu_stack_speed_device || !&dymu_solve_batch_device ||
       !&dymu_gather_costs_device)
     return false;
-  std::vector<BatchGoal> bg;
   for (const base::Waypoint& w : goals) {
     unsigned i = 0, j = 0;
     if (!goalCell(w, i, j)) return false;
@@ -2797,9 +2800,16 @@ bool DyMuPathPlanner::computeTotalCostMaps(const std::vector<base::Waypoint>& go
   } catch (const std::exception&) {
     return false;  // no device engine
   }
+  return true;
+}
+
+bool DyMuPathPlanner::computeTotalCostMaps(const std::vector<base::Waypoint>& goals) {
+  std::vector<BatchGoal> bg;
+  if (!prepareBatch(goals, bg)) return false;
   // trackSpeedChanges: the held batch of these very goals is reused, or re-propagated
-  // from the pending box where that box is small enough (refreshBatch)
-  if (track_ && dT_batch_ && bg.size() == batch_goals_.size() &&
+  // from the pending box where that box is small enough (refreshBatch); a truncated
+  // batch (costMatrixUntil) is not: the cold solve below replaces it
+  if (track_ && dT_batch_ && !(batch_level_ < kInf) && bg.size() == batch_goals_.size() &&
       std::equal(bg.begin(), bg.end(), batch_goals_.begin(),
                  [](const BatchGoal& a, const BatchGoal& b) { return a.i == b.i && a.j == b.j; })) {
     if (!bpend_) {
@@ -2849,6 +2859,13 @@ bool DyMuPathPlanner::solveBatchCold(std::vector<BatchGoal>& bg) {
 // the grid: F re-stacked from dF_ (temporary) and every plane re-propagated from the box
 // in one call; a larger box, or an update that fails: the cold solve of the same goals.
 bool DyMuPathPlanner::refreshBatch() {
+  if (batch_level_ < kInf) {  // truncated (costMatrixUntil): completed by the cold solve
+    if (!ctx_ || !dT_batch_) return false;
+    std::vector<BatchGoal> bg = batch_goals_;
+    if (solveBatchCold(bg)) return true;
+    dropBatch();
+    return false;
+  }
   if (!bpend_) return true;
   if (!ctx_ || !dT_batch_) return false;
   const uint32_t B = (uint32_t)batch_goals_.size();
@@ -2901,6 +2918,12 @@ bool DyMuPathPlanner::getTotalCosts(const std::vector<base::Waypoint>& points,
                                     std::vector<double>& out) {
   if (batch_goals_.empty() || !ctx_ || !dT_batch_ || points.size() > 0xffffffffull) return false;
   if (!refreshBatch()) return false;
+  gatherBatch(points, out);
+  return true;
+}
+
+void DyMuPathPlanner::gatherBatch(const std::vector<base::Waypoint>& points,
+                                  std::vector<double>& out) {
   const uint32_t B = (uint32_t)batch_goals_.size(), M = (uint32_t)points.size();
   std::vector<double> res((uint64_t)B * M);
   if (M) {
@@ -2924,13 +2947,74 @@ bool DyMuPathPlanner::getTotalCosts(const std::vector<base::Waypoint>& points,
     check(dymu_memcpy_d2h(ctx_, res.data(), d_out, sizeof(double) * res.size()), "download");
   }
   out.swap(res);
-  return true;
 }
 
 bool DyMuPathPlanner::costMatrix(const std::vector<base::Waypoint>& goals,
                                  const std::vector<base::Waypoint>& targets,
                                  std::vector<double>& out) {
   return computeTotalCostMaps(goals) && getTotalCosts(targets, out);
+}
+
+// costMatrix with the batch solve stopped once the matrix's inputs are final (DESIGN.md
+// s5.9).  The targets of the solve are the cells k_gather_costs / getTotalCost may read
+// for each point, in every plane: the nearest node alone where a corner of the point's
+// cell is off the grid, else the four corners (the nearest node is one of them).  A
+// corner on an obstacle is ignored by the stop test and reads +inf either way; every
+// other one is final on return, so the gather sees what it would see on converged maps.
+bool DyMuPathPlanner::costMatrixUntil(const std::vector<base::Waypoint>& goals,
+                                      const std::vector<base::Waypoint>& targets,
+                                      std::vector<double>& out) {
+  if (!&dymu_solve_batch_until_device || targets.size() > 0xffffffffull) return false;
+  if (targets.empty()) return costMatrix(goals, targets, out);  // nothing to stop on
+  std::vector<BatchGoal> bg;
+  if (!prepareBatch(goals, bg)) return false;
+  const uint32_t B = (uint32_t)bg.size();
+  const uint64_t P = dymu_batch_plane_rows(ny_);
+  std::vector<dymu_cell> cells;
+  for (const base::Waypoint& w : targets) {
+    const double x = w.position[0] - global_offset_[0], y = w.position[1] - global_offset_[1];
+    const uint64_t i = grid_u32(x / global_res_), j = grid_u32(y / global_res_);
+    const uint64_t ni = grid_u32(x / global_res_ + 0.5), nj = grid_u32(y / global_res_ + 0.5);
+    if (i >= nx_ || j >= ny_ || i + 1 >= nx_ || j + 1 >= ny_) {
+      if (ni < nx_ && nj < ny_) cells.push_back(dymu_cell{(uint32_t)ni, (uint32_t)nj});
+    } else {
+      for (uint32_t q = 0; q < 4; ++q)
+        cells.push_back(dymu_cell{(uint32_t)i + (q & 1u), (uint32_t)j + (q >> 1)});
+    }
+  }
+  if (cells.empty() || (uint64_t)cells.size() * B >= (1ull << 31))
+    return costMatrix(goals, targets, out);  // every point reads +inf / too many cells
+  std::vector<dymu_batch_seed> seeds;
+  std::vector<dymu_batch_cell> tg;
+  tg.reserve(cells.size() * B);
+  for (uint32_t b = 0; b < B; ++b) {
+    seeds.push_back(dymu_batch_seed{b, bg[b].i, bg[b].j, 0u, 0.0});
+    for (const dymu_cell& c : cells) tg.push_back(dymu_batch_cell{b, c.i, c.j, 0u});
+  }
+  const uint64_t bytes = sizeof(double) * (uint64_t)B * P * nx_;
+  void *pf = nullptr, *pt = nullptr;
+  dymu_stats st{};
+  double level = kInf;
+  int rc = dymu_device_alloc(ctx_, bytes, &pf);
+  if (rc == DYMU_OK) rc = dymu_device_alloc(ctx_, bytes, &pt);
+  double* f = static_cast<double*>(pf);
+  double* t = static_cast<double*>(pt);
+  if (rc == DYMU_OK) rc = dymu_stack_speed_device(ctx_, dF_, nx_, 0, nx_, ny_, B, f, nx_, nullptr);
+  if (rc == DYMU_OK)
+    rc = dymu_solve_batch_until_device(ctx_, f, t, nx_, ny_, B, nx_, seeds.data(), B, tg.data(),
+                                       (uint32_t)tg.size(), nullptr, &level, nullptr, &st);
+  if (f) (void)dymu_device_free(ctx_, f);
+  if (rc != DYMU_OK) {
+    if (t) (void)dymu_device_free(ctx_, t);
+    return false;
+  }
+  dropBatch();
+  dT_batch_ = t;
+  batch_goals_.swap(bg);
+  batch_stats_ = st;
+  batch_level_ = level;  // +inf: the solve ran to convergence, the batch is complete
+  gatherBatch(targets, out);
+  return true;
 }
 
 std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getPathsTo(

@@ -481,6 +481,25 @@ int dymu_planner_cost_matrix(dymu_planner* p, const double* goals_xyzh, int n_go
   });
 }
 
+int dymu_planner_cost_matrix_until(dymu_planner* p, const double* goals_xyzh, int n_goals,
+                                   const double* targets_xy, int n_targets, double* out) {
+  if (!p || !goals_xyzh || n_goals <= 0 || n_targets < 0 || (n_targets > 0 && (!targets_xy || !out)))
+    return DYMU_ERR_ARG;
+  return guarded([&] {
+    std::vector<double> v;
+    if (!p->pl.costMatrixUntil(wps(goals_xyzh, n_goals, 4), wps(targets_xy, n_targets, 2), v))
+      return 0;
+    if (!v.empty()) std::memcpy(out, v.data(), sizeof(double) * v.size());
+    return 1;
+  });
+}
+
+int dymu_planner_batch_level(dymu_planner* p, double* level) {
+  if (!p || !level) return DYMU_ERR_ARG;
+  *level = p->pl.batchLevel();
+  return DYMU_OK;
+}
+
 int dymu_planner_get_paths_to(dymu_planner* p, uint32_t b, const double* starts, int n, int max_wp,
                               int stride, double* out, int* counts, int* status) {
   if (!starts) return dymu_planner_get_paths(p, nullptr, n, max_wp, stride, out, counts, status);

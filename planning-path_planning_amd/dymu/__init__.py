@@ -114,6 +114,10 @@ BATCH_SEED_DTYPE = np.dtype([("plane", np.uint32), ("i", np.uint32), ("j", np.ui
 BATCH_WINDOW_DTYPE = np.dtype([("plane", np.uint32), ("i0", np.uint32), ("j0", np.uint32),
                                ("w", np.uint32), ("h", np.uint32), ("reserved", np.uint32)],
                               align=True)
+# dymu_cell / dymu_batch_cell: the target cells of the early-exit solves
+CELL_DTYPE = np.dtype([("i", np.uint32), ("j", np.uint32)], align=True)
+BATCH_CELL_DTYPE = np.dtype([("plane", np.uint32), ("i", np.uint32), ("j", np.uint32),
+                             ("reserved", np.uint32)], align=True)
 
 FIM_SYMBOLS = {
     "dymu_create": (_i32, [ctypes.POINTER(_vp), ctypes.POINTER(DymuOpts)]),
@@ -197,6 +201,12 @@ FIM_SYMBOLS = {
                                                ctypes.POINTER(DymuStats)]),
     "dymu_update_batch_window_device": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _u32,
                                                _vp, _u32, _i32, _vp, ctypes.POINTER(DymuStats)]),
+    "dymu_solve_seeds_until_device": (_i32, [_vp, _vp, _vp, _u32, _u32, _u64, _vp, _u32, _vp, _u32,
+                                             _vp, ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(DymuStats)]),
+    "dymu_solve_batch_until_device": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _u32,
+                                             _vp, _u32, _vp, ctypes.POINTER(ctypes.c_double),
+                                             _vp, ctypes.POINTER(DymuStats)]),
     "dymu_device_alloc_cached": (_i32, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "dymu_memcpy2d_d2h": (_i32, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
                                  ctypes.c_size_t, ctypes.c_size_t]),
@@ -540,6 +550,43 @@ class Engine:
                                                  ctypes.byref(st)), self.ctx)
         return st.as_dict()
 
+    # -- early exit on target cells --
+    def solve_seeds_until_device(self, dF: int, dT: int, nx: int, ny: int, ld: int, seeds,
+                                 targets, stream: int = 0):
+        """dymu_solve_seeds_until_device: solve_seeds_device that stops once the target
+        cells (i, j) of finite speed are final.  Returns (t_closed, stats)."""
+        a = self._seeds(seeds)
+        tg = np.zeros(len(targets), dtype=CELL_DTYPE)
+        for k, q in enumerate(targets):
+            tg[k] = (int(q[0]), int(q[1]))
+        st = DymuStats()
+        tc = ctypes.c_double()
+        _check(self._lib.dymu_solve_seeds_until_device(
+            self.ctx, dF, dT, nx, ny, ld, a.ctypes.data if len(a) else None, len(a),
+            tg.ctypes.data if len(tg) else None, len(tg), stream or None, ctypes.byref(tc),
+            ctypes.byref(st)), self.ctx)
+        return tc.value, st.as_dict()
+
+    def solve_batch_until_device(self, dF_stack: int, dT_stack: int, nx: int, ny: int, B: int,
+                                 ld: int, seeds, targets, stream: int = 0):
+        """dymu_solve_batch_until_device: solve_batch_device that stops once the target
+        cells (plane, i, j) of finite speed are final in every plane.  Returns (t_closed,
+        t_plane [B], stats)."""
+        a = np.zeros(len(seeds), dtype=BATCH_SEED_DTYPE)
+        for k, s in enumerate(seeds):
+            a[k] = (int(s[0]), int(s[1]), int(s[2]), 0, float(s[3]) if len(s) > 3 else 0.0)
+        tg = np.zeros(len(targets), dtype=BATCH_CELL_DTYPE)
+        for k, q in enumerate(targets):
+            tg[k] = (int(q[0]), int(q[1]), int(q[2]), 0)
+        st = DymuStats()
+        tc = ctypes.c_double()
+        tp = np.zeros(max(int(B), 1))
+        _check(self._lib.dymu_solve_batch_until_device(
+            self.ctx, dF_stack, dT_stack, nx, ny, B, ld, a.ctypes.data if len(a) else None,
+            len(a), tg.ctypes.data if len(tg) else None, len(tg), stream or None,
+            ctypes.byref(tc), tp.ctypes.data, ctypes.byref(st)), self.ctx)
+        return tc.value, tp[:B].copy(), st.as_dict()
+
     # -- windowed updates of seeded maps and stacks (DESIGN.md s5.8) --
     def update_seeds_window_device(self, dF: int, dT: int, nx: int, ny: int, ld: int, seeds,
                                    i0: int, j0: int, w: int, h: int,
@@ -767,6 +814,8 @@ PLANNER_SYMBOLS = {
     "dymu_planner_copy_batch_total_cost": (_i32, [_vp, _u32, _dp, _i32]),
     "dymu_planner_get_total_costs": (_i32, [_vp, _vp, _i32, _vp]),
     "dymu_planner_cost_matrix": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp]),
+    "dymu_planner_cost_matrix_until": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp]),
+    "dymu_planner_batch_level": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "dymu_planner_get_paths_to": (_i32, [_vp, _u32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dymu_planner_last_batch_stats": (_i32, [_vp, ctypes.POINTER(DymuStats)]),
     "dymu_planner_track_speed_changes": (_i32, [_vp, _i32]),
@@ -1069,18 +1118,29 @@ class Planner:
             return None
         return out
 
-    def costMatrix(self, goals, targets):
+    def costMatrix(self, goals, targets, until: bool = False):
         """computeTotalCostMaps(goals) and getTotalCosts(targets) in one call: the
-        [len(goals), len(targets)] traverse-cost matrix, or None on failure."""
+        [len(goals), len(targets)] traverse-cost matrix, or None on failure.  until=True
+        (costMatrixUntil): the batch solve stops once the cells the targets
+        read are final in every map -- the same matrix, and a truncated batch (batchLevel()
+        finite) that the batch readers complete with a cold solve before they use it."""
         g = np.ascontiguousarray([self._wp(w) for w in goals], dtype=np.float64).reshape(-1, 4)
         xy = self._xy(targets)
         if len(g) == 0:
             return None
         out = np.zeros((len(g), len(xy)))
-        if not _b(self._lib.dymu_planner_cost_matrix(self.h, g.ctypes.data, len(g),
-                                                     xy.ctypes.data, len(xy), out.ctypes.data)):
+        fn = self._lib.dymu_planner_cost_matrix_until if until else \
+            self._lib.dymu_planner_cost_matrix
+        if not _b(fn(self.h, g.ctypes.data, len(g), xy.ctypes.data, len(xy), out.ctypes.data)):
             return None
         return out
+
+    def batchLevel(self) -> float:
+        """The level up to which the held batch's maps are final: finite after
+        costMatrix(..., until=True), +inf for a complete batch and with no batch."""
+        v = ctypes.c_double()
+        _check(self._lib.dymu_planner_batch_level(self.h, ctypes.byref(v)))
+        return v.value
 
     def getPathsTo(self, b: int, starts, max_wp: int = 1 << 20, stride: int = 1):
         """getPaths on map b of the batch, with goal b as the sink: (paths, status)."""
