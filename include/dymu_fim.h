@@ -322,8 +322,12 @@ int dymu_solve_batch_until_device(dymu_ctx* ctx, const double* dF_stack, double*
  * A rank owns rows [row0, row0+nrows) of an nx-wide global grid.  T points at
  * its first owned row; with ghost_lo the row above it (T - ld) holds the
  * neighbour rank's last row, with ghost_hi the row T + nrows*ld holds the
- * next rank's first row (then nrows must be a multiple of 32).  Ghost rows are
- * read-only halo for the kernels.  Protocol (bench_sharded.py / dymu.sharded):
+ * next rank's first row (then nrows must be a multiple of the tile height: 8 for
+ * kernels 3 and 4, 16 for kernel 5; dymu_slab_rows cuts on multiples of 32).  Ghost
+ * rows are read-only halo for the kernels: only dymu_dom_begin (+inf) and the merges
+ * below write them, and no call touches the columns nx .. ld-1 of any row, a row
+ * beyond a ghost row, or the ghost slot of a side whose flag is 0.
+ * Protocol (bench_sharded.py / dymu.sharded):
  *   dymu_dom_begin -> repeat { dymu_dom_run(K passes); exchange boundary rows
  *   (RCCL); dymu_dom_merge_ghosts(received rows) } until the all-reduced
  *   pending count is 0 -> dymu_dom_finish.
@@ -350,7 +354,17 @@ int dymu_dom_begin(dymu_ctx* ctx, const dymu_domain* dom, int64_t goal_i, int64_
 int dymu_dom_run(dymu_ctx* ctx, uint32_t passes, void* stream);
 /* Min-merge received neighbour rows (device pointers, nx doubles, or NULL)
  * into the ghost rows and queue the tiles under improved columns; if
- * d_pending != NULL also write the number of queued tiles there (int32). */
+ * d_pending != NULL also write the number of queued tiles there (int32).
+ * The merge rule (also dymu_dom_exchange's and the fused rounds'): a ghost value
+ * is replaced only by a received value STRICTLY below it.  An equal value and a
+ * NaN write nothing and queue nothing, so merging the same rows again is a no-op.
+ * Tile trow * ntx + i / tile_w is queued when a column i of it improved, trow = 0
+ * for new_lo and the last tile row for new_hi (tiles are 8 x 8 cells for kernels 3
+ * and 4, 16 x 16 for kernel 5); a tile is in the list at most once per pass,
+ * whichever sides and however many merges reach it.  A NULL side leaves its ghost
+ * row alone.  The count is that of the whole list the next pass reads: tiles the
+ * passes queued plus merged ones.  DYMU_ERR_STATE without a live domain;
+ * DYMU_ERR_ARG for a row on a side without a ghost. */
 int dymu_dom_merge_ghosts(dymu_ctx* ctx, const double* new_lo, const double* new_hi,
                           int32_t* d_pending, void* stream);
 /* dymu_dom_merge_ghosts with the queued-tile count in the SAME launch (the
@@ -391,7 +405,12 @@ int dymu_dom_wait_post(dymu_ctx* ctx, uint32_t seq, double timeout_s, int32_t* v
  * old and new values is a valid upper bound.  The round's second pass records in
  * `ctl` the status a termination check needs: P (tiles queued for the round's two
  * first passes), S per side (pushes that carried a decrease) and R per side (the
- * smallest tag the round's merge read).  Kernel-5 domains, passes >= 2. */
+ * smallest tag the round's merge read).  Kernel-5 domains, passes >= 2.
+ * Initial state, set by the caller before the first round of a solve: `ctl` all
+ * zero bytes except bytes 32 .. 47 (the two words holding the smallest tag read per
+ * side), which are all ones; every `last` row and every receive row +inf; every
+ * tag 0.  A tag counts the pushes that carried a decrease: it stays 0 for a
+ * boundary row that never becomes finite, and +inf is never pushed. */
 #define DYMU_PEER_CTL_BYTES 128
 typedef struct dymu_peer_links {
   const double* recv[2];                 /* own receive rows: from rank-1 (0) / rank+1 (1) */

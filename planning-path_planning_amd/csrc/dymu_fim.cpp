@@ -2250,6 +2250,8 @@ int dymu_dom_round_peer(dymu_ctx* c, uint32_t passes, const dymu_peer_links* lin
                         void* stream) {
   if (!c || !links) return DYMU_ERR_ARG;
   static_assert(sizeof(PeerCtl) <= DYMU_PEER_CTL_BYTES, "peer control block");
+  // the initial state include/dymu_fim.h documents: zeros, bytes 32 .. 47 all ones
+  static_assert(offsetof(PeerCtl, rmin) == 32 && sizeof(PeerCtl::rmin) == 16, "documented rmin");
   HIPC(c, hipSetDevice(c->device));
   return dom_round_peer(c, passes, *links, pick_stream(c, stream));
 }

@@ -68,6 +68,22 @@ class DymuDomain(ctypes.Structure):
     ]
 
 
+PEER_CTL_BYTES = 128  # DYMU_PEER_CTL_BYTES
+PEER_CTL_RMIN = (32, 16)  # byte offset and size of the two rmin words (all ones at the start)
+
+
+class DymuPeerLinks(ctypes.Structure):
+    """dymu_peer_links: side 0 = the link to rank-1, side 1 = to rank+1; 0 = none."""
+    _fields_ = [
+        ("recv", ctypes.c_void_p * 2),
+        ("recv_tag", ctypes.c_void_p * 2),
+        ("send", ctypes.c_void_p * 2),
+        ("send_tag", ctypes.c_void_p * 2),
+        ("last", ctypes.c_void_p * 2),
+        ("ctl", ctypes.c_void_p),
+    ]
+
+
 class DymuCostState(ctypes.Structure):
     """dymu_cost_state: device pointers of the planner node fields."""
     FIELDS = ("cost", "raw_cost", "slope", "terrain", "is_obstacle", "hazard", "traff",
@@ -675,6 +691,30 @@ class Engine:
                          stream: int = 0):
         _check(self._lib.dymu_dom_merge_ghosts(self.ctx, new_lo or None, new_hi or None,
                                                pending or None, stream or None), self.ctx)
+
+    def dom_exchange(self, new_lo: int = 0, new_hi: int = 0, d_total: int = 0, stream: int = 0):
+        """dom_merge_ghosts with the queued-tile count in the same launch: *d_total (device
+        int32, required)."""
+        _check(self._lib.dymu_dom_exchange(self.ctx, new_lo or None, new_hi or None,
+                                           d_total or None, stream or None), self.ctx)
+
+    def dom_round(self, passes: int, new_lo: int = 0, new_hi: int = 0, d_total: int = 0,
+                  stream: int = 0):
+        """One fused round (kernel-5 domains, passes >= 2): the first pass merges the rows."""
+        _check(self._lib.dymu_dom_round(self.ctx, passes, new_lo or None, new_hi or None,
+                                        d_total or None, stream or None), self.ctx)
+
+    def dom_round_supported(self, passes: int) -> int:
+        return self._lib.dymu_dom_round_supported(self.ctx, passes)
+
+    def dom_round_capable(self, nx: int, nrows: int, passes: int) -> int:
+        return self._lib.dymu_dom_round_capable(self.ctx, nx, nrows, passes)
+
+    def dom_round_peer(self, passes: int, links: "DymuPeerLinks", stream: int = 0):
+        """dom_round with the peer push and the tagged merge; links: DymuPeerLinks (kept
+        alive by the caller for the call only)."""
+        _check(self._lib.dymu_dom_round_peer(self.ctx, passes, ctypes.addressof(links),
+                                             stream or None), self.ctx)
 
     def dom_pending(self, stream: int = 0) -> int:
         n = ctypes.c_uint64()

@@ -72,45 +72,62 @@ def test_virtual_slabs_match_oracle(dymu, oracle, S, nx, ny, goal, frac, kw):
     assert rounds > 1
 
 
-def solve_vdist(dymu, F, goal, S, K=8, **engine_kw):
+POISON = np.uint64(0x7FF8C0DEC0DEC0DE)  # in the padding of a pitched buffer (a quiet NaN)
+
+
+def solve_vdist(dymu, F, goal, S, K=8, pad=0, **engine_kw):
     """The native C++ sharded loop (libdymu_dist, dymu_vdist_solve): S slabs on
-    one GPU, device-to-device row exchange, lagged termination check."""
+    one GPU, device-to-device row exchange, lagged termination check.  pad > 0:
+    buffers of pitch ld = nx + pad, poisoned outside the domain (the padding columns,
+    and the ghost slot of a side without a neighbour); the poison must survive."""
     from dymu import dist
 
     ny, nx = F.shape
+    ld = nx + pad
     engs, dFs, dTs, geo = [], [], [], []
     for s in range(S):
         row0, nrows = dymu.slab_rows(ny, S, s)
         eng = dymu.Engine(**engine_kw)
-        dF = eng.alloc(8 * nrows * nx)
-        dT = eng.alloc(8 * (nrows + 2) * nx)
-        eng.h2d(dF, np.ascontiguousarray(F[row0:row0 + nrows]))
+        dF = eng.alloc(8 * nrows * ld)
+        dT = eng.alloc(8 * (nrows + 2) * ld)
+        Fh = np.full((nrows, ld), POISON, dtype=np.uint64)
+        Fh[:, :nx] = np.ascontiguousarray(F[row0:row0 + nrows]).view(np.uint64)
+        eng.h2d(dF, Fh)
+        if pad:
+            eng.h2d(dT, np.full((nrows + 2, ld), POISON, dtype=np.uint64))
         engs.append(eng)
         dFs.append(dF)
         dTs.append(dT)
         geo.append((row0, nrows))
-    stats = dist.vdist_solve(engs, dFs, dTs, nx, nx, ny, goal[0], goal[1], K)
+    stats = dist.vdist_solve(engs, dFs, dTs, ld, nx, ny, goal[0], goal[1], K)
     T = np.empty((ny, nx))
-    for eng, dF, dT, (row0, nrows) in zip(engs, dFs, dTs, geo):
-        buf = np.empty((nrows, nx))
-        eng.d2h(buf, dT + 8 * nx)
-        T[row0:row0 + nrows] = buf
+    for s, (eng, dF, dT, (row0, nrows)) in enumerate(zip(engs, dFs, dTs, geo)):
+        buf = np.empty((nrows + 2, ld), dtype=np.uint64)
+        eng.d2h(buf, dT)
+        T[row0:row0 + nrows] = buf[1:-1, :nx].view(np.float64)
+        if pad:
+            assert (buf[:, nx:] == POISON).all(), f"slab {s}: padding written"
+            assert s > 0 or (buf[0] == POISON).all(), "slab 0: the row above it written"
+            assert s < S - 1 or (buf[-1] == POISON).all(), "last slab: the row below it written"
         eng.free(dF)
         eng.free(dT)
         eng.close()
     return T, stats
 
 
-@pytest.mark.parametrize("S,nx,ny,goal,frac,K", [(1, 96, 80, (10, 70), 0.02, 4),
-                                                 (2, 200, 160, (100, 40), 0.02, 8),
-                                                 (3, 130, 200, (7, 190), 0.05, 3),
-                                                 (4, 256, 256, (128, 128), 0.0, 16),
-                                                 (5, 64, 320, (32, 0), 0.03, 1)])
+@pytest.mark.parametrize("S,nx,ny,goal,frac,K,pad", [
+    pytest.param(1, 96, 80, (10, 70), 0.02, 4, 0, id="1-96-80-goal0-0.02-4"),
+    pytest.param(2, 200, 160, (100, 40), 0.02, 8, 0, id="2-200-160-goal1-0.02-8"),
+    pytest.param(3, 130, 200, (7, 190), 0.05, 3, 0, id="3-130-200-goal2-0.05-3"),
+    pytest.param(4, 256, 256, (128, 128), 0.0, 16, 0, id="4-256-256-goal3-0.0-16"),
+    pytest.param(5, 64, 320, (32, 0), 0.03, 1, 0, id="5-64-320-goal4-0.03-1"),
+    # ld = nx + 8: dymu_vdist_solve's pitch argument, poisoned padding
+    pytest.param(3, 130, 200, (7, 190), 0.05, 3, 8, id="3-130-200-pitched")])
 @pytest.mark.parametrize("kw", [dict(kernel=3), dict(kernel=5, prio_target=8)],
                          ids=["fim", "prio16"])
-def test_native_vdist_matches_oracle(dymu, oracle, S, nx, ny, goal, frac, K, kw):
+def test_native_vdist_matches_oracle(dymu, oracle, S, nx, ny, goal, frac, K, pad, kw):
     F = oracle.synth_speed(nx, ny, seed=37, obst_frac=frac, obst_seed=9, goal=goal)
-    T, stats = solve_vdist(dymu, F, goal, S, K=K, **kw)
+    T, stats = solve_vdist(dymu, F, goal, S, K=K, pad=pad, **kw)
     Tref, _ = oracle.fmm(F, goal)
     assert np.array_equal(np.isinf(T), np.isinf(Tref))
     fin = np.isfinite(Tref)
