@@ -109,7 +109,8 @@ int dymu_solve_device(dymu_ctx* ctx, const double* dF, double* dT, uint32_t nx, 
  * The reference stops its FMM as soon as the start node and its 4-neighbours
  * are CLOSED (isFullyClosedNode :424-436).  dymu_solve_until_device is
  * dymu_solve_device with that stop: it returns as soon as every queued tile's
- * priority key -- a lower bound on any value the remaining passes can produce --
+ * priority key -- a lower bound on any value the remaining passes can produce: the key
+ * bound stated at dymu_dom_min_key, which holds before every pass --
  * exceeds t = max T over the start (start_i, start_j) and its in-grid
  * 4-neighbours, or when the map has converged.  On return every cell whose
  * converged value is <= *t_closed = t holds that value (the reference's CLOSED
@@ -286,7 +287,7 @@ int dymu_gather_costs_device(dymu_ctx* ctx, const double* dT_stack, uint32_t nx,
  * +inf by definition) and is ignored.  (This differs from dymu_solve_until_device's
  * five-cell probe, where an obstacle among the start's neighbours reads +inf and makes
  * the solve run to the end.)  The solve returns at the first check at which the smallest
- * key of any queued tile exceeds t = max T over all counting targets of all planes, or
+ * key of any queued tile (the key bound of dymu_dom_min_key) exceeds t = max T over all counting targets of all planes, or
  * when the domain has converged; *t_closed = t.  On return every cell of every plane
  * whose converged value is <= *t_closed holds that value (dymu_solve_until_device's
  * contract); other cells hold upper bounds or +inf.  t_plane (host, B doubles, or NULL):
@@ -432,6 +433,36 @@ int dymu_dom_pending(dymu_ctx* ctx, void* stream, uint64_t* pending);
 /* End the domain solve; fills stats (passes, visits, sweeps). */
 int dymu_dom_finish(dymu_ctx* ctx, void* stream, dymu_stats* stats);
 
+/* ---- stepping: a device-resident entry stopped after its preparation ----
+ * With stepping on, dymu_solve_device, dymu_solve_seeds_device, dymu_solve_batch_device,
+ * dymu_resolve_window_device, dymu_update_window_device, dymu_update_seeds_window_device
+ * and dymu_update_batch_window_device do everything up to their first pass -- the fill
+ * and the seeds of a cold solve; theta, the reset (or the raise front) and the queued
+ * tiles of an update -- then synchronise `stream` and return DYMU_OK with the domain
+ * LIVE and *stats untouched.  The caller runs the passes with dymu_dom_run, reads
+ * dymu_dom_pending / dymu_dom_min_key between them and ends with dymu_dom_finish
+ * (stats.ms = 0); the map after the pass at which nothing is pending is the one the
+ * entry would have returned.  dymu_last_update_stats is valid as soon as the entry has
+ * returned.  The entries that cannot leave a domain behind return DYMU_ERR_STATE while
+ * stepping is on: dymu_solve, dymu_resolve_window (host buffers) and the *_until_*
+ * entries.  Off (the default) nothing changes.  For tests and diagnostics. */
+int dymu_set_stepping(dymu_ctx* ctx, int on);
+/* *key = the smallest priority key of the list the next pass reads, +inf when no tile is
+ * queued (synchronises `stream`).  The key bound every early exit rests on: before every
+ * pass, every cell whose value a later pass will still change ends at a value >= *key
+ * (within the parity bound 1e-12 * max(1, *key), which covers kernel 5's sweep sqrt).
+ * So once *key exceeds a value v, every cell whose converged value is <= v already holds
+ * it.  The keys: a seed (the goal: value 0) queues its own tile and (kernels 4 and 5; kernel
+ * 3 has no keys and queues the seed's tile only), where its cell lies on a tile edge, the
+ * tile across that edge -- whose cell next to the seed is updated
+ * from a value no visit changes -- each keyed with its smallest such seed value; a tile queued
+ * by a visit of its neighbour has the smallest value that visit changed on the shared
+ * edge; a tile deferred by key or by colour, or re-queued after a capped visit, keeps the
+ * key it had; the tiles an update queues have theta (below), a seed's tile its smallest
+ * t0 if that is lower.  A tile's key is the minimum over everything that queued it.
+ * DYMU_ERR_STATE without a live domain and for a domain on kernel 3 (no keys). */
+int dymu_dom_min_key(dymu_ctx* ctx, void* stream, double* key);
+
 /* Synthetic input generator on the device (bench/test data):
  *   F[k] = 1 + 4*u(seed, k),  u(s,k) = (splitmix64(s ^ k) >> 11) * 2^-53,
  *   obstacle (F = +inf) where u(obst_seed, k) < obst_frac, except the 3x3
@@ -490,7 +521,32 @@ int dymu_host_unregister(dymu_ctx* ctx, void* p);
  * boundary -- exact and smaller, but slower on config 5.
  * Increases and decreases are both handled; the result is the fixed point a
  * cold dymu_solve of the new speed reaches.
- * The window is clipped to the grid. */
+ * The window is clipped to the grid.
+ *
+ * The preparation, exactly (what dymu_set_stepping exposes; tiles are 8 x 8 cells for
+ * kernels 3 and 4, 16 x 16 for kernel 5; a tile is queued at most once):
+ * Theta reset (decrease_only = 0, no DYMU_RAISE).  theta = the minimum of old T over the
+ *   clipped window grown by one cell on every side and clipped again (+inf when all of
+ *   it is +inf).  A cell with old T >= theta is set to +inf, except the goal and cells
+ *   that already hold +inf; every other cell is not written (kept bit for bit, the
+ *   columns nx .. ld-1 included).  A tile is queued when it holds a cell with old
+ *   T >= theta (the goal excepted) of finite new speed that has an in-grid 4-neighbour
+ *   which is kept: old T < theta, or the goal.  The queued tiles are keyed theta.
+ * Decrease-only.  Nothing is written.  The tiles that meet the clipped window are
+ *   queued, keyed theta.
+ * Raise (DYMU_RAISE=1, decrease_only = 0).  The invalidated set S is the largest set of
+ *   live cells (finite old T, not the goal) such that every cell of S has new speed +inf
+ *   (or NaN), or has u > T * (1 + 1e-13), u being the reference update (:531-535) under
+ *   the new speed of its in-grid 4-neighbours' values with the cells of S (and off-grid
+ *   neighbours) at +inf.  The front starts from the window's cells and follows
+ *   4-neighbours, which finds all of S when T is a fixed point of the update under the
+ *   old speed within that tolerance.  S is set to +inf, nothing else is written.  A tile
+ *   is queued when it meets the clipped window, or holds a non-goal cell with T = +inf
+ *   and finite new speed that has a finite in-grid 4-neighbour; such a tile's key is the
+ *   smallest such neighbour value, and the list's smallest key is min(theta, those).
+ * dymu_last_update_stats after these single-goal forms: {raise passes, raise tile
+ * visits, |S|, 0} for the raise; all zeros for the theta reset (its reset cells are not
+ * counted, unlike the seeded form's below) and for decrease-only. */
 int dymu_resolve_window_device(dymu_ctx* ctx, const double* dF, double* dT, uint32_t nx,
                                uint32_t ny, uint64_t ld, uint32_t goal_i, uint32_t goal_j,
                                uint32_t i0, uint32_t j0, uint32_t w, uint32_t h, void* stream,
@@ -508,7 +564,9 @@ int dymu_update_window_device(dymu_ctx* ctx, const double* dF, double* dT, uint3
                               void* stream, dymu_stats* stats);
 /* What the last windowed update did before its re-solve: out[0] raise passes,
  * out[1] tiles visited by them, out[2] cells invalidated (the dependency cone of
- * the window's speed increases; 0s for decrease-only updates), out[3] reserved. */
+ * the window's speed increases; 0s for decrease-only updates and for the single-goal
+ * theta reset, which does not count the cells it resets), out[3] reserved.  Filled by the
+ * update's preparation: valid after a stepped entry has returned (dymu_set_stepping). */
 int dymu_last_update_stats(dymu_ctx* ctx, uint64_t out[4]);
 /* ---- windowed updates of seeded maps and of stacks ----
  * dymu_update_window_device for a seed list: dT holds the converged multi-source map of
@@ -523,7 +581,17 @@ int dymu_last_update_stats(dymu_ctx* ctx, uint64_t out[4]);
  * the theta reset (DYMU_RAISE is not consulted: the raise front is single-goal).
  * dymu_last_update_stats afterwards: out[0] = out[1] = 0, out[2] = the cells whose finite
  * old value was at or above theta (0 for decrease_only).  seeds: HOST array.  The window
- * is clipped to the grid.  DYMU_ERR_ARG, before any device work: a null pointer, ld < nx,
+ * is clipped to the grid.
+ * The preparation, exactly: the theta reset of dymu_resolve_window_device without an
+ * exempt cell -- every finite cell with old T >= theta is set to +inf, every other cell is
+ * not written; a tile is queued, keyed theta, when it holds a cell with old T >= theta of
+ * finite new speed with an in-grid 4-neighbour of old T < theta -- then every seed is
+ * min-written (T = min(T, t0): a kept seed cell is not changed) and every seed's tile,
+ * with (kernels 4 and 5) the tile across each tile edge the seed's cell lies on (tile
+ * edges of the whole stacked domain), is queued with the smallest t0 of those seeds as a key (a tile's key
+ * is the minimum of both; a seed in the reset region has t0 >= theta).  Nothing else is written; a tile is queued
+ * at most once; the list's smallest key is theta.  theta = +inf (a window on +inf cells
+ * only): no cell is reset and only the seeds' tiles are queued.  DYMU_ERR_ARG, before any device work: a null pointer, ld < nx,
  * dymu_solve_seeds_device's seed rules, w or h = 0, i0 >= nx, j0 >= ny. */
 int dymu_update_seeds_window_device(dymu_ctx* ctx, const double* dF, double* dT, uint32_t nx,
                                     uint32_t ny, uint64_t ld, const dymu_seed* seeds,

@@ -157,6 +157,9 @@ struct dymu_ctx {
   unsigned long long* d_until = nullptr;
   uint32_t until_cap = 0;
   uint64_t until_batch = 16;
+  // dymu_set_stepping: the device-resident entries return after their preparation with
+  // the domain live (converge_auto); the caller runs the passes (tests of the stages)
+  bool stepping = false;
 
   // profiling
   int profiling = 0;
@@ -378,10 +381,19 @@ int dom_begin(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t n
   }
   if (cold && gj >= 0) {
     const uint32_t gtile = (uint32_t)(gj / THd) * ntx + (uint32_t)(gi / TWd);
-    HIPC(c, launch_seed(dT, ld, gi, gj, D.lists[0], D.counts[0], c->d_tile_epoch, D.eb + 1, gtile,
-                        1, st));
+    // the goal's tile and, for the priority kernels, the tiles across the tile edges the
+    // goal lies on (SeedTiles)
+    SeedTiles gt{{gtile, 0u, 0u}, 1u};
+    if (is_prio(D.variant)) {
+      if (gi % TWd == 0 && gi > 0) gt.t[gt.n++] = gtile - 1u;
+      if (gi % TWd == TWd - 1 && gi + 1 < (int64_t)nx) gt.t[gt.n++] = gtile + 1u;
+      if (gj % THd == 0 && gj > 0) gt.t[gt.n++] = gtile - ntx;
+      if (gj % THd == THd - 1 && gj + 1 < (int64_t)nrows) gt.t[gt.n++] = gtile + ntx;
+    }
+    HIPC(c, launch_seed(dT, ld, gi, gj, D.lists[0], D.counts[0], c->d_tile_epoch, D.eb + 1, gt, 1,
+                        st));
     if (is_prio(D.variant))
-      HIPC(c, launch_prio_seed(c->d_keys, c->d_hist, c->d_prio, gtile, 0.0, st));
+      HIPC(c, launch_prio_seed(c->d_keys, c->d_hist, c->d_prio, gt, 0.0, st));
   }
   // kernel 5 edge columns: +inf (cold) plus the goal's tile; a warm domain
   // (resolve_core) rebuilds them from T once its seeding kernels have run (ec_sync)
@@ -937,6 +949,10 @@ int converge_stream(dymu_ctx* c, hipStream_t st, dymu_stats* stats,
 }
 
 int converge_auto(dymu_ctx* c, hipStream_t st, dymu_stats* stats) {
+  if (c->stepping) {  // the caller drives the live domain (dymu_set_stepping)
+    HIPC(c, hipStreamSynchronize(st));
+    return DYMU_OK;
+  }
   if (c->pipeline == 2 && c->d_mail && c->opts.passes_per_check <= 0)
     return converge_stream(c, st, stats);
   if (c->pipeline && c->d_mail && c->opts.passes_per_check <= 0)
@@ -974,6 +990,7 @@ int solve_until_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uin
                      uint64_t ld, uint32_t gi, uint32_t gj, uint32_t si, uint32_t sj,
                      hipStream_t st, double* t_closed, dymu_stats* stats) {
   if (gi >= nx || gj >= ny || si >= nx || sj >= ny || !t_closed) return DYMU_ERR_ARG;
+  if (c->stepping) return DYMU_ERR_STATE;
   int rc = dom_begin(c, dF, dT, nx, ny, ld, 0, 0, gi, gj, st, true, /*need_keys=*/true);
   if (rc) return rc;
   const ProbeCells p = start_probe(nx, ny, si, sj);
@@ -1233,6 +1250,7 @@ int solve_seeds_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uin
                      uint64_t ld, const dymu_seed* seeds, uint32_t n, hipStream_t st,
                      dymu_stats* stats, const UntilTargets* until = nullptr) {
   if (!dF || !dT || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
+  if (until && c->stepping) return DYMU_ERR_STATE;
   const GoalSeed* d_seeds = nullptr;
   double tmin = 0.0;
   const uint64_t tg_bytes = until ? sizeof(ProbeTarget) * (uint64_t)until->n : 0;
@@ -1625,6 +1643,7 @@ int dymu_solve_device(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, ui
 int dymu_solve(dymu_ctx* c, const double* F, uint32_t nx, uint32_t ny, uint32_t gi, uint32_t gj,
                double* T_out, dymu_stats* stats) {
   if (!c || !F || !T_out || nx == 0 || ny == 0) return DYMU_ERR_ARG;
+  if (c->stepping) return DYMU_ERR_STATE;
   HIPC(c, hipSetDevice(c->device));
   const uint64_t cells = (uint64_t)nx * ny;
   int rc = ensure_cells(c, cells);
@@ -2130,6 +2149,7 @@ int dymu_resolve_window(dymu_ctx* c, const double* F, uint32_t nx, uint32_t ny, 
                         uint32_t gj, uint32_t i0, uint32_t j0, uint32_t w, uint32_t h,
                         double* T_out, dymu_stats* stats) {
   if (!c || !F || !T_out || nx == 0 || ny == 0) return DYMU_ERR_ARG;
+  if (c->stepping) return DYMU_ERR_STATE;
   if (!c->host_valid || c->host_nx != nx || c->host_ny != ny || c->host_gi != gi ||
       c->host_gj != gj) {
     c->last_error = "dymu_resolve_window: no previous dymu_solve of this grid and goal";
@@ -2294,6 +2314,25 @@ int dymu_dom_pending(dymu_ctx* c, void* stream, uint64_t* pending) {
   if (!c || !pending) return DYMU_ERR_ARG;
   HIPC(c, hipSetDevice(c->device));
   return dom_pending(c, pick_stream(c, stream), pending);
+}
+
+int dymu_set_stepping(dymu_ctx* c, int on) {
+  if (!c) return DYMU_ERR_ARG;
+  c->stepping = on != 0;
+  return DYMU_OK;
+}
+
+int dymu_dom_min_key(dymu_ctx* c, void* stream, double* key) {
+  if (!c || !key) return DYMU_ERR_ARG;
+  auto& D = c->dom;
+  if (!D.live || !is_prio(D.variant)) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  HIPC(c, hipMemcpyAsync(c->h_probe, prio_minkey(c, D.p % 3), sizeof(unsigned long long),
+                         hipMemcpyDeviceToHost, st));
+  HIPC(c, hipStreamSynchronize(st));
+  std::memcpy(key, &c->h_probe[0], sizeof *key);
+  return DYMU_OK;
 }
 
 int dymu_dom_finish(dymu_ctx* c, void* stream, dymu_stats* stats) {

@@ -157,9 +157,20 @@ int pass_blocks_per_cu(int variant);
 
 hipError_t launch_fill_inf(double* T, uint64_t ld, uint32_t nx, int64_t row_lo, int64_t row_hi,
                            hipStream_t st);
+// The tiles a seeded cell queues: its own and, where the cell lies on a tile edge, the
+// tile across that edge.  A cell across the edge is updated from the seed's value, which
+// no visit of the seed's tile changes, and a visit queues its neighbours (and keys them)
+// for the edge values it CHANGED only: without these entries the tile across would be
+// keyed above the value its cell ends at, or, with every in-tile neighbour of the seed
+// blocked, never be queued at all.  Priority kernels (4, 5) only: the plain FIM (kernel 3)
+// queues the seed's own tile, as before.
+struct SeedTiles {
+  uint32_t t[3];
+  uint32_t n;
+};
 hipError_t launch_seed(double* T, uint64_t ld, int64_t gi, int64_t gj, uint32_t* list,
-                       uint32_t* count, uint32_t* tile_epoch, uint32_t epoch, uint32_t tile,
-                       int set_goal, hipStream_t st);
+                       uint32_t* count, uint32_t* tile_epoch, uint32_t epoch,
+                       const SeedTiles& tiles, int set_goal, hipStream_t st);
 hipError_t launch_pass_prio(const PassArgs& a, int blocks, hipStream_t st,
                            hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 hipError_t launch_pass_prio16(const PassArgs& a, int blocks, hipStream_t st,
@@ -387,8 +398,9 @@ struct SeedArgs {
   const double* delta;
   double* ec;  // kernel 5 edge columns, else null
 };
-// T[seed] = min(T, t0) for every seed; each seeded tile once into list 0, its key the
-// smallest seed value in it, binned against *base
+// T[seed] = min(T, t0) for every seed; each seeded tile (a seed's own and the tile across
+// each tile edge its cell lies on, see SeedTiles) once into list 0, its key the smallest
+// value of the seeds that queued it, binned against *base
 hipError_t launch_seed_goals(const SeedArgs& a, hipStream_t st);
 // L (nx * ny entries, pitch nx): per cell a resolved label (top bit set) or its parent's
 // cell index; then in-place pointer-jumping rounds (cnt[round] = entries still
@@ -432,7 +444,7 @@ hipError_t launch_prio_init(const double* F, int64_t ld, int64_t nx, int64_t ny,
                            unsigned long long* minkey, double* base, double* delta, double kappa,
                            hipStream_t st);
 hipError_t launch_prio_seed(unsigned long long* key0, uint32_t* hist0, unsigned long long* minkey0,
-                           uint32_t tile, double keyv, hipStream_t st);
+                           const SeedTiles& tiles, double keyv, hipStream_t st);
 hipError_t launch_synth(double* F, uint64_t ld, uint32_t nx, uint32_t ny, uint64_t row0,
                         uint64_t seed, double frac, uint64_t oseed, int64_t gi, int64_t gj,
                         hipStream_t st);

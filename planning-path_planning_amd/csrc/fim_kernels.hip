@@ -68,14 +68,15 @@ __global__ void k_fill_inf(double* T, uint64_t ld, uint32_t nx, int64_t row_lo, 
 }
 
 __global__ void k_seed(double* T, uint64_t ld, int64_t gi, int64_t gj, uint32_t* list,
-                       uint32_t* count, uint32_t* tile_epoch, uint32_t epoch, uint32_t tile,
+                       uint32_t* count, uint32_t* tile_epoch, uint32_t epoch, SeedTiles tiles,
                        int set_goal) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     if (set_goal) T[gj * (int64_t)ld + gi] = 0.0;
-    if (atomicMax(&tile_epoch[tile], epoch) < epoch) {
-      const uint32_t pos = atomicAdd(count, 1u);
-      list[pos] = tile;
-    }
+    for (uint32_t k = 0; k < tiles.n; ++k)
+      if (atomicMax(&tile_epoch[tiles.t[k]], epoch) < epoch) {
+        const uint32_t pos = atomicAdd(count, 1u);
+        list[pos] = tiles.t[k];
+      }
   }
 }
 
@@ -1586,12 +1587,12 @@ __global__ void k_prio_init(const double* F, int64_t ld, int64_t nx, int64_t ny,
   }
 }
 
-// The goal tile (or a re-seeded tile) enters list 0 with key keyv, bin 0.
+// The goal's tiles (SeedTiles) enter list 0 with key keyv, bin 0.
 __global__ void k_prio_seed(unsigned long long* key0, uint32_t* hist0, unsigned long long* minkey0,
-                            uint32_t tile, double keyv) {
+                            SeedTiles tiles, double keyv) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    key0[tile] = dbits(keyv);
-    hist0[0] += 1u;
+    for (uint32_t k = 0; k < tiles.n; ++k) key0[tiles.t[k]] = dbits(keyv);
+    hist0[0] += tiles.n;
     *minkey0 = dbits(keyv);
   }
 }
@@ -1759,10 +1760,10 @@ hipError_t launch_fill_inf(double* T, uint64_t ld, uint32_t nx, int64_t row_lo, 
 }
 
 hipError_t launch_seed(double* T, uint64_t ld, int64_t gi, int64_t gj, uint32_t* list,
-                       uint32_t* count, uint32_t* tile_epoch, uint32_t epoch, uint32_t tile,
-                       int set_goal, hipStream_t st) {
+                       uint32_t* count, uint32_t* tile_epoch, uint32_t epoch,
+                       const SeedTiles& tiles, int set_goal, hipStream_t st) {
   hipLaunchKernelGGL(k_seed, dim3(1), dim3(64), 0, st, T, ld, gi, gj, list, count, tile_epoch,
-                     epoch, tile, set_goal);
+                     epoch, tiles, set_goal);
   return hipGetLastError();
 }
 
@@ -1825,8 +1826,8 @@ hipError_t launch_prio_init(const double* F, int64_t ld, int64_t nx, int64_t ny,
 }
 
 hipError_t launch_prio_seed(unsigned long long* key0, uint32_t* hist0, unsigned long long* minkey0,
-                            uint32_t tile, double keyv, hipStream_t st) {
-  hipLaunchKernelGGL(k_prio_seed, dim3(1), dim3(64), 0, st, key0, hist0, minkey0, tile, keyv);
+                            const SeedTiles& tiles, double keyv, hipStream_t st) {
+  hipLaunchKernelGGL(k_prio_seed, dim3(1), dim3(64), 0, st, key0, hist0, minkey0, tiles, keyv);
   return hipGetLastError();
 }
 

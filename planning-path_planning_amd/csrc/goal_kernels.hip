@@ -36,6 +36,20 @@ __device__ __forceinline__ int key_bin(double k, double origin, double inv_delta
   return b < (float)(kBins - 1) ? (int)b : kBins - 1;
 }
 
+// fn(tile) for the tiles a seed queues (fim_kernels.h SeedTiles): its own, then the tile
+// across each tile edge its cell lies on
+template <class Fn>
+__device__ __forceinline__ void for_seed_tiles(const SeedArgs& a, const GoalSeed& sd, Fn fn) {
+  const uint32_t tile = (sd.j / a.th) * a.ntx + sd.i / a.tw;
+  fn(tile);
+  if (!a.keys) return;  // the plain FIM (kernel 3) keeps the seed's own tile only
+  const uint32_t ci = sd.i % a.tw, cj = sd.j % a.th;
+  if (ci == 0u && sd.i > 0u) fn(tile - 1u);
+  if (ci == a.tw - 1u && sd.i + 1u < a.nx) fn(tile + 1u);
+  if (cj == 0u && sd.j > 0u) fn(tile - a.ntx);
+  if (cj == a.th - 1u && sd.j + 1u < a.ny) fn(tile + a.ntx);
+}
+
 // t0 >= +0.0 and finite (checked on the host), so the bit patterns order like the values
 __global__ void k_seed_values(SeedArgs a) {
   for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < a.n; s += gridDim.x * blockDim.x) {
@@ -44,7 +58,7 @@ __global__ void k_seed_values(SeedArgs a) {
     const unsigned long long b = dbits(sd.t0);
     atomicMin(reinterpret_cast<unsigned long long*>(a.T + (int64_t)sd.j * a.ld + sd.i), b);
     const uint32_t tile = (sd.j / a.th) * a.ntx + sd.i / a.tw;
-    if (a.keys) atomicMin(&a.keys[tile], b);
+    if (a.keys) for_seed_tiles(a, sd, [&](uint32_t t) { atomicMin(&a.keys[t], b); });
     if (a.ec) {  // 16x16 tiles: column 0 -> ec[0..15], column 15 -> ec[16..31] (k_ec_rebuild)
       const uint32_t ci = sd.i % 16u, r = sd.j % 16u;
       if (ci == 0u || ci == 15u)
@@ -60,14 +74,15 @@ __global__ void k_seed_tiles(SeedArgs a) {
   for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < a.n; s += gridDim.x * blockDim.x) {
     const GoalSeed sd = a.seeds[s];
     if (sd.i >= a.nx || sd.j >= a.ny) continue;
-    const uint32_t tile = (sd.j / a.th) * a.ntx + sd.i / a.tw;
-    if (atomicMax(&a.tile_epoch[tile], a.epoch) < a.epoch) {
-      const uint32_t pos = atomicAdd(&a.counts[shard], 1u);
-      a.list[(uint64_t)shard * a.shard_cap + pos] = tile;
-      if (a.hist)
-        atomicAdd(&a.hist[shard * kBins + key_bin(bitsd(a.keys[tile]), *a.base, 1.0 / *a.delta)],
-                  1u);
-    }
+    for_seed_tiles(a, sd, [&](uint32_t tile) {
+      if (atomicMax(&a.tile_epoch[tile], a.epoch) < a.epoch) {
+        const uint32_t pos = atomicAdd(&a.counts[shard], 1u);
+        a.list[(uint64_t)shard * a.shard_cap + pos] = tile;
+        if (a.hist)
+          atomicAdd(&a.hist[shard * kBins + key_bin(bitsd(a.keys[tile]), *a.base, 1.0 / *a.delta)],
+                    1u);
+      }
+    });
   }
 }
 

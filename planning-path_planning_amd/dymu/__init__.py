@@ -170,6 +170,8 @@ FIM_SYMBOLS = {
     "dymu_dom_post": (_i32, [_vp, _vp, ctypes.POINTER(_u32)]),
     "dymu_dom_wait_post": (_i32, [_vp, _u32, ctypes.c_double, ctypes.POINTER(ctypes.c_int32),
                                   _vp]),
+    "dymu_set_stepping": (_i32, [_vp, _i32]),
+    "dymu_dom_min_key": (_i32, [_vp, _vp, ctypes.POINTER(ctypes.c_double)]),
     "dymu_dom_finish": (_i32, [_vp, _vp, ctypes.POINTER(DymuStats)]),
     "dymu_last_pass_timing": (_i32, [_vp, ctypes.POINTER(ctypes.c_double),
                                      ctypes.POINTER(ctypes.c_uint64)]),
@@ -720,6 +722,17 @@ class Engine:
         n = ctypes.c_uint64()
         _check(self._lib.dymu_dom_pending(self.ctx, stream or None, ctypes.byref(n)), self.ctx)
         return n.value
+
+    def set_stepping(self, on: bool = True):
+        """dymu_set_stepping: the device-resident entries return after their preparation
+        with the domain live; dom_run / dom_pending / dom_min_key / dom_finish drive it."""
+        _check(self._lib.dymu_set_stepping(self.ctx, int(bool(on))), self.ctx)
+
+    def dom_min_key(self, stream: int = 0) -> float:
+        """dymu_dom_min_key: the smallest key of the list the next pass reads (+inf: none)."""
+        k = ctypes.c_double()
+        _check(self._lib.dymu_dom_min_key(self.ctx, stream or None, ctypes.byref(k)), self.ctx)
+        return k.value
 
     def dom_finish(self, stream: int = 0) -> dict:
         st = DymuStats()
