@@ -129,7 +129,10 @@ constexpr int IP = 12;
 // slots apart -- so that with lane (r = lane>>2, q = lane&3) owning columns
 // 4q..4q+3 of row r, every ds_read_b64 of a half-sweep (W, E, N, S of the
 // lane's two same-colour cells) lands its 32 lanes on 32 distinct bank pairs and
-// every ds_write_b64 its 16-lane groups on distinct banks.  With a constant
+// every ds_write_b64 its 16-lane groups on distinct banks.  The sweep issues
+// exactly these: seven ds_read_b64 and two ds_write_b64 per half-sweep
+// (lds_read64 / img_put2 below; up to v35 the compiler paired plain accesses
+// into 3 ds_read2_b64 + 1 ds_read_b64 + 1 ds_write2_b64).  With a constant
 // pitch the colour offset (r & 1) leaves only two bank classes per row
 // parity: the former pitch-20 image had every read and write 2-way
 // (PMC SQ_LDS_BANK_CONFLICT 3.7 G cycles per 16384^2 solve, more than the LDS
@@ -138,6 +141,33 @@ __device__ __forceinline__ int img16_row(int r) {
   return 47 + 144 * (r >> 2) + 32 * (r & 3) + 2 * ((r >> 1) & 1);
 }
 constexpr int IMG16 = 640;  // img16_row(16) + 17
+
+// One 8-byte read of a __shared__ double that stays one ds_read_b64: a volatile
+// access in the LDS address space is not paired with its neighbours into
+// ds_read2_b64 (a volatile generic pointer would become flat_load_dwordx2).
+// p must point into LDS.
+__device__ __forceinline__ double lds_read64(const double* p) {
+  return *(const volatile __attribute__((address_space(3))) double*)p;
+}
+
+// the same for a store: one ds_write_b64, not half of a ds_write2_b64
+__device__ __forceinline__ void lds_write64(double* p, double v) {
+  *(volatile __attribute__((address_space(3))) double*)p = v;
+}
+
+// a half-sweep's two image writes (p[0], p[2]).  SPLIT (the product's form): two
+// ds_write_b64; otherwise plain stores, which the compiler pairs into one
+// ds_write2_b64 (tools/sweep_probe.hip compares the two)
+template <bool SPLIT = true>
+__device__ __forceinline__ void img_put2(double* p, double a, double b) {
+  if constexpr (SPLIT) {
+    lds_write64(p, a);
+    lds_write64(p + 2, b);
+  } else {
+    p[0] = a;
+    p[2] = b;
+  }
+}
 
 // v_min_f64 on operands that are never NaN (T >= 0 or +inf): one instruction,
 // no canonicalisation (the compiler cannot prove no-NaN for fmin).
@@ -749,15 +779,27 @@ __device__ __forceinline__ int visit8(const PassArgs& a, double* img, unsigned l
 // running one after the other behind per-cell branches.  Same operations as
 // rb_update: bit-identical results (a discarded two-sided candidate may be
 // NaN from a negative radicand; it is never selected).
-template <bool FAST, bool APPROX = false>
+// SINGLE (the product's form): the seven neighbour reads are seven ds_read_b64.
+// Left as plain loads, the load/store optimiser pairs six of them into three
+// ds_read2_b64 (+ one ds_read_b64), which take 8 LDS cycles each against 2 for
+// a ds_read_b64 -- 26 against 14 cycles per half-sweep for the same bytes
+// (tools/sweep_mix.py prints the loop's mix, profiles/r07/sweep_mix_v38.txt).
+// SINGLE = false keeps the merged form for tools/sweep_probe.hip to compare.
+template <bool FAST, bool APPROX = false, bool SINGLE = true>
 __device__ __forceinline__ void rb_update2(const double* p, const double* pn, const double* ps,
                                            double f0, double f1, double& t0, double& t1,
                                            bool& ch0, bool& ch1) {
   // p: the lane's first cell of this colour (the second is p + 2, same row);
   // pn / ps: the same column in the rows above / below (skewed image rows).
   // All neighbour reads in flight before the first use (cell 1's W is cell 0's E).
-  double w0 = p[-1], e0 = p[1], n0 = pn[0], so0 = ps[0];
-  double e1 = p[3], n1 = pn[2], so1 = ps[2];
+  double w0, e0, n0, so0, e1, n1, so1;
+  if constexpr (SINGLE) {
+    w0 = lds_read64(p - 1), e0 = lds_read64(p + 1), n0 = lds_read64(pn), so0 = lds_read64(ps);
+    e1 = lds_read64(p + 3), n1 = lds_read64(pn + 2), so1 = lds_read64(ps + 2);
+  } else {
+    w0 = p[-1], e0 = p[1], n0 = pn[0], so0 = ps[0];
+    e1 = p[3], n1 = pn[2], so1 = ps[2];
+  }
   // one wait for all of them (the v_min asm below would otherwise pin reads behind it);
   // cell 1's W is cell 0's E, one register (a separate asm operand costs a copy)
   asm volatile("" : "+v"(w0), "+v"(e0), "+v"(n0), "+v"(so0), "+v"(e1), "+v"(n1), "+v"(so1));
@@ -820,29 +862,30 @@ __device__ __forceinline__ int rb_sweeps4(double* pr, double* pb, int dn, int ds
   capped = true;
   // past stop_at (the pass deadline) a visit ends as if capped -- but only after
   // its first sweep pair, so every visit makes progress and the solve terminates
-  // (the low 32 bits of the 10-ns clock, compared wrap-safe: scalar instructions only)
-  while (sweeps < max_inner &&
-         (sweeps == 0 || (int32_t)(stop_at - (uint32_t)__builtin_amdgcn_s_memrealtime()) > 0)) {
+  // (the low 32 bits of the 10-ns clock, compared wrap-safe: scalar instructions only).
+  // The clock is read in the middle of the pair before the test, ahead of its
+  // second sweep's LDS reads: one wait covers both, where a read at the test
+  // itself stalls the wave with nothing else of its own in flight (v38: -0.3%
+  // per 16384^2 solve, one s_waitcnt fewer per pair).
+  uint32_t now = 0;
+  while (sweeps < max_inner && (sweeps == 0 || (int32_t)(stop_at - now) > 0)) {
     bool i0, i1, i2, i3;
     // two sweeps per convergence test: the second sweep's flags decide (a sweep
     // that changes nothing is the local fixed point)
     __builtin_amdgcn_wave_barrier();
     rb_update2<FAST, APPROX>(pr, prn, prs, fr[0], fr[1], tr[0], tr[1], i0, i1);
-    pr[0] = tr[0];
-    pr[2] = tr[1];
+    img_put2(pr, tr[0], tr[1]);
     __builtin_amdgcn_wave_barrier();
     rb_update2<FAST, APPROX>(pb, pbn, pbs, fb[0], fb[1], tb[0], tb[1], i2, i3);
-    pb[0] = tb[0];
-    pb[2] = tb[1];
+    img_put2(pb, tb[0], tb[1]);
     ++sweeps;
+    now = (uint32_t)__builtin_amdgcn_s_memrealtime();
     __builtin_amdgcn_wave_barrier();
     rb_update2<FAST, APPROX>(pr, prn, prs, fr[0], fr[1], tr[0], tr[1], i0, i1);
-    pr[0] = tr[0];
-    pr[2] = tr[1];
+    img_put2(pr, tr[0], tr[1]);
     __builtin_amdgcn_wave_barrier();
     rb_update2<FAST, APPROX>(pb, pbn, pbs, fb[0], fb[1], tb[0], tb[1], i2, i3);
-    pb[0] = tb[0];
-    pb[2] = tb[1];
+    img_put2(pb, tb[0], tb[1]);
     ++sweeps;
     // the lane masks of the four compares, or-ed in scalar registers (no VGPR round trip)
     if ((__builtin_amdgcn_ballot_w64(i0) | __builtin_amdgcn_ballot_w64(i1) |

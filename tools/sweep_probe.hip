@@ -3,11 +3,18 @@
 // fixed number of red-black sweep pairs over its own 16x16 tile image in LDS,
 // with kernel 5's own update (rb_update2<true, true>, fim_kernels.hip), and the
 // kernel is timed with events.  Variants:
-//   0  kernel 5's half-sweep: 8 LDS reads, the update, 2 LDS writes
-//   1  the same without the LDS writes (reads + VALU)
-//   2  LDS reads + writes with a single v_min instead of the update (LDS only)
-//   3  the update on register values only (VALU only, no LDS)
-// Waves per CU W = 4 / 8 / 12 / 16 give 1..4 waves per SIMD.
+//   0  kernel 5's half-sweep: 7 LDS reads, the update, 2 LDS writes  (full)
+//   1  the same without the LDS writes (reads + VALU)                (no-write)
+//   2  LDS reads + writes with a few v_min instead of the update     (LDS only)
+//   3  the update (cand_approx2) on register values only             (VALU only)
+// Read form: "merged" = plain loads, which the compiler pairs into 3
+// ds_read2_b64 + 1 ds_read_b64 per half-sweep (kernel 5 up to v35); "single" =
+// 7 ds_read_b64 (lds_read64, kernel 5 from v38).  Write form: "w2" = one
+// ds_write2_b64 per half-sweep (kernel 5 up to v35), "w1" = two ds_write_b64
+// (img_put2, kernel 5 from v38).
+// Waves per CU W = 4 / 8 / 12 / 16 give 1..4 waves per SIMD.  Each table is
+// printed REPS times so the run-to-run spread stands next to the differences.
+// Usage: sweep_probe [pairs = 20000] [reps = 3]
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -Iplanning-path_planning_amd/csrc \
 //          -Iinclude tools/sweep_probe.hip -o tools/sweep_probe
 #include "../planning-path_planning_amd/csrc/fim_kernels.hip"
@@ -18,7 +25,43 @@
 namespace probe {
 using namespace dymu;
 
-template <int V>
+// variant 2's half-sweep: the seven reads, three v_min per cell, the two writes
+template <bool SINGLE, bool SPLITW>
+__device__ __forceinline__ void lds_only(double* p, const double* pn, const double* ps, double& t0,
+                                         double& t1) {
+  double a0, a1, a2, a3, a4, a5, a6;
+  if constexpr (SINGLE) {
+    a0 = lds_read64(p - 1), a1 = lds_read64(p + 1), a2 = lds_read64(pn), a3 = lds_read64(ps);
+    a4 = lds_read64(p + 3), a5 = lds_read64(pn + 2), a6 = lds_read64(ps + 2);
+  } else {
+    a0 = p[-1], a1 = p[1], a2 = pn[0], a3 = ps[0], a4 = p[3], a5 = pn[2], a6 = ps[2];
+  }
+  t0 = vmin64(t0, vmin64(vmin64(a0, a1), vmin64(a2, a3)));
+  t1 = vmin64(t1, vmin64(vmin64(a1, a4), vmin64(a5, a6)));
+  img_put2<SPLITW>(p, t0, t1);
+}
+
+// variant 3's half-sweep: rb_update2<true, true>'s arithmetic, the seven
+// neighbour values made from the other colour's registers instead of read
+__device__ __forceinline__ void valu_only(double x0, double x1, double f0, double f1, double& t0,
+                                          double& t1, bool& ch0, bool& ch1) {
+  double w0 = x0 + 1, e0 = x1 + 2, n0 = x0 + 3, so0 = x1 + 4, e1 = x0 + 5, n1 = x1 + 6, so1 = x0 + 7;
+  asm volatile("" : "+v"(w0), "+v"(e0), "+v"(n0), "+v"(so0), "+v"(e1), "+v"(n1), "+v"(so1));
+  const double w1 = e0;
+  const double c20 = 2.0 * (f0 * f0), c21 = 2.0 * (f1 * f1);
+  const double tx0 = vmin64(w0, e0), ty0 = vmin64(n0, so0);
+  const double tx1 = vmin64(w1, e1), ty1 = vmin64(n1, so1);
+  const double m0 = vmin64(tx0, ty0), m1 = vmin64(tx1, ty1);
+  const double d0 = tx0 - ty0, d1 = tx1 - ty1;
+  double u0, u1;
+  cand_approx2(vmin64_abs(d0, f0), c20, m0, vmin64_abs(d1, f1), c21, m1, u0, u1);
+  ch0 = u0 < t0;
+  ch1 = u1 < t1;
+  t0 = vmin64(t0, u0);
+  t1 = vmin64(t1, u1);
+}
+
+template <int V, bool SINGLE, bool SPLITW>
 __global__ __launch_bounds__(1024) void k_probe(double* sink, int pairs) {
   __shared__ double s_img[16][IMG16];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -31,65 +74,28 @@ __global__ __launch_bounds__(1024) void k_probe(double* sink, int pairs) {
   double* pb = img + rb + 4 * q + 1 - odd;
   const double *prn = pr + dn, *prs = pr - ds, *pbn = pb + dn, *pbs = pb - ds;
   double fr[2] = {1.5 + 0.01 * lane, 2.5}, fb[2] = {3.0, 1.25 + 0.02 * lane};
+  __builtin_amdgcn_wave_barrier();
   double tr[2] = {pr[0], pr[2]}, tb[2] = {pb[0], pb[2]};
-  bool c0, c1, c2, c3;
+  bool c0 = false, c1 = false, c2 = false, c3 = false;
   __builtin_amdgcn_wave_barrier();
   for (int s = 0; s < pairs; ++s) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       if constexpr (V == 0 || V == 1) {
         __builtin_amdgcn_wave_barrier();
-        rb_update2<true, true>(pr, prn, prs, fr[0], fr[1], tr[0], tr[1], c0, c1);
-        if constexpr (V == 0) {
-          pr[0] = tr[0];
-          pr[2] = tr[1];
-        }
+        rb_update2<true, true, SINGLE>(pr, prn, prs, fr[0], fr[1], tr[0], tr[1], c0, c1);
+        if constexpr (V == 0) img_put2<SPLITW>(pr, tr[0], tr[1]);
         __builtin_amdgcn_wave_barrier();
-        rb_update2<true, true>(pb, pbn, pbs, fb[0], fb[1], tb[0], tb[1], c2, c3);
-        if constexpr (V == 0) {
-          pb[0] = tb[0];
-          pb[2] = tb[1];
-        }
+        rb_update2<true, true, SINGLE>(pb, pbn, pbs, fb[0], fb[1], tb[0], tb[1], c2, c3);
+        if constexpr (V == 0) img_put2<SPLITW>(pb, tb[0], tb[1]);
       } else if constexpr (V == 2) {
         __builtin_amdgcn_wave_barrier();
-        double a0 = pr[-1], a1 = pr[1], a2 = prn[0], a3 = prs[0], a4 = pr[3], a5 = prn[2], a6 = prs[2];
-        tr[0] = vmin64(tr[0], vmin64(vmin64(a0, a1), vmin64(a2, a3)));
-        tr[1] = vmin64(tr[1], vmin64(vmin64(a1, a4), vmin64(a5, a6)));
-        pr[0] = tr[0];
-        pr[2] = tr[1];
+        lds_only<SINGLE, SPLITW>(pr, prn, prs, tr[0], tr[1]);
         __builtin_amdgcn_wave_barrier();
-        double b0 = pb[-1], b1 = pb[1], b2 = pbn[0], b3 = pbs[0], b4 = pb[3], b5 = pbn[2], b6 = pbs[2];
-        tb[0] = vmin64(tb[0], vmin64(vmin64(b0, b1), vmin64(b2, b3)));
-        tb[1] = vmin64(tb[1], vmin64(vmin64(b1, b4), vmin64(b5, b6)));
-        pb[0] = tb[0];
-        pb[2] = tb[1];
-      } else {  // V == 3: the update's arithmetic on registers
-        double w0 = tb[0] + 1, e0 = tb[1] + 2, n0 = tb[0] + 3, s0 = tb[1] + 4;
-        asm volatile("" : "+v"(w0), "+v"(e0), "+v"(n0), "+v"(s0));
-        const double c20 = 2.0 * (fr[0] * fr[0]), c21 = 2.0 * (fr[1] * fr[1]);
-        const double tx0 = vmin64(w0, e0), ty0 = vmin64(n0, s0);
-        const double tx1 = vmin64(e0, n0), ty1 = vmin64(s0, w0);
-        const double m0 = vmin64(tx0, ty0), m1 = vmin64(tx1, ty1);
-        const double d0 = tx0 - ty0, d1 = tx1 - ty1;
-        double v0, v1;
-        two_sided_approx2(ty0, d0, c20, ty1, d1, c21, v0, v1);
-        const double u0 = fabs(d0) < fr[0] ? v0 : m0 + fr[0];
-        const double u1 = fabs(d1) < fr[1] ? v1 : m1 + fr[1];
-        tr[0] = vmin64(tr[0], u0);
-        tr[1] = vmin64(tr[1], u1);
-        double w1 = tr[0] + 1, e1 = tr[1] + 2, n1 = tr[0] + 3, s1 = tr[1] + 4;
-        asm volatile("" : "+v"(w1), "+v"(e1), "+v"(n1), "+v"(s1));
-        const double c22 = 2.0 * (fb[0] * fb[0]), c23 = 2.0 * (fb[1] * fb[1]);
-        const double tx2 = vmin64(w1, e1), ty2 = vmin64(n1, s1);
-        const double tx3 = vmin64(e1, n1), ty3 = vmin64(s1, w1);
-        const double m2 = vmin64(tx2, ty2), m3 = vmin64(tx3, ty3);
-        const double d2 = tx2 - ty2, d3 = tx3 - ty3;
-        double v2, v3;
-        two_sided_approx2(ty2, d2, c22, ty3, d3, c23, v2, v3);
-        const double u2 = fabs(d2) < fb[0] ? v2 : m2 + fb[0];
-        const double u3 = fabs(d3) < fb[1] ? v3 : m3 + fb[1];
-        tb[0] = vmin64(tb[0], u2);
-        tb[1] = vmin64(tb[1], u3);
+        lds_only<SINGLE, SPLITW>(pb, pbn, pbs, tb[0], tb[1]);
+      } else {
+        valu_only(tb[0], tb[1], fr[0], fr[1], tr[0], tr[1], c0, c1);
+        valu_only(tr[0], tr[1], fb[0], fb[1], tb[0], tb[1], c2, c3);
       }
     }
   }
@@ -107,38 +113,55 @@ __global__ __launch_bounds__(1024) void k_probe(double* sink, int pairs) {
     }                                                                     \
   } while (0)
 
-template <int V>
-static void run(double* sink, int cus, int waves, int pairs) {
+// ns per sweep pair (2 sweeps = 4 half-sweeps, 8 cell updates per lane) with
+// `waves` waves on every CU
+template <int V, bool SINGLE, bool SPLITW>
+static double run(double* sink, int cus, int waves, int pairs) {
   hipEvent_t a, b;
   CK(hipEventCreate(&a));
   CK(hipEventCreate(&b));
-  hipLaunchKernelGGL(probe::k_probe<V>, dim3(cus), dim3(64 * waves), 0, 0, sink, pairs);
+  hipLaunchKernelGGL((probe::k_probe<V, SINGLE, SPLITW>), dim3(cus), dim3(64 * waves), 0, 0, sink,
+                     pairs);
   CK(hipDeviceSynchronize());
   CK(hipEventRecord(a));
-  hipLaunchKernelGGL(probe::k_probe<V>, dim3(cus), dim3(64 * waves), 0, 0, sink, pairs);
+  hipLaunchKernelGGL((probe::k_probe<V, SINGLE, SPLITW>), dim3(cus), dim3(64 * waves), 0, 0, sink,
+                     pairs);
   CK(hipEventRecord(b));
   CK(hipEventSynchronize(b));
   float ms = 0;
   CK(hipEventElapsedTime(&ms, a, b));
-  // one sweep pair = 2 sweeps = 4 half-sweeps (8 cell updates per lane)
-  std::printf("variant %d waves/CU %2d (%d per SIMD): %.1f ns per sweep pair per wave\n", V, waves,
-              waves / 4, 1e6 * ms / pairs);
   CK(hipEventDestroy(a));
   CK(hipEventDestroy(b));
+  return 1e6 * ms / pairs;
+}
+
+template <bool SINGLE, bool SPLITW>
+static void table(double* sink, int cus, int pairs, int rep) {
+  for (int w : {4, 8, 12, 16}) {
+    const double full = run<0, SINGLE, SPLITW>(sink, cus, w, pairs);
+    const double now = run<1, SINGLE, SPLITW>(sink, cus, w, pairs);
+    const double lds = run<2, SINGLE, SPLITW>(sink, cus, w, pairs);
+    const double valu = run<3, SINGLE, SPLITW>(sink, cus, w, pairs);
+    std::printf("rep %d reads %-6s writes %s waves/CU %2d (%d per SIMD): full %7.1f  no-write %7.1f  "
+                "LDS-only %7.1f  VALU-only %7.1f  ns per sweep pair\n",
+                rep, SINGLE ? "single" : "merged", SPLITW ? "w1" : "w2", w, w / 4, full, now, lds,
+                valu);
+  }
 }
 
 int main(int argc, char** argv) {
   const int pairs = argc > 1 ? std::atoi(argv[1]) : 20000;
+  const int reps = argc > 2 ? std::atoi(argv[2]) : 3;
   int dev = 0, cus = 0;
   CK(hipGetDevice(&dev));
   CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   double* sink = nullptr;
   CK(hipMalloc(&sink, sizeof(double) * (size_t)cus * 1024));
-  for (int w : {4, 8, 12, 16}) {
-    run<0>(sink, cus, w, pairs);
-    run<1>(sink, cus, w, pairs);
-    run<2>(sink, cus, w, pairs);
-    run<3>(sink, cus, w, pairs);
+  for (int rep = 1; rep <= reps; ++rep) {
+    table<false, false>(sink, cus, pairs, rep);
+    table<true, false>(sink, cus, pairs, rep);
+    table<false, true>(sink, cus, pairs, rep);
+    table<true, true>(sink, cus, pairs, rep);
   }
   CK(hipFree(sink));
   return 0;
