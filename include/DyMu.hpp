@@ -417,8 +417,42 @@ class DyMuPathPlanner {
   bool localBlock(unsigned i, unsigned j, double* dev, double* tc, double* risk, uint8_t* state,
                   uint8_t* obst) const;
   unsigned resRatio() const { return res_ratio_; }
+  // ---- obstacle clearance for the global plan ----
+  // The reference keeps a rover away from an obstacle in the local layer only, after a
+  // repair (expandRisk / propagateRisk).  This gives the global layer the same notion for
+  // the obstacles already on the global map: R = max(1 - d / risk_distance, 0), d the
+  // distance (metres, Eikonal on the grid) to the nearest obstacle node, is one more
+  // per-cell factor of the speed every global solve runs on,
+  //   F = (global_res * cost * (2 + hazard - traff)) * (risk_ratio * R + 1),
+  // computed on the device (dymu_clearance_device) at the next speed synchronisation after
+  // the setting or the obstacles changed, and mirrored on the host.  Off by default and
+  // with either argument 0: then every call packs and launches what it did before.
+  // Independent of the constructor's risk_distance / risk_ratio (the local layer's).
+  // false, and nothing changes: a negative, NaN or infinite argument; a non-zero setting
+  // without a device engine or on an engine that lacks the entry.  A change re-packs the
+  // whole map at the next solve.
+  bool setGlobalRisk(double risk_distance, double risk_ratio);
+  double globalRiskDistance() const { return grisk_distance_; }
+  double globalRiskRatio() const { return grisk_ratio_; }
+  // R as [j][i] (recomputed first when stale); all zeros while the feature is off
+  std::vector<std::vector<double>> getGlobalRiskMatrix();
 
  private:
+  // the global risk: on iff both are > 0; R (ny*nx, empty while off) belongs to the
+  // obstacles and the distance it was computed for, else risk_stale_
+  double grisk_distance_ = 0.0, grisk_ratio_ = 0.0;
+  std::vector<double> global_risk_;
+  bool risk_stale_ = false;
+  bool globalRiskOn() const { return grisk_distance_ > 0 && grisk_ratio_ > 0; }
+  // the speed of a non-obstacle node (:527-528), with the risk factor while that is on:
+  // the one expression syncSpeed packs and propagateGlobalNode updates with
+  double nodeSpeed(uint64_t k) const {
+    const double f = global_res_ * cost_[k] * (2 + hazard_[k] - traff_[k]);
+    return global_risk_.empty() ? f : f * (grisk_ratio_ * global_risk_[k] + 1.0);
+  }
+  // R from the obstacles now on the map: the raw speed and the clearance field on
+  // temporary device maps, R = max(1 - S, 0); every row dirty
+  void refreshGlobalRisk();
   uint64_t idx(unsigned i, unsigned j) const { return (uint64_t)j * nx_ + i; }
   // total cost of cell k: the device map, fetched into the host mirror in blocks
   // of kBlk x kBlk cells on first read

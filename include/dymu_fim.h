@@ -319,6 +319,40 @@ int dymu_solve_batch_until_device(dymu_ctx* ctx, const double* dF_stack, double*
                                   const dymu_batch_cell* targets, uint32_t n_targets, void* stream,
                                   double* t_closed, double* t_plane, dymu_stats* stats);
 
+/* ---- obstacle clearance field and risk-inflated speed ----
+ * The clearance field of a speed map: the multi-source solution on the CONSTANT speed c
+ * with every obstacle cell of dF -- a cell with !(F < +inf): +inf or NaN -- seeded at 0,
+ * i.e. dymu_solve_seeds_device on a map of c with one seed (i, j, 0) per obstacle cell,
+ * taken from the device-resident map itself and stopped at the level 1.  With
+ * c = global_res / risk_distance the field is the distance to the nearest obstacle in
+ * units of the risk distance, and risk = max(1 - S, 0) is the reference's risk
+ * (src/DyMu_LocalPathRepairing.cpp:493-576), here for the global layer.
+ * dF: read only (by the seeding kernel alone).  dW: a caller-provided work map of nx x ny
+ * doubles at pitch ld; the call fills it with c in every cell, obstacles included, and
+ * solves on it; its contents afterwards are unspecified.  dS: the output.  On return every
+ * cell whose converged value is <= 1 holds that value (within the parity bound
+ * 1e-12 * max(1, S); an obstacle cell holds +0.0 exactly); every other cell holds an upper
+ * bound of its converged value or +inf -- dymu_solve_seeds_until_device's contract with the
+ * level fixed at 1: the solve ends at the first check at which the key bound of
+ * dymu_dom_min_key exceeds 1.0, or with nothing queued (checks every
+ * dymu_opts.passes_per_check passes when given, else after 16 passes and then every 16).
+ * A map without an obstacle cell: dS = +inf everywhere, stats->passes = 0, DYMU_OK.
+ * Runs a priority kernel (4 or 5) whatever dymu_opts.kernel says; deterministic and
+ * exact_sqrt as for any solve.  stats->ms covers the fill, the seeding and the passes.
+ * DYMU_ERR_ARG, before any device work: a null pointer (stats excepted), nx or ny = 0,
+ * ld < nx, c not > 0, NaN or infinite.  DYMU_ERR_STATE while stepping is on.  Blocks
+ * until the exit. */
+int dymu_clearance_device(dymu_ctx* ctx, const double* dF, double* dW, double* dS, uint32_t nx,
+                          uint32_t ny, uint64_t ld, double c, void* stream, dymu_stats* stats);
+/* The risk folded into the speed, per cell and operation by operation:
+ *   R = fmax(1.0 - S, 0.0);  out = F * (risk_ratio * R + 1.0)
+ * so S > 1, S = +inf and risk_ratio = 0 give F bit for bit, and an obstacle stays +inf or
+ * NaN by arithmetic.  dOut may be dF.  Asynchronous on `stream`.  DYMU_ERR_ARG: a null
+ * pointer, nx or ny = 0, ld < nx, risk_ratio negative, NaN or infinite. */
+int dymu_inflate_speed_device(dymu_ctx* ctx, const double* dF, const double* dS, double* dOut,
+                              uint32_t nx, uint32_t ny, uint64_t ld, double risk_ratio,
+                              void* stream);
+
 /* ---- row-slab domains (multi-GPU sharding; also single-GPU virtual slabs) ----
  * A rank owns rows [row0, row0+nrows) of an nx-wide global grid.  T points at
  * its first owned row; with ghost_lo the row above it (T - ld) holds the

@@ -150,6 +150,14 @@ int dymu_planner_set_hazard_density_window(dymu_planner* p, uint32_t i0, uint32_
                                            uint32_t h, const double* hd);
 int dymu_planner_set_trafficability_window(dymu_planner* p, uint32_t i0, uint32_t j0, uint32_t w,
                                            uint32_t h, const double* tr);
+/* DyMuPathPlanner::setGlobalRisk (off by default): the obstacle clearance
+ * of the global map as one more factor of the speed, F * (risk_ratio * R + 1) with
+ * R = max(1 - distance to the nearest obstacle / risk_distance, 0).  Either argument 0
+ * switches it off.  1 = set; 0 = rejected, nothing changed (a negative, NaN or infinite
+ * argument; a non-zero setting without a device engine). */
+int dymu_planner_set_global_risk(dymu_planner* p, double risk_distance, double risk_ratio);
+/* getGlobalRiskMatrix(): R, ny*nx (recomputed first when stale; zeros while off) */
+int dymu_planner_get_global_risk(dymu_planner* p, double* out);
 /* narrow-band cells left by the last computeTotalCostMap's early exit (0 after
  * computeEntireTotalCostMap) */
 int64_t dymu_planner_last_band_size(dymu_planner* p);

@@ -1,0 +1,163 @@
+// clearance_kernels.hip -- the obstacle clearance field and the risk-inflated speed
+// (DESIGN.md s5.11).
+//
+// The clearance field S is the multi-source solution on a constant speed c with every
+// obstacle cell of the speed map F (+inf or NaN) seeded at 0: S = 1 where a cell lies one
+// risk distance from the nearest obstacle (c = global_res / risk_distance), and the
+// reference's risk is max(1 - S, 0) (src/DyMu_LocalPathRepairing.cpp:493-576, there on
+// the local layer only).
+//
+// k_fill_const writes the constant work map.  k_seed_mask seeds a cold domain from F
+// itself, a workgroup on one tile at a time: what k_seed_values and k_seed_tiles (goal_kernels.hip)
+// do for a seed list on the host, for the millions of obstacle cells of a device-resident
+// map.  Every seed value is 0, so every key is 0 and every queued tile lands in bin 0 of a
+// histogram whose origin is 0: one launch, nothing depends on the order of arrival.  The
+// pass kernels run unchanged behind it.
+// k_inflate_speed folds the risk into the speed: out = F * (risk_ratio * R + 1).
+#include "fim_kernels.h"
+
+#include <algorithm>
+
+namespace dymu {
+namespace {
+
+constexpr double kInfD = __builtin_huge_val();
+
+// one lane per cell of a row strip, rows and column strips by grid stride (k_stack_speed)
+__global__ __launch_bounds__(256) void k_fill_const(double* __restrict__ W, uint64_t ld,
+                                                    uint32_t nx, uint32_t ny, double v) {
+  for (uint64_t r = blockIdx.y; r < ny; r += gridDim.y) {
+    double* d = W + r * ld;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < nx;
+         i += (uint64_t)gridDim.x * 256u)
+      d[i] = v;
+  }
+}
+
+// A workgroup of tw * th lanes takes one tile at a time (tiles by grid stride), one lane per
+// cell: S = 0 at the tile's obstacle cells.  A tile that has any enters list 0 with key 0
+// and, for the priority kernels, so does the tile across each tile edge an obstacle cell
+// lies on (fim_kernels.h SeedTiles: the cell across is updated from a value no visit
+// changes).  Each tile is claimed once through tile_epoch, whichever workgroups reach it;
+// lanes 0..4 make the up to five claims of a tile side by side.  The claimed tiles are
+// collected in LDS and published with one atomic per workgroup and flush, like the pass
+// kernels' enqueues: the kShards list counters share a cache line, and one atomic per
+// tile on it -- a million at 16384^2 -- took 11.9 ms there.
+constexpr uint32_t kMaskQueue = 1024;
+__global__ __launch_bounds__(256) void k_seed_mask(const double* __restrict__ F, MaskSeedArgs a,
+                                                   uint32_t ntiles) {
+  __shared__ uint32_t s_q[kMaskQueue];
+  __shared__ uint32_t s_n, s_base;
+  __shared__ uint32_t s_edges[2];  // per tile, alternating: bit 0 W, 1 E, 2 N, 3 S -- an
+                                   // obstacle on that edge with a tile across it
+  const uint32_t shard = blockIdx.x % kShards;
+  const uint32_t cj = threadIdx.x / a.tw, ci = threadIdx.x - cj * a.tw;
+  unsigned long long cells = 0;  // lane 0: the obstacle cells of this workgroup's tiles
+  if (threadIdx.x == 0) s_n = s_edges[0] = s_edges[1] = 0u;
+  __syncthreads();
+  // list 0 <- the collected tiles (all lanes, after a barrier behind the last claim)
+  auto flush = [&]() {
+    const uint32_t n = s_n;
+    if (threadIdx.x == 0) {
+      s_base = atomicAdd(&a.counts[shard], n);
+      if (a.hist) atomicAdd(&a.hist[shard * kBins], n);  // key_bin(0, base = 0) = 0
+    }
+    __syncthreads();
+    const uint32_t base = s_base;
+    for (uint32_t k = threadIdx.x; k < n; k += blockDim.x)
+      a.list[(uint64_t)shard * a.shard_cap + base + k] = s_q[k];
+    __syncthreads();
+    if (threadIdx.x == 0) s_n = 0u;
+    __syncthreads();
+  };
+  uint32_t it = 0;
+  for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, ++it) {
+    uint32_t* edges = &s_edges[it & 1u];
+    if (threadIdx.x == 0) s_edges[(it + 1u) & 1u] = 0u;  // the next tile's, last read a barrier ago
+    const uint32_t ty = tile / a.ntx, tx = tile - ty * a.ntx;
+    const uint32_t i = tx * a.tw + ci, j = ty * a.th + cj;
+    bool obst = false;
+    if (i < a.nx && j < a.ny) {
+      const int64_t k = (int64_t)j * a.ld + i;
+      obst = !(F[k] < kInfD);
+      if (obst) a.T[k] = 0.0;
+    }
+    if (obst) {
+      uint32_t e = 0u;
+      if (ci == 0u && i > 0u) e |= 1u;
+      if (ci == a.tw - 1u && i + 1u < a.nx) e |= 2u;
+      if (cj == 0u && j > 0u) e |= 4u;
+      if (cj == a.th - 1u && j + 1u < a.ny) e |= 8u;
+      if (e) atomicOr(edges, e);
+      // 16x16 tiles: column 0 -> ec[0..15], column 15 -> ec[16..31] (k_ec_rebuild); the
+      // edge columns are +inf after the cold dom_begin and this tile's are written here only
+      if (a.ec && (ci == 0u || ci == 15u))
+        a.ec[(uint64_t)tile * 32u + (ci ? 16u : 0u) + cj] = 0.0;
+    }
+    const int n_obst = __syncthreads_count(obst);
+    if (n_obst && threadIdx.x < 5u) {
+      const uint32_t e = *edges;
+      uint32_t t = tile;
+      bool want = true;  // lane 0: the tile itself; 1..4: the tiles across its W, E, N, S edge
+      if (threadIdx.x == 1u) want = e & 1u, t = tile - 1u;
+      if (threadIdx.x == 2u) want = e & 2u, t = tile + 1u;
+      if (threadIdx.x == 3u) want = e & 4u, t = tile - a.ntx;
+      if (threadIdx.x == 4u) want = e & 8u, t = tile + a.ntx;
+      if (threadIdx.x > 0u && !a.keys) want = false;  // the plain FIM: the own tile only
+      if (want) {
+        if (a.keys) a.keys[t] = 0ull;  // the bits of +0.0: no other value is stored before the passes
+        if (atomicMax(&a.tile_epoch[t], a.epoch) < a.epoch) s_q[atomicAdd(&s_n, 1u)] = t;
+      }
+      if (threadIdx.x == 0u) cells += (unsigned long long)n_obst;
+    }
+    __syncthreads();
+    if (s_n > kMaskQueue - 8u) flush();  // at most five more per tile
+  }
+  if (s_n > 0u) flush();
+  if (threadIdx.x == 0 && cells) atomicAdd(a.n_obst, cells);
+}
+
+// a wave on 64 consecutive doubles of a row, 2-D grid stride; out may be F (every cell is
+// read and written by its own lane)
+__global__ __launch_bounds__(256) void k_inflate_speed(const double* F, const double* S,
+                                                       double* out, uint64_t ld, uint32_t nx,
+                                                       uint32_t ny, double risk_ratio) {
+  for (uint64_t r = blockIdx.y; r < ny; r += gridDim.y) {
+    const uint64_t row = r * ld;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < nx;
+         i += (uint64_t)gridDim.x * 256u) {
+      const double R = fmax(1.0 - S[row + i], 0.0);
+      out[row + i] = F[row + i] * (risk_ratio * R + 1.0);
+    }
+  }
+}
+
+dim3 row_grid(uint32_t nx, uint32_t ny) {
+  const unsigned gx = (unsigned)std::min<uint64_t>(((uint64_t)nx + 255u) / 256u, 64u);
+  const unsigned gy = (unsigned)std::min<uint64_t>(ny, 16384u);
+  return dim3(gx, gy);
+}
+
+}  // namespace
+
+hipError_t launch_fill_const(double* W, uint64_t ld, uint32_t nx, uint32_t ny, double v,
+                             hipStream_t st) {
+  hipLaunchKernelGGL(k_fill_const, row_grid(nx, ny), dim3(256), 0, st, W, ld, nx, ny, v);
+  return hipGetLastError();
+}
+
+hipError_t launch_seed_mask(const double* F, const MaskSeedArgs& a, uint32_t ntiles, uint32_t blocks,
+                            hipStream_t st) {
+  hipLaunchKernelGGL(k_seed_mask, dim3(std::min(ntiles, std::max(blocks, 1u))), dim3(a.tw * a.th),
+                     0, st, F, a, ntiles);
+  return hipGetLastError();
+}
+
+hipError_t launch_inflate_speed(const double* F, const double* S, double* out, uint64_t ld,
+                                uint32_t nx, uint32_t ny, double risk_ratio, hipStream_t st) {
+  hipLaunchKernelGGL(k_inflate_speed, row_grid(nx, ny), dim3(256), 0, st, F, S, out, ld, nx, ny,
+                     risk_ratio);
+  return hipGetLastError();
+}
+
+}  // namespace dymu

@@ -1991,6 +1991,114 @@ int dymu_solve_seeds_until_device(dymu_ctx* c, const double* dF, double* dT, uin
                           &until);
 }
 
+/* ---- obstacle clearance field and risk-inflated speed ---- */
+
+namespace {
+// converge_targets with a constant level instead of a probe over target cells: K passes,
+// the key bound read back with the counters, compare.  Ends at the first check at which
+// every queued tile's key exceeds `level` (no pass can lower a value at or below it any
+// more), or with nothing queued.  The caller has recorded ev0 before its preparation.
+int converge_level(dymu_ctx* c, hipStream_t st, dymu_stats* stats, double level) {
+  const bool fixed = c->opts.passes_per_check > 0;
+  uint64_t K = fixed ? (uint64_t)c->opts.passes_per_check : c->first_batch;
+  for (;;) {
+    int rc = dom_launch(c, K, st);
+    if (rc == DYMU_OK) {
+      const hipError_t e =
+          hipMemcpyAsync(c->h_probe + 1, prio_minkey(c, c->dom.p % 3), sizeof(unsigned long long),
+                         hipMemcpyDeviceToHost, st);
+      if (e != hipSuccess) rc = fail_hip(c, e, "key bound read-back");
+    }
+    if (rc == DYMU_OK) {
+      uint64_t pending = 0;
+      rc = dom_pending(c, st, &pending);  // synchronises: the key bound is here too
+      if (rc == DYMU_OK) {
+        double kmin;
+        std::memcpy(&kmin, &c->h_probe[1], sizeof kmin);
+        if (kmin > level || pending == 0) break;
+      }
+    }
+    if (rc == DYMU_OK && c->dom.p >= c->dom.max_passes) {
+      c->last_error = "pass cap reached before convergence";
+      rc = DYMU_ERR_NOT_CONVERGED;
+    }
+    if (rc) {
+      dom_retire(c);
+      return rc;
+    }
+    if (!fixed) K = c->until_batch;
+  }
+  HIPC(c, hipEventRecord(c->ev1, st));
+  HIPC(c, hipEventSynchronize(c->ev1));
+  float ms = 0.f;
+  HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  return dom_finish(c, st, stats, ms);
+}
+}  // namespace
+
+int dymu_clearance_device(dymu_ctx* c, const double* dF, double* dW, double* dS, uint32_t nx,
+                          uint32_t ny, uint64_t ld, double step, void* stream, dymu_stats* stats) {
+  if (!c || !dF || !dW || !dS || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
+  if (!(step > 0.0) || !(step < __builtin_inf())) return DYMU_ERR_ARG;
+  if (c->stepping) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  HIPC(c, hipEventRecord(c->ev0, st));  // the fill and the seeding count as the call's time
+  HIPC(c, launch_fill_const(dW, ld, nx, ny, step, st));
+  int rc = dom_begin(c, dW, dS, nx, ny, ld, 0, 0, -1, -1, st, true, /*need_keys=*/true);
+  if (rc) return rc;
+  auto& D = c->dom;
+  MaskSeedArgs a{};
+  a.T = dS;
+  a.ld = (int64_t)ld;
+  a.nx = nx;
+  a.ny = ny;
+  a.tw = (uint32_t)tile_w(D.variant);
+  a.th = (uint32_t)tile_h(D.variant);
+  a.ntx = (uint32_t)D.a.ntx;
+  a.list = D.lists[0];
+  a.counts = D.counts[0];
+  a.shard_cap = D.ntiles;
+  a.tile_epoch = c->d_tile_epoch;
+  a.epoch = D.eb + 1;  // the epoch of list 0 (solve_seeds_core)
+  a.keys = prio_keys(c, 0);
+  a.hist = prio_hist(c, 0);
+  a.ec = D.a.ec;
+  a.n_obst = c->d_scratch + 4;
+  // list 0's smallest key and histogram origin: +0.0, the value of every seed
+  hipError_t e = launch_store_u64(prio_minkey(c, 0), 0ull, st);
+  if (e == hipSuccess)
+    e = launch_store_u64(reinterpret_cast<unsigned long long*>(prio_base(c, 0)), 0ull, st);
+  if (e == hipSuccess) e = launch_store_u64(a.n_obst, 0ull, st);
+  // 8 workgroups of at most 256 lanes per CU: all resident, their claims' latencies overlap
+  if (e == hipSuccess) e = launch_seed_mask(dF, a, D.ntiles, (uint32_t)c->cu_count * 8u, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(c->h_probe, a.n_obst, sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    dom_retire(c);
+    return fail_hip(c, e, "obstacle seeding");
+  }
+  if (c->h_probe[0] == 0ull) {  // no obstacle: the field is +inf everywhere, no pass runs
+    HIPC(c, hipEventRecord(c->ev1, st));
+    HIPC(c, hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    return dom_finish(c, st, stats, ms);
+  }
+  return converge_level(c, st, stats, 1.0);
+}
+
+int dymu_inflate_speed_device(dymu_ctx* c, const double* dF, const double* dS, double* dOut,
+                              uint32_t nx, uint32_t ny, uint64_t ld, double risk_ratio,
+                              void* stream) {
+  if (!c || !dF || !dS || !dOut || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
+  if (!(risk_ratio >= 0.0) || !(risk_ratio < __builtin_inf())) return DYMU_ERR_ARG;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, launch_inflate_speed(dF, dS, dOut, ld, nx, ny, risk_ratio, pick_stream(c, stream)));
+  return DYMU_OK;
+}
+
 int dymu_gather_costs_device(dymu_ctx* c, const double* dT_stack, uint32_t nx, uint32_t ny,
                              uint32_t B, uint64_t ld, double res, const double* d_xy, uint32_t M,
                              double* d_out, void* stream) {

@@ -439,6 +439,34 @@ hipError_t launch_probe_targets(const double* F, const double* T, uint64_t ld, u
                                 uint32_t n, const unsigned long long* minkey,
                                 unsigned long long* out, hipStream_t st);
 
+// obstacle clearance field and risk-inflated speed (clearance_kernels.hip)
+struct MaskSeedArgs {
+  double* T;  // the field: +inf after the cold dom_begin
+  int64_t ld;
+  uint32_t nx, ny;
+  uint32_t tw, th, ntx;
+  uint32_t* list;    // list 0 (kShards x shard_cap)
+  uint32_t* counts;  // its kShards counters
+  uint32_t shard_cap;
+  uint32_t* tile_epoch;
+  uint32_t epoch;
+  unsigned long long* keys;  // priority kernels: keys / histogram of list 0, else null
+  uint32_t* hist;
+  double* ec;                   // kernel 5 edge columns, else null
+  unsigned long long* n_obst;  // += the obstacle cells found (one atomic per workgroup)
+};
+// W (nx x ny, pitch ld) <- v
+hipError_t launch_fill_const(double* W, uint64_t ld, uint32_t nx, uint32_t ny, double v,
+                             hipStream_t st);
+// T = 0 at every cell whose F is +inf or NaN; each tile that holds one (and, with keys, the
+// tile across each tile edge such a cell lies on, see SeedTiles) once into list 0, key 0,
+// bin 0.  `blocks` workgroups, each on one tile at a time.
+hipError_t launch_seed_mask(const double* F, const MaskSeedArgs& a, uint32_t ntiles, uint32_t blocks,
+                            hipStream_t st);
+// out = F * (risk_ratio * max(1 - S, 0) + 1) per cell, operation by operation; out may be F
+hipError_t launch_inflate_speed(const double* F, const double* S, double* out, uint64_t ld,
+                                uint32_t nx, uint32_t ny, double risk_ratio, hipStream_t st);
+
 hipError_t launch_prio_init(const double* F, int64_t ld, int64_t nx, int64_t ny,
                            unsigned long long* keys, uint64_t nkeys, uint32_t* hist, uint64_t nhist,
                            unsigned long long* minkey, double* base, double* delta, double kappa,

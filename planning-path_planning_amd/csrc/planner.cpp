@@ -134,6 +134,8 @@ bool DyMuPathPlanner::initGlobalLayer(double globalres, double localres, unsigne
   manual_list_ = false;
   speed_.clear();
   speed_valid_ = false;
+  if (globalRiskOn()) global_risk_.assign(n, 0.0);
+  risk_stale_ = true;
   markDirty(0, ny_);
   return true;
 }
@@ -154,6 +156,7 @@ bool DyMuPathPlanner::setCostMap(std::vector<std::vector<double>> cost_map) {
       }
     }
   }
+  risk_stale_ = true;
   markDirty(0, ny_);
   return true;
 }
@@ -324,6 +327,7 @@ bool DyMuPathPlanner::costMapFromRows(const ERows& elev_row, const TRows& terr_r
     for (unsigned j = j0; j < j1; ++j)
       for (unsigned i = 0; i < nx_; ++i) smoothCost(i, j);
   });
+  risk_stale_ = true;
   markDirty(0, ny_);
   return true;
 }
@@ -555,6 +559,7 @@ void DyMuPathPlanner::ensureEngine() {
 // F = global_res * cost * (2 + hazard - traff) (:527-528), +inf for obstacles,
 // re-packed for the dirty rows; the rows whose F changed are uploaded.
 bool DyMuPathPlanner::syncSpeed(unsigned& i0, unsigned& i1, unsigned& j0, unsigned& j1) {
+  if (globalRiskOn() && risk_stale_) refreshGlobalRisk();
   i0 = nx_;
   i1 = 0;
   j0 = ny_;
@@ -567,7 +572,7 @@ bool DyMuPathPlanner::syncSpeed(unsigned& i0, unsigned& i1, unsigned& j0, unsign
     const uint64_t k0 = idx(0, j);
     for (unsigned i = 0; i < nx_; ++i) {
       const uint64_t k = k0 + i;
-      row_[i] = is_obstacle_[k] ? kInf : global_res_ * cost_[k] * (2 + hazard_[k] - traff_[k]);
+      row_[i] = is_obstacle_[k] ? kInf : nodeSpeed(k);
     }
     double* old = &speed_[k0];
     if (speed_valid_ && std::memcmp(row_.data(), old, sizeof(double) * nx_) == 0) continue;
@@ -597,6 +602,82 @@ bool DyMuPathPlanner::syncSpeed(unsigned& i0, unsigned& i1, unsigned& j0, unsign
     throw std::runtime_error(std::string("dymu: speed upload failed: ") + dymu_last_error(ctx_));
   }
   return true;
+}
+
+// ---- obstacle clearance for the global plan ----
+#pragma weak dymu_clearance_device
+
+bool DyMuPathPlanner::setGlobalRisk(double risk_distance, double risk_ratio) {
+  if (!(risk_distance >= 0) || !(risk_ratio >= 0) || !(risk_distance < kInf) ||
+      !(risk_ratio < kInf))
+    return false;
+  const bool on = risk_distance > 0 && risk_ratio > 0;
+  if (on) {  // computeTotalCostMaps' rule: no device engine, no change
+    if (!&dymu_clearance_device) return false;
+    try {
+      ensureEngine();
+    } catch (const std::exception&) {
+      return false;
+    }
+  }
+  if (risk_distance == grisk_distance_ && risk_ratio == grisk_ratio_) return true;
+  const bool was_on = globalRiskOn();
+  grisk_distance_ = risk_distance;
+  grisk_ratio_ = risk_ratio;
+  if (on) {
+    global_risk_.assign((uint64_t)nx_ * ny_, 0.0);
+    risk_stale_ = true;
+  } else {
+    std::vector<double>().swap(global_risk_);
+  }
+  if (on || was_on) markDirty(0, ny_);
+  return true;
+}
+
+void DyMuPathPlanner::refreshGlobalRisk() {
+  ensureEngine();
+  const uint64_t n = (uint64_t)nx_ * ny_;
+  if (n == 0) {
+    risk_stale_ = false;
+    return;
+  }
+  // the raw speed, through R's own buffer, into a temporary map: the obstacle mask the
+  // seeding kernel reads.  dF_ is not touched: it stays the upload of speed_, the speed
+  // the solved maps belong to and the next diff is taken against
+  global_risk_.resize(n);
+  for (uint64_t k = 0; k < n; ++k)
+    global_risk_[k] =
+        is_obstacle_[k] ? kInf : global_res_ * cost_[k] * (2 + hazard_[k] - traff_[k]);
+  void *f = nullptr, *w = nullptr, *s = nullptr;
+  int rc = dymu_device_alloc(ctx_, sizeof(double) * n, &f);
+  if (rc == DYMU_OK) rc = dymu_device_alloc(ctx_, sizeof(double) * n, &w);
+  if (rc == DYMU_OK) rc = dymu_device_alloc(ctx_, sizeof(double) * n, &s);
+  if (rc == DYMU_OK) rc = dymu_memcpy_h2d(ctx_, f, global_risk_.data(), sizeof(double) * n);
+  dymu_stats st{};
+  if (rc == DYMU_OK)
+    rc = dymu_clearance_device(ctx_, static_cast<double*>(f), static_cast<double*>(w),
+                               static_cast<double*>(s), nx_, ny_, nx_,
+                               global_res_ / grisk_distance_, nullptr, &st);
+  if (rc == DYMU_OK) rc = dymu_memcpy_d2h(ctx_, global_risk_.data(), s, sizeof(double) * n);
+  const std::string err = rc == DYMU_OK ? "" : dymu_last_error(ctx_);
+  for (void* p : {f, w, s})
+    if (p) (void)dymu_device_free(ctx_, p);
+  if (rc != DYMU_OK) {  // still stale: the next synchronisation tries again
+    std::fill(global_risk_.begin(), global_risk_.end(), 0.0);
+    throw std::runtime_error(std::string("dymu: global risk: ") + dymu_strerror(rc) + " " + err);
+  }
+  for (uint64_t k = 0; k < n; ++k) global_risk_[k] = std::fmax(1.0 - global_risk_[k], 0.0);
+  risk_stale_ = false;
+  markDirty(0, ny_);
+}
+
+std::vector<std::vector<double>> DyMuPathPlanner::getGlobalRiskMatrix() {
+  std::vector<std::vector<double>> m(ny_, std::vector<double>(nx_, 0.0));
+  if (!globalRiskOn()) return m;
+  if (risk_stale_) refreshGlobalRisk();
+  for (unsigned j = 0; j < ny_; ++j)
+    for (unsigned i = 0; i < nx_; ++i) m[j][i] = global_risk_[idx(i, j)];
+  return m;
 }
 
 // Thread-safe (the band replay's threads read through it): a block's flag is read
@@ -2540,7 +2621,8 @@ void DyMuPathPlanner::propagateGlobalNode(unsigned i, unsigned j) {
     Tx = n2 ? t[k + 1] : kInf;
   else
     Tx = t[k - 1];
-  const double C = global_res_ * (cost_[k]) * (2 + hazard_[k] - traff_[k]);  // :527-528
+  if (globalRiskOn() && risk_stale_) refreshGlobalRisk();
+  const double C = nodeSpeed(k);  // :527-528, times the global risk's factor (s5.11)
   double Tn;
   if ((std::fabs(Tx - Ty) < C) && (Tx < kInf) && (Ty < kInf))
     Tn = (Tx + Ty + std::sqrt(2 * (C * C) - ((Tx - Ty) * (Tx - Ty)))) / 2;  // pow(., 2.0) == x*x

@@ -201,6 +201,16 @@ int dymu_planner_set_trafficability(dymu_planner* p, const double* tr) {
   return guarded([&] { return (int)p->pl.setTrafficability(std::vector<double>(tr, tr + n)); });
 }
 
+int dymu_planner_set_global_risk(dymu_planner* p, double risk_distance, double risk_ratio) {
+  if (!p) return DYMU_ERR_ARG;
+  return guarded([&] { return (int)p->pl.setGlobalRisk(risk_distance, risk_ratio); });
+}
+
+int dymu_planner_get_global_risk(dymu_planner* p, double* out) {
+  if (!p || !out) return DYMU_ERR_ARG;
+  return guarded([&] { from_rows(p->pl.getGlobalRiskMatrix(), out); return DYMU_OK; });
+}
+
 int dymu_planner_last_stats(dymu_planner* p, dymu_stats* out) {
   if (!p || !out) return DYMU_ERR_ARG;
   *out = p->pl.lastStats();

@@ -225,6 +225,10 @@ FIM_SYMBOLS = {
     "dymu_solve_batch_until_device": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _u32,
                                              _vp, _u32, _vp, ctypes.POINTER(ctypes.c_double),
                                              _vp, ctypes.POINTER(DymuStats)]),
+    "dymu_clearance_device": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, ctypes.c_double, _vp,
+                                     ctypes.POINTER(DymuStats)]),
+    "dymu_inflate_speed_device": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, ctypes.c_double,
+                                         _vp]),
     "dymu_device_alloc_cached": (_i32, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "dymu_memcpy2d_d2h": (_i32, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
                                  ctypes.c_size_t, ctypes.c_size_t]),
@@ -605,6 +609,24 @@ class Engine:
             ctypes.byref(tc), tp.ctypes.data, ctypes.byref(st)), self.ctx)
         return tc.value, tp[:B].copy(), st.as_dict()
 
+    # -- obstacle clearance field and risk-inflated speed --
+    def clearance_device(self, dF: int, dW: int, dS: int, nx: int, ny: int, ld: int, c: float,
+                         stream: int = 0) -> dict:
+        """dymu_clearance_device: dS = the multi-source solution on the constant speed c with
+        every obstacle cell of dF (+inf or NaN) seeded at 0, exact up to the level 1; dW is
+        a work map of the same shape."""
+        st = DymuStats()
+        _check(self._lib.dymu_clearance_device(self.ctx, dF, dW, dS, nx, ny, ld, c,
+                                               stream or None, ctypes.byref(st)), self.ctx)
+        return st.as_dict()
+
+    def inflate_speed(self, dF: int, dS: int, dOut: int, nx: int, ny: int, ld: int,
+                      risk_ratio: float, stream: int = 0):
+        """dymu_inflate_speed_device: dOut = dF * (risk_ratio * max(1 - dS, 0) + 1); dOut may
+        be dF."""
+        _check(self._lib.dymu_inflate_speed_device(self.ctx, dF, dS, dOut, nx, ny, ld,
+                                                   risk_ratio, stream or None), self.ctx)
+
     # -- windowed updates of seeded maps and stacks (DESIGN.md s5.8) --
     def update_seeds_window_device(self, dF: int, dT: int, nx: int, ny: int, ld: int, seeds,
                                    i0: int, j0: int, w: int, h: int,
@@ -875,6 +897,8 @@ PLANNER_SYMBOLS = {
     "dymu_planner_last_batch_solve_kind": (_i32, [_vp]),
     "dymu_planner_goal_cell": (_i32, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "dymu_planner_get_locomotion_mode": (_i32, [_vp, _d, _d, _d, _d, ctypes.c_char_p, _i32]),
+    "dymu_planner_set_global_risk": (_i32, [_vp, _d, _d]),
+    "dymu_planner_get_global_risk": (_i32, [_vp, _dp]),
     "dymu_planner_set_hazard_density": (_i32, [_vp, _dp]),
     "dymu_planner_set_trafficability": (_i32, [_vp, _dp]),
     "dymu_planner_last_stats": (_i32, [_vp, ctypes.POINTER(DymuStats)]),
@@ -1250,6 +1274,17 @@ class Planner:
         buf = ctypes.create_string_buffer(256)
         _check(min(0, self._lib.dymu_planner_get_locomotion_mode(self.h, *self._wp(w), buf, 256)))
         return buf.value.decode()
+
+    def setGlobalRisk(self, risk_distance: float, risk_ratio: float) -> bool:
+        """Obstacle clearance for the global plan: every global solve
+        runs on F * (risk_ratio * R + 1), R = max(1 - d / risk_distance, 0) with d the
+        distance to the nearest obstacle of the global map.  Either argument 0: off (the
+        default).  False: rejected, nothing changed."""
+        return _b(self._lib.dymu_planner_set_global_risk(self.h, risk_distance, risk_ratio))
+
+    def getGlobalRiskMatrix(self):
+        """R as [j][i]; zeros while the global risk is off."""
+        return self._matrix(self._lib.dymu_planner_get_global_risk)
 
     def setHazardDensity(self, hd) -> bool:
         return _b(self._lib.dymu_planner_set_hazard_density(self.h, self._grid(hd)))
