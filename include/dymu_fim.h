@@ -517,6 +517,19 @@ int dymu_synth_speed(dymu_ctx* ctx, double* dF, uint32_t nx, uint32_t ny, uint64
 int dymu_eikonal_batch(dymu_ctx* ctx, const double* tx, const double* ty, const double* c,
                        double* out, uint64_t n, int fast);
 
+/* Scheduling self-test: one wave runs the list scan every priority pass starts with
+ * (the shard prefix sums and the threshold bin b*) on the given inputs.
+ * counts: 16 shard counts; hist: the 16 x 64 key histogram (shard-major); target,
+ * target_frac, cap_frac: the pass's target in tiles, as at least this fraction of
+ * the listed tiles, and as at most this fraction (not below 256 tiles; 0 = no cap).
+ * prefix[0..16]: prefix[k] = counts[0] + .. + counts[k-1] (mod 2^32); *bstar: the
+ * first of bins 0..62 whose inclusive histogram prefix reaches the target, or 64 when
+ * target is 0, the list is no longer than the target, or no bin reaches it.
+ * Host pointers; blocks until done. */
+int dymu_pass_scan_probe(dymu_ctx* ctx, const uint32_t* counts, const uint32_t* hist,
+                         uint32_t target, float target_frac, float cap_frac, uint32_t* prefix,
+                         int32_t* bstar);
+
 /* Device memory helpers (so a host without torch can run the device path).
  * dymu_device_alloc returns uncached device memory (hipDeviceMallocUncached: no L2
  * lines of the maps are left dirty for each pass's end-of-kernel release to write

@@ -82,7 +82,7 @@ struct dymu_ctx {
   uint32_t* d_tile_epoch = nullptr;  // tiles_cap
   unsigned long long* d_stats = nullptr;  // kStatSlots
   // v4 priority state: keys 3 x tiles_cap, hist 3 x kShards x kBins,
-  // prio = {minkey[3] (u64), base[3] (f64), delta (f64)}
+  // prio = {minkey[3] (u64), base[3] (f64), delta (f64), 1 / delta (f64)}
   unsigned long long* d_keys = nullptr;
   uint32_t keys_cap = 0;
   uint32_t* d_hist = nullptr;
@@ -421,6 +421,11 @@ int dom_begin(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t n
   a.nx = nx;
   a.ny = nrows;
   a.ntx = (int)ntx;
+  {
+    const TileDiv td = tile_div(ntx);
+    a.ntx_mul = td.mul;
+    a.ntx_shift = td.shift;
+  }
   a.nty = (int)nty;
   a.ghost_lo = ghost_lo;
   a.ghost_hi = ghost_hi;
@@ -2470,6 +2475,32 @@ int dymu_eikonal_batch(dymu_ctx* c, const double* tx, const double* ty, const do
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, launch_eikonal_batch(tx, ty, cc, out, n, fast, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
+  return DYMU_OK;
+}
+
+int dymu_pass_scan_probe(dymu_ctx* c, const uint32_t* counts, const uint32_t* hist,
+                         uint32_t target, float target_frac, float cap_frac, uint32_t* prefix,
+                         int32_t* bstar) {
+  if (!c || !counts || !hist || !prefix || !bstar) return DYMU_ERR_ARG;
+  HIPC(c, hipSetDevice(c->device));
+  constexpr size_t n_in = kShards + (size_t)kShards * kBins, n_out = kShards + 2;
+  uint32_t* d = nullptr;
+  HIPC(c, hipMalloc(&d, sizeof(uint32_t) * (n_in + n_out)));
+  uint32_t out[n_out];
+  hipError_t e = hipMemcpyAsync(d, counts, sizeof(uint32_t) * kShards, hipMemcpyHostToDevice,
+                                c->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d + kShards, hist, sizeof(uint32_t) * kShards * kBins,
+                       hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess)
+    e = launch_pass_scan_probe(d, d + kShards, target, target_frac, cap_frac, d + n_in, c->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(out, d + n_in, sizeof out, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(d);
+  HIPC(c, e);
+  std::memcpy(prefix, out, sizeof(uint32_t) * (kShards + 1));
+  *bstar = (int32_t)out[kShards + 1];
   return DYMU_OK;
 }
 

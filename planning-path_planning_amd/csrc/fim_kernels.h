@@ -43,6 +43,8 @@ struct PassArgs {
   int64_t ld;
   int64_t nx, ny;   // local domain
   int ntx, nty;     // tiles
+  // kernel 5: tile / ntx = (tile * ntx_mul) >> ntx_shift for every tile < 2^25 (tile_div)
+  uint32_t ntx_mul, ntx_shift;
   int ghost_lo;     // row -1 exists in memory (read-only halo)
   int ghost_hi;     // row ny exists in memory (requires ny % tile height == 0)
   int max_inner;    // cap on in-tile sweeps per visit
@@ -66,7 +68,7 @@ struct PassArgs {
   unsigned long long* minkey_clear;
   const double* base_in;  // histogram origin of list p
   double* base_out;       // ... of list p+1 (= min key of list p, written by block 0)
-  const double* delta;    // histogram bin width (k_prio_init)
+  const double* delta;    // histogram bin width, and in delta[1] its reciprocal (k_prio_init)
   uint32_t target;        // tiles to relax per pass; 0 = all (plain FIM)
   float target_frac;      // ... at least this fraction of the active list
   float cap_frac;         // kernel 5: ... and at most this fraction (>= 256 tiles); 0 = off
@@ -133,6 +135,23 @@ struct PassArgs {
 constexpr int kPackShift = 25;
 constexpr uint32_t kTileMask = (1u << kPackShift) - 1u;
 
+// Division of a tile index by the tiles per row without a divider: with l =
+// ceil(log2 d), s = kPackShift + l and m = floor(2^s / d) + 1,
+//   floor(n * m / 2^s) = floor(n / d)   for every 0 <= n < 2^25, 1 <= d <= 2^25.
+// Proof: m = 2^s / d + e with 0 < e <= 1, so n * m / 2^s = n / d + n * e / 2^s, and the
+// excess n * e / 2^s < 2^25 / 2^s = 2^-l <= 1 / d; n / d lies at least 1 / d below the next
+// integer, so the floor does not change.  m <= 2^25 * (2^l / d) + 1 < 2^26 + 1 fits 32
+// bits and n * m < 2^52 fits 64.  tools/tile_div_check.cpp checks it against / and %.
+struct TileDiv {
+  uint32_t mul, shift;
+};
+inline TileDiv tile_div(uint32_t d) {
+  uint32_t l = 0;
+  while ((1ull << l) < d) ++l;
+  const uint32_t s = (uint32_t)kPackShift + l;
+  return TileDiv{(uint32_t)((1ull << s) / d + 1ull), s};
+}
+
 // per-pass statistics words (kernel 5)
 enum PassStat : int {
   kPsActive = 0,    // listed entries (block 0)
@@ -192,6 +211,12 @@ hipError_t launch_exchange(double* T, int64_t ld, int64_t nx, int64_t nrows, con
 hipError_t launch_eikonal_batch(const double* tx, const double* ty, const double* c, double* out,
                                 uint64_t n, int fast, hipStream_t st);
 hipError_t launch_sum_counts(const uint32_t* counts, int32_t* out, hipStream_t st);
+// one wave runs the priority passes' list scan (pass_scan) on kShards counts and a
+// kShards x kBins histogram: out[0 .. kShards] = the shard prefixes (s_pref),
+// out[kShards + 1] = the threshold bin b*
+hipError_t launch_pass_scan_probe(const uint32_t* counts, const uint32_t* hist, uint32_t target,
+                                  float target_frac, float cap_frac, uint32_t* out,
+                                  hipStream_t st);
 // edge columns of tiles [t0, t1) (16x16 tiles, ntx per row) from T (see PassArgs::ec)
 hipError_t launch_ec_rebuild(const double* T, uint64_t ld, uint32_t nx, uint32_t ny, double* ec,
                              uint32_t ntx, uint32_t t0, uint32_t t1, hipStream_t st);

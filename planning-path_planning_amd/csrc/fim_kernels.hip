@@ -672,6 +672,61 @@ __device__ __forceinline__ int key_bin(double k, double origin, double inv_delta
   return b < (float)(kBins - 1) ? (int)b : kBins - 1;
 }
 
+// x + (x of the lane CTRL selects), lanes without a source or outside ROWS add 0.
+// CTRL: a DPP control (0x110 + n = row_shr:n within the 16-lane rows, 0x142 =
+// row_bcast:15, 0x143 = row_bcast:31), ROWS: the row mask.  One v_add_u32_dpp, no
+// LDS round trip.
+template <int CTRL, int ROWS = 0xf>
+__device__ __forceinline__ uint32_t dpp_add(uint32_t x) {
+  return x + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROWS, 0xf, false);
+}
+
+// The list scan of a priority pass's prologue, one full wave.  c: lane k < kShards
+// holds shard k's count (the other lanes 0), h: lane b holds the histogram summed
+// over the shards.  Returns the threshold bin b* (kBins: relax every listed tile);
+// on return lane k < kShards of c holds count[0] + .. + count[k] (s_pref[k + 1]) and
+// n is their total.  The sums are mod 2^32 whichever way they are associated, so the
+// DPP scan (row shifts inside the 16-lane rows, then lane 15 of rows 0 and 2 into
+// rows 1 and 3, then lane 31 into rows 2 and 3) gives the bits of the former
+// __shfl_up steps (six ds_bpermute round trips on two values), which
+// DYMU_PASS_SCAN_SHFL keeps for A/B.  cap_frac 0: no cap (kernel 4).
+__device__ __forceinline__ int pass_scan(uint32_t& c, uint32_t h, int lane, uint32_t target0,
+                                         float target_frac, float cap_frac, uint32_t& n) {
+#ifdef DYMU_PASS_SCAN_SHFL
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t yc = __shfl_up(c, o), yh = __shfl_up(h, o);
+    if (lane >= o) {
+      c += yc;
+      h += yh;
+    }
+  }
+  n = __shfl(c, kShards - 1);
+#else
+  static_assert(kShards == 16 && kBins == 64, "one DPP row of counts, one wave of bins");
+  c = dpp_add<0x111>(c);
+  h = dpp_add<0x111>(h);
+  c = dpp_add<0x112>(c);
+  h = dpp_add<0x112>(h);
+  c = dpp_add<0x114>(c);
+  h = dpp_add<0x114>(h);
+  c = dpp_add<0x118>(c);
+  h = dpp_add<0x118>(h);
+  h = dpp_add<0x142, 0xa>(h);
+  h = dpp_add<0x143, 0xc>(h);
+  n = (uint32_t)__builtin_amdgcn_readlane((int)c, kShards - 1);
+#endif
+  const uint32_t fr = (uint32_t)(target_frac * (float)n);
+  uint32_t target = target0 > fr ? target0 : fr;
+  if (cap_frac > 0.0f) {  // at most this fraction of the list (not below 256 tiles)
+    uint32_t cf = (uint32_t)(cap_frac * (float)n);
+    cf = cf > 256u ? cf : 256u;
+    target = target < cf ? target : cf;
+  }
+  const unsigned long long m = __ballot(h >= target && lane < kBins - 1);
+  return (target0 > 0 && n > target && m) ? (int)__ffsll((long long)m) - 1 : kBins;
+}
+
 // ---- v4 tile visits: load tile + halo into the wave's LDS image, red-black
 // sweeps to local convergence, write back decreased cells, and leave in ek[0..3]
 // (S, W, E, N) the minimum decreased value on each edge (+inf bits: unchanged).
@@ -850,14 +905,14 @@ __device__ __forceinline__ void rb_update2(const double* p, const double* pn, co
   }
 }
 
-// pr / pb: the lane's first red / black cell in the image; dn / ds: slots to the
-// same column one row up / down (the lane's row and its neighbours, img16_row)
+// pr / pb: the lane's first red / black cell in the image; prn / prs, pbn / pbs: the
+// same column one row up / down (the lane's row and its neighbours, img16_row; Lane16)
 template <bool FAST, bool APPROX = false>
-__device__ __forceinline__ int rb_sweeps4(double* pr, double* pb, int dn, int ds,
+__device__ __forceinline__ int rb_sweeps4(double* pr, const double* prn, const double* prs,
+                                          double* pb, const double* pbn, const double* pbs,
                                           const double (&fr)[2], const double (&fb)[2],
                                           double (&tr)[2], double (&tb)[2], int max_inner,
                                           bool& capped, uint32_t stop_at) {
-  const double *prn = pr + dn, *prs = pr - ds, *pbn = pb + dn, *pbs = pb - ds;
   int sweeps = 0;
   capped = true;
   // past stop_at (the pass deadline) a visit ends as if capped -- but only after
@@ -902,24 +957,68 @@ struct NoGate {
   __device__ bool operator()() const { return true; }
 };
 
+// What a visit derives from the lane alone (16x16 tiles, one per wave): lane
+// (r = lane >> 2, q = lane & 3) owns the cells (r, 4q .. 4q+3), red columns cr0 =
+// 4q + (r & 1) and cr0 + 2, black columns cb0 = 4q + 1 - (r & 1) and cb0 + 2, and
+// these cells of its wave's image (LDS addresses, img16_row).  Its global addresses are a wave-uniform base (the tile's
+// cell (0, 0), its edge columns, its halo rows) plus one of the byte offsets kept
+// here.  k_fim_pass_dyn builds it once per pass, BEFORE the
+// prologue barrier -- the time every wave but the first spends waiting for the list
+// scan -- and pins it in registers: left to the compiler the same arithmetic is
+// hoisted out of the entry loop too, but lands behind the barrier, on the way to
+// the pass's first visit.
+using lds_f64 = __attribute__((address_space(3))) double;
+struct Lane16 {
+  uint32_t r8, q32;                // bytes: 8 r (edge columns), 32 q (halo rows)
+  uint64_t off_r, off_b;           // bytes from the tile's cell (0, 0) to (r, cr0) / (r, cb0)
+  lds_f64* row;                    // cell (r, 0); the halo columns are row[-1], row[16]
+  lds_f64 *pr, *prn, *prs;         // first red cell; the same column one row up / down
+  lds_f64 *pb, *pbn, *pbs;         // first black cell; ...
+  lds_f64 *hs, *hn;                // halo rows -1 / 16, column 4q
+};
+__device__ __forceinline__ Lane16 lane16(int lane, double* img, int64_t ld) {
+  Lane16 g;
+  const int r = lane >> 2, q = lane & 3, odd = r & 1;
+  const int cr0 = 4 * q + odd, cb0 = 4 * q + 1 - odd;
+  g.r8 = 8u * (uint32_t)r;
+  g.q32 = 32u * (uint32_t)q;
+  g.off_r = ((uint64_t)r * (uint64_t)ld + (uint64_t)cr0) * 8u;
+  g.off_b = ((uint64_t)r * (uint64_t)ld + (uint64_t)cb0) * 8u;
+  lds_f64* im = (lds_f64*)img;
+  const int rb = img16_row(r);
+  const int dn = img16_row(r + 1) - rb, ds = rb - img16_row(r - 1);
+  g.row = im + rb;
+  g.pr = g.row + cr0;
+  g.prn = g.pr + dn;
+  g.prs = g.pr - ds;
+  g.pb = g.row + cb0;
+  g.pbn = g.pb + dn;
+  g.pbs = g.pb - ds;
+  g.hs = im + img16_row(-1) + 4 * q;
+  g.hn = im + img16_row(16) + 4 * q;
+  // opaque from here on: nothing of it can be recomputed (sunk) behind the barrier
+  asm volatile("" : "+v"(g.r8), "+v"(g.q32), "+v"(g.off_r), "+v"(g.off_b), "+v"(g.row));
+  asm volatile("" : "+v"(g.pr), "+v"(g.prn), "+v"(g.prs), "+v"(g.pb), "+v"(g.pbn), "+v"(g.pbs));
+  asm volatile("" : "+v"(g.hs), "+v"(g.hn));
+  return g;
+}
+
 // gate(): wave-uniform, evaluated after the tile's loads are issued (so a key
 // load the gate waits on overlaps them); false = skip the visit, return -1.
 template <bool APPROX = false, class Gate = NoGate>
-__device__ __forceinline__ int visit16(const PassArgs& a, double* img, unsigned long long* ek,
-                                       bool has, int tx, int ty, int lane, bool& capped,
-                                       Gate gate, uint32_t stop_at) {
+__device__ __forceinline__ int visit16(const PassArgs& a, const Lane16& g, unsigned long long* ek,
+                                       bool has, int tx, int ty, bool& capped, Gate gate,
+                                       uint32_t stop_at) {
   const int cap = a.max_inner;
   constexpr int TT = 16;
-  const int r = lane >> 2, q = lane & 3, odd = r & 1;
-  const int cr[2] = {4 * q + odd, 4 * q + 2 + odd};
-  const int cb[2] = {4 * q + 1 - odd, 4 * q + 3 - odd};
-  const int rb = img16_row(r);  // slot of (r, 0); the halo columns are rb - 1, rb + 16
-  const int dn = img16_row(r + 1) - rb, ds = rb - img16_row(r - 1);
-  const int sr[2] = {rb + cr[0], rb + cr[1]};
-  const int sb[2] = {rb + cb[0], rb + cb[1]};
+  // a copy per visit: what is derived from it -- the edge-lane tests, the boundary
+  // path's indices -- is computed in the visit that needs it and holds no register
+  // (or parked SGPR) from the pass's start to its end
+  uint32_t r8 = g.r8, q32 = g.q32;
+  asm volatile("" : "+v"(r8), "+v"(q32));
+  const bool row0 = r8 == 0u, row15 = r8 == 8u * (TT - 1), col0 = q32 == 0u, col3 = q32 == 96u;
+  const bool odd = (r8 & 8u) != 0u;
   const int64_t i0 = (int64_t)tx * TT, j0 = (int64_t)ty * TT;
-  const int64_t gj = j0 + r;
-  const bool rowin = has && gj < a.ny;
   double tr[2], tb[2], fr[2], fb[2];
   double hw, he, hs[4], hn[4];
   // interior tile (wave-uniform): every cell and halo address is valid, so every
@@ -928,39 +1027,50 @@ __device__ __forceinline__ int visit16(const PassArgs& a, double* img, unsigned 
   // of their neighbours' addresses and are never stored to the image.
   const bool interior = has && i0 > 0 && i0 + TT < a.nx && (j0 > 0 || a.ghost_lo) &&
                         (j0 + TT < a.ny || (j0 + TT == a.ny && a.ghost_hi));
+  // wave-uniform bases; the lane's part of every address is a Lane16 offset
+  const char* T0 = (const char*)(a.T + j0 * a.ld + i0);
+  const char* F0 = (const char*)(a.F + j0 * a.ld + i0);
+  double* Tred = (double*)(T0 + g.off_r);  // (r, cr[k]) = Tred[2 k]
+  double* Tblk = (double*)(T0 + g.off_b);
+  const double* Fred = (const double*)(F0 + g.off_r);
+  const double* Fblk = (const double*)(F0 + g.off_b);
+  // the tile's edge columns, this lane's row
+  double* ecr = (double*)((const char*)(a.ec + ((uint64_t)ty * (uint64_t)a.ntx + (uint64_t)tx) * 32) +
+                          r8);
   if (interior) {
-    const double* Tr = a.T + gj * a.ld + i0;
-    const double* Fr = a.F + gj * a.ld + i0;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      tr[k] = Tr[cr[k]];
-      fr[k] = Fr[cr[k]];
-      tb[k] = Tr[cb[k]];
-      fb[k] = Fr[cb[k]];
+      tr[k] = Tred[2 * k];
+      fr[k] = Fred[2 * k];
+      tb[k] = Tblk[2 * k];
+      fb[k] = Fblk[2 * k];
     }
-    {  // the neighbours' edge columns: one line each instead of 16
-      const double* e = a.ec + ((uint64_t)ty * (uint64_t)a.ntx + (uint64_t)tx) * 32 + r;
-      hw = e[-32 + 16];
-      he = e[32];
-    }
-    const double* Ts = a.T + (j0 - 1) * a.ld + i0 + 4 * q;
-    const double* Tn = a.T + (j0 + TT) * a.ld + i0 + 4 * q;
+    // the neighbours' edge columns: one line each instead of 16
+    hw = ecr[-32 + 16];
+    he = ecr[32];
+    const double* Ts = (const double*)((const char*)(a.T + (j0 - 1) * a.ld + i0) + q32);
+    const double* Tn = (const double*)((const char*)(a.T + (j0 + TT) * a.ld + i0) + q32);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       hs[k] = Ts[k];
       hn[k] = Tn[k];
     }
   } else {
+    const int r = (int)(r8 >> 3), q = (int)(q32 >> 5);
+    const int cr[2] = {4 * q + (r & 1), 4 * q + 2 + (r & 1)};
+    const int cb[2] = {4 * q + 1 - (r & 1), 4 * q + 3 - (r & 1)};
+    const int64_t gj = j0 + r;
+    const bool rowin = has && gj < a.ny;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       tr[k] = fr[k] = tb[k] = fb[k] = dinf();
       if (rowin && i0 + cr[k] < a.nx) {
-        tr[k] = a.T[gj * a.ld + i0 + cr[k]];
-        fr[k] = a.F[gj * a.ld + i0 + cr[k]];
+        tr[k] = Tred[2 * k];
+        fr[k] = Fred[2 * k];
       }
       if (rowin && i0 + cb[k] < a.nx) {
-        tb[k] = a.T[gj * a.ld + i0 + cb[k]];
-        fb[k] = a.F[gj * a.ld + i0 + cb[k]];
+        tb[k] = Tblk[2 * k];
+        fb[k] = Fblk[2 * k];
       }
     }
     hw = dinf();
@@ -989,26 +1099,28 @@ __device__ __forceinline__ int visit16(const PassArgs& a, double* img, unsigned 
   }
   asm volatile("" ::: "memory");  // the loads above issue before the gate's wait
   if (!gate()) return -1;
-  if (q == 0) img[rb - 1] = hw;
-  if (q == 3) img[rb + TT] = he;
-  if (r == 0) {
+  if (col0) g.row[-1] = hw;
+  if (col3) g.row[TT] = he;
+  if (row0) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) img[img16_row(-1) + 4 * q + k] = hs[k];
+    for (int k = 0; k < 4; ++k) g.hs[k] = hs[k];
   }
-  if (r == TT - 1) {
+  if (row15) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) img[img16_row(TT) + 4 * q + k] = hn[k];
+    for (int k = 0; k < 4; ++k) g.hn[k] = hn[k];
   }
-  img[sb[0]] = tb[0];
-  img[sb[1]] = tb[1];
+  g.pb[0] = tb[0];
+  g.pb[2] = tb[1];
   const double tr0[2] = {tr[0], tr[1]}, tb0[2] = {tb[0], tb[1]};
   const bool fast = __all(!(fr[0] < kFastMinF) && !(fr[1] < kFastMinF) &&
                           !(fb[0] < kFastMinF) && !(fb[1] < kFastMinF));
   const int sweeps =
-      fast ? rb_sweeps4<true, APPROX>(img + sr[0], img + sb[0], dn, ds, fr, fb, tr, tb, cap,
-                                      capped, stop_at)
-           : rb_sweeps4<false>(img + sr[0], img + sb[0], dn, ds, fr, fb, tr, tb, cap, capped,
-                               stop_at);
+      fast ? rb_sweeps4<true, APPROX>((double*)g.pr, (const double*)g.prn, (const double*)g.prs,
+                                      (double*)g.pb, (const double*)g.pbn, (const double*)g.pbs,
+                                      fr, fb, tr, tb, cap, capped, stop_at)
+           : rb_sweeps4<false>((double*)g.pr, (const double*)g.prn, (const double*)g.prs,
+                               (double*)g.pb, (const double*)g.pbn, (const double*)g.pbs, fr, fb,
+                               tr, tb, cap, capped, stop_at);
   // write back decreased cells; dr/db: the decreased value or +inf.  Keys are
   // non-negative doubles, so the u64 order of their bits (ek) is their f64
   // order and the edge minima below are v_min_f64 / v_cmp_f64 work.
@@ -1016,8 +1128,8 @@ __device__ __forceinline__ int visit16(const PassArgs& a, double* img, unsigned 
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const bool cr_ = tr[k] < tr0[k], cb_ = tb[k] < tb0[k];
-    if (cr_) a.T[gj * a.ld + i0 + cr[k]] = tr[k];
-    if (cb_) a.T[gj * a.ld + i0 + cb[k]] = tb[k];
+    if (cr_) Tred[2 * k] = tr[k];
+    if (cb_) Tblk[2 * k] = tb[k];
     dr[k] = cr_ ? tr[k] : dinf();
     db[k] = cb_ ? tb[k] : dinf();
   }
@@ -1028,17 +1140,17 @@ __device__ __forceinline__ int visit16(const PassArgs& a, double* img, unsigned 
   // ulp, so an activation of that size can be skipped -- a deviation within the
   // solve tolerance, not a change of the fixed point's mask.
   auto across = [&](double v, double hx) { return (!a.prune || v < hx) ? v : dinf(); };
-  if (r == 0 || r == TT - 1) {  // S / N edge: rows 0 and 15 (disjoint lanes), halo row beyond
-    const int vo = r == 0 ? -ds : dn;
-    const double m = vmin64(vmin64(across(dr[0], img[sr[0] + vo]), across(dr[1], img[sr[1] + vo])),
-                            vmin64(across(db[0], img[sb[0] + vo]), across(db[1], img[sb[1] + vo])));
-    if (m < dinf()) atomicMin(&ek[r == 0 ? 0 : 3], dbits(m));
+  if (row0 || row15) {  // S / N edge: rows 0 and 15 (disjoint lanes), halo row beyond
+    const lds_f64 *vr = row0 ? g.prs : g.prn, *vb = row0 ? g.pbs : g.pbn;
+    const double m = vmin64(vmin64(across(dr[0], vr[0]), across(dr[1], vr[2])),
+                            vmin64(across(db[0], vb[0]), across(db[1], vb[2])));
+    if (m < dinf()) atomicMin(&ek[row0 ? 0 : 3], dbits(m));
   }
-  if (q == 0 || q == 3) {  // W / E edge: column 0 (cr[0] or cb[0]) / column 15 (cr[1] or cb[1])
-    const double c = q == 0 ? (odd ? db[0] : dr[0]) : (odd ? dr[1] : db[1]);
-    if (c < dinf()) a.ec[((uint64_t)ty * (uint64_t)a.ntx + (uint64_t)tx) * 32 + (q == 0 ? 0 : 16) + r] = c;
-    const double m = across(c, img[q == 0 ? rb - 1 : rb + TT]);
-    if (m < dinf()) atomicMin(&ek[q == 0 ? 1 : 2], dbits(m));
+  if (col0 || col3) {  // W / E edge: column 0 (cr[0] or cb[0]) / column 15 (cr[1] or cb[1])
+    const double c = col0 ? (odd ? db[0] : dr[0]) : (odd ? dr[1] : db[1]);
+    if (c < dinf()) ecr[col0 ? 0 : 16] = c;
+    const double m = across(c, g.row[col0 ? -1 : TT]);
+    if (m < dinf()) atomicMin(&ek[col0 ? 1 : 2], dbits(m));
   }
   return sweeps;
 }
@@ -1085,22 +1197,12 @@ __global__ __launch_bounds__(64 * WPB, 4) void k_fim_pass_prio(PassArgs a) {
     uint32_t h = 0;
 #pragma unroll
     for (int k = 0; k < kShards; ++k) h += a.hist_in[k * kBins + lane];
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t yc = __shfl_up(c, o), yh = __shfl_up(h, o);
-      if (lane >= o) {
-        c += yc;
-        h += yh;
-      }
-    }
+    uint32_t n;
+    const int bs = pass_scan(c, h, lane, a.target, a.target_frac, 0.0f, n);
     if (lane < kShards) s_pref[lane + 1] = c;
-    const uint32_t n = __shfl(c, kShards - 1);
-    const uint32_t fr = (uint32_t)(a.target_frac * (float)n);
-    const uint32_t target = a.target > fr ? a.target : fr;
-    const unsigned long long m = __ballot(h >= target && lane < kBins - 1);
     if (lane == 0) {
       s_pref[0] = 0u;
-      s_bstar = (a.target > 0 && n > target && m) ? (int)__ffsll((long long)m) - 1 : kBins;
+      s_bstar = bs;
       s_nq = 0;
       s_visits = 0;
       s_sweeps = 0;
@@ -1281,42 +1383,50 @@ __global__ __launch_bounds__(64 * WPB, 4) void k_fim_pass_dyn(PassArgs a) {
   const int lane = tid & 63;
   const int wv = tid >> 6;
   const uint32_t shard = blockIdx.x % kShards;
+  // the kernel arguments of the prologue in ONE batch of scalar loads: fetched where
+  // each is first used, they are four dependent round trips to the scalar cache
+  // ahead of wave 0's histogram loads, which every wave of the workgroup waits for
+  asm volatile("" ::"s"(a.trace), "s"(a.count_in), "s"(a.hist_in), "s"(a.base_in),
+               "s"(a.minkey_in), "s"(a.delta), "s"(a.ld));
   unsigned long long* trace = a.trace ? a.trace + (uint64_t)blockIdx.x * kTracePts : nullptr;
   const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
   // no deadline: 2^30 ticks (10.7 s) ahead, far beyond any pass
   const uint32_t stop_at = (uint32_t)t_start + (a.sweep_deadline ? a.sweep_deadline : (1u << 30));
   if (trace && tid == 0) trace[0] = t_start;
 
-  const double delta = *a.delta;
   const double origin_in = *a.base_in;
   const double origin_out = bitsd(*a.minkey_in);
-  const double inv_delta = 1.0 / delta;
+  const double inv_delta = a.delta[1];  // k_prio_init's 1.0 / delta: no division per wave
+  // Everything below up to the barrier is work the other 15 waves would otherwise
+  // wait through idle and then repeat behind it.  Wave 0 issues the loads of the
+  // scan first, so the lane geometry runs in the shadow of their latency.
+  uint32_t c = 0u, hk[kShards];
+#pragma unroll
+  for (int k = 0; k < kShards; ++k) hk[k] = 0u;
+  if (wv == 0) {
+    if (lane < kShards) c = a.count_in[lane];
+#pragma unroll
+    for (int k = 0; k < kShards; ++k) hk[k] = a.hist_in[k * kBins + lane];
+  }
+  const Lane16 g = lane16(lane, s_img[wv], a.ld);
+  // the entry loop's kernel arguments, fetched here in one batch while the wave waits
+  // for the scan anyway: behind the barrier their scalar loads (three dependent
+  // groups) then find the lines in the scalar cache
+  asm volatile("" ::"s"(a.T), "s"(a.F), "s"(a.nx), "s"(a.ny), "s"(a.ntx), "s"(a.nty),
+               "s"(a.list_in), "s"(a.key_in), "s"(a.key_out), "s"(a.tile_epoch), "s"(a.ec),
+               "s"(a.shard_cap), "s"(a.ntx_mul), "s"(a.ntx_shift), "s"(a.checker),
+               "s"(a.checker_parity), "s"(a.prune), "s"(a.pack_bins), "s"(a.list_out),
+               "s"(a.count_out), "s"(a.epoch), "s"(a.max_inner), "s"(gridDim.x));
   if (wv == 0) {  // shard prefix counts and the threshold bin (as k_fim_pass_prio)
-    uint32_t c = lane < kShards ? a.count_in[lane] : 0u;
     uint32_t h = 0;
 #pragma unroll
-    for (int k = 0; k < kShards; ++k) h += a.hist_in[k * kBins + lane];
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t yc = __shfl_up(c, o), yh = __shfl_up(h, o);
-      if (lane >= o) {
-        c += yc;
-        h += yh;
-      }
-    }
+    for (int k = 0; k < kShards; ++k) h += hk[k];
+    uint32_t n;
+    const int bs = pass_scan(c, h, lane, a.target, a.target_frac, a.cap_frac, n);
     if (lane < kShards) s_pref[lane + 1] = c;
-    const uint32_t n = __shfl(c, kShards - 1);
-    const uint32_t fr = (uint32_t)(a.target_frac * (float)n);
-    uint32_t target = a.target > fr ? a.target : fr;
-    if (a.cap_frac > 0.0f) {  // at most this fraction of the list (not below 256 tiles)
-      uint32_t cf = (uint32_t)(a.cap_frac * (float)n);
-      cf = cf > 256u ? cf : 256u;
-      target = target < cf ? target : cf;
-    }
-    const unsigned long long m = __ballot(h >= target && lane < kBins - 1);
     if (lane == 0) {
       s_pref[0] = 0u;
-      s_bstar = (a.target > 0 && n > target && m) ? (int)__ffsll((long long)m) - 1 : kBins;
+      s_bstar = bs;
       s_nq = 0;
       s_next = 0;
       s_merge = 0;
@@ -1373,7 +1483,6 @@ __global__ __launch_bounds__(64 * WPB, 4) void k_fim_pass_dyn(PassArgs a) {
 
   unsigned long long my_visits = 0, my_sweeps = 0, my_defer = 0;
   uint32_t my_cd = 0, my_cap = 0, my_dl = 0, my_rmax = 0, my_rmin = ~0u;  // a.pstat only
-  double* img = s_img[wv];
   unsigned long long* ek = s_ek[wv];
   // the workgroup's entries are every gridDim.x-th of the list from its own index, not
   // a contiguous chunk: a producer flushes its queue contiguously, so a chunk holds
@@ -1392,8 +1501,10 @@ __global__ __launch_bounds__(64 * WPB, 4) void k_fim_pass_dyn(PassArgs a) {
         __builtin_amdgcn_readfirstlane(list_at_wave(a.list_in, a.shard_cap, s_pref, e, lane));
     const uint32_t tile = ent & kTileMask;
     const int pbin = (int)(ent >> kPackShift) - 1;  // first-insertion bin, -1: none
-    const int tx = (int)(tile % (uint32_t)a.ntx);
-    const int ty = (int)(tile / (uint32_t)a.ntx);
+    // tile / ntx by the host's multiplier (tile_div, fim_kernels.h): scalar
+    // instructions only, no reciprocal sequence in the wave's path
+    const int ty = (int)(((uint64_t)tile * a.ntx_mul) >> a.ntx_shift);
+    const int tx = (int)(tile - (uint32_t)ty * (uint32_t)a.ntx);
     if (a.checker && ((uint32_t)(tx + ty) + a.checker_parity) % 2u != 0u) {
       // the other colour of the checkerboard: deferred with its key, tile not loaded
       if (lane == 0) {
@@ -1421,7 +1532,7 @@ __global__ __launch_bounds__(64 * WPB, 4) void k_fim_pass_dyn(PassArgs a) {
     if (trace && tid == 0 && first) trace[6] = __builtin_amdgcn_s_memrealtime();
     bool capped = false;
     const int sweeps = visit16<APPROX>(
-        a, img, ek, true, tx, ty, lane, capped,
+        a, g, ek, true, tx, ty, capped,
         [&] { return decided || key_bin(bitsd(kb), origin_in, inv_delta) <= bstar; }, stop_at);
     if (lane == 0) a.key_in[tile] = kInfBits;
     if (sweeps < 0) {  // deferred to the next pass with its key
@@ -1569,7 +1680,8 @@ __global__ __launch_bounds__(64 * WPB, 4) void k_fim_pass_dyn(PassArgs a) {
 }
 
 // Priority-pass state for a new solve: every key +inf, histograms zero, list-0
-// origin 0, bin width delta = kappa * mean finite F over a strided sample.
+// origin 0, bin width delta[0] = kappa * mean finite F over a strided sample and its
+// reciprocal in delta[1] (one division per solve instead of one per lane, wave and pass).
 __global__ void k_prio_init(const double* F, int64_t ld, int64_t nx, int64_t ny,
                             unsigned long long* keys, uint64_t nkeys, uint32_t* hist,
                             uint64_t nhist, unsigned long long* minkey, double* base,
@@ -1621,7 +1733,9 @@ __global__ void k_prio_init(const double* F, int64_t ld, int64_t nx, int64_t ny,
         c += s_cnt[k];
       }
       const double mean = c ? s / (double)c : 1.0;
-      *delta = (mean > 0.0 && mean < dinf()) ? kappa * mean : 1.0;
+      const double d = (mean > 0.0 && mean < dinf()) ? kappa * mean : 1.0;
+      delta[0] = d;
+      delta[1] = 1.0 / d;  // the bits every key_bin user's own 1.0 / *delta gives
       for (int k = 0; k < 3; ++k) {
         minkey[k] = kInfBits;
         base[k] = 0.0;
@@ -1973,6 +2087,34 @@ hipError_t launch_ec_rebuild(const double* T, uint64_t ld, uint32_t nx, uint32_t
   if (b == 0) return hipSuccess;
   hipLaunchKernelGGL(k_ec_rebuild, dim3((unsigned)b), dim3(256), 0, st, T, ld, nx, ny, ec, ntx, t0,
                      t1);
+  return hipGetLastError();
+}
+
+// pass_scan on given inputs (dymu_pass_scan_probe): 64 threads, loaded as the pass
+// kernels' wave 0 loads them
+__global__ __launch_bounds__(64) void k_pass_scan_probe(const uint32_t* counts,
+                                                        const uint32_t* hist, uint32_t target,
+                                                        float target_frac, float cap_frac,
+                                                        uint32_t* out) {
+  const int lane = threadIdx.x;
+  uint32_t c = lane < kShards ? counts[lane] : 0u;
+  uint32_t h = 0;
+#pragma unroll
+  for (int k = 0; k < kShards; ++k) h += hist[k * kBins + lane];
+  uint32_t n;
+  const int bs = pass_scan(c, h, lane, target, target_frac, cap_frac, n);
+  if (lane < kShards) out[lane + 1] = c;
+  if (lane == 0) {
+    out[0] = 0u;
+    out[kShards + 1] = (uint32_t)bs;
+  }
+}
+
+hipError_t launch_pass_scan_probe(const uint32_t* counts, const uint32_t* hist, uint32_t target,
+                                  float target_frac, float cap_frac, uint32_t* out,
+                                  hipStream_t st) {
+  hipLaunchKernelGGL(k_pass_scan_probe, dim3(1), dim3(64), 0, st, counts, hist, target,
+                     target_frac, cap_frac, out);
   return hipGetLastError();
 }
 

@@ -152,6 +152,8 @@ FIM_SYMBOLS = {
     "dymu_last_update_stats": (_i32, [_vp, ctypes.POINTER(_u64)]),
     "dymu_last_pass_stats": (_i32, [_vp, _vp, _u64, ctypes.POINTER(_u64)]),
     "dymu_eikonal_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _i32]),
+    "dymu_pass_scan_probe": (_i32, [_vp, _vp, _vp, _u32, ctypes.c_float, ctypes.c_float, _vp,
+                                    ctypes.POINTER(ctypes.c_int32)]),
     "dymu_slab_rows": (_i32, [_u32, _u32, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "dymu_dom_begin": (_i32, [_vp, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, _vp]),
     "dymu_dom_run": (_i32, [_vp, _u32, _vp]),
@@ -783,6 +785,21 @@ class Engine:
         finally:
             for p in ptrs:
                 self.free(p)
+
+    def pass_scan_probe(self, counts, hist, target: int, target_frac: float = 0.0,
+                        cap_frac: float = 0.0):
+        """dymu_pass_scan_probe: the priority passes' list scan on 16 shard counts and a
+        16 x 64 key histogram.  Returns (prefix[0..16] as uint32, b*)."""
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        hist = np.ascontiguousarray(hist, dtype=np.uint32)
+        if counts.shape != (16,) or hist.shape != (16, 64):
+            raise ValueError("counts: 16 words, hist: 16 x 64 words")
+        prefix = np.empty(17, dtype=np.uint32)
+        bstar = ctypes.c_int32()
+        _check(self._lib.dymu_pass_scan_probe(self.ctx, counts.ctypes.data, hist.ctypes.data,
+                                              target, target_frac, cap_frac, prefix.ctypes.data,
+                                              ctypes.byref(bstar)), self.ctx)
+        return prefix, bstar.value
 
     # ---- computeCostMap on the device (SURVEY s8(f)1) ----
     @staticmethod
