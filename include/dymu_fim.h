@@ -497,6 +497,55 @@ int dymu_set_stepping(dymu_ctx* ctx, int on);
  * DYMU_ERR_STATE without a live domain and for a domain on kernel 3 (no keys). */
 int dymu_dom_min_key(dymu_ctx* ctx, void* stream, double* key);
 
+/* ---- the state a domain starts from and carries between passes (tests, diagnostics) ----
+ * What an engine keeps from one solve to the next -- the tile-epoch stamps, the three
+ * lists with their counters, keys and histograms, the edge columns -- copied out of the
+ * LIVE domain (the one a stepped entry or dymu_dom_begin left) after a synchronisation
+ * of `stream`.  Read-only: the domain runs on as if the call had not been made.
+ * Scalars are always filled.  Each array goes to the host buffer given for it, or is
+ * skipped when that pointer is null; a buffer shorter than the array (its *_cap, in
+ * elements) is DYMU_ERR_ARG, so call once without buffers to learn the sizes. */
+typedef struct dymu_dom_state {
+  /* out */
+  uint32_t eb;         /* the domain's epoch base: the seed's tiles carry eb + 1, the tiles
+                          listed for pass p carry eb + p + 1, no stamp exceeds that */
+  uint32_t ntiles;     /* tiles of the domain */
+  uint32_t tiles_cap;  /* entries of the tile-epoch array (>= ntiles) */
+  int32_t variant;     /* pass kernel: 3, 4 or 5 */
+  uint64_t p;          /* index of the next pass; it reads list p % 3 */
+  const double* F;     /* device addresses and shape the passes use */
+  double* T;
+  uint64_t ld;
+  uint32_t nx, ny;
+  int32_t has_keys;    /* kernels 4 and 5: keys, hist, minkey, base, delta are valid */
+  int32_t has_ec;      /* kernel 5 with edge columns: ec is valid */
+  uint64_t list_n;     /* entries of the list the next pass reads (sum of its counters) */
+  uint64_t minkey[3];  /* per list: bits of its smallest key (+inf: none) */
+  double base[3];      /* per list: origin of its histogram */
+  double delta;        /* histogram bin width */
+  /* in: host buffers (null: skipped) and their capacities in elements */
+  uint32_t* tile_epoch;     /* tiles_cap stamps */
+  uint64_t tile_epoch_cap;
+  uint32_t* counts;         /* 3 lists x 16 shards, list-major (always 48 words) */
+  uint32_t* list_raw;       /* the next pass's list, shard after shard: entries as stored */
+  uint32_t* list_tile;      /* ... and their tile indices (the key-bin field masked off) */
+  uint64_t list_cap;        /* of each of the two; 16 * ntiles always suffices */
+  uint64_t* keys;           /* 3 lists x ntiles key bits, list-major */
+  uint64_t keys_cap;
+  uint32_t* hist;           /* 3 lists x 16 shards x 64 bins (always 3072 words) */
+  double* ec;               /* 32 * ntiles: per tile its column 0, then its column 15 */
+  uint64_t ec_cap;
+} dymu_dom_state;
+/* DYMU_ERR_STATE without a live domain, and (with nothing copied from the lists, the
+ * reason in dymu_last_error) if a shard counter exceeds the shard's capacity. */
+int dymu_dom_snapshot(dymu_ctx* ctx, void* stream, dymu_dom_state* state);
+/* epoch_base = max(epoch_base, value): the next domain's eb.  Only while no domain is
+ * live (else DYMU_ERR_STATE), and only ever upwards, so it cannot by itself leave a
+ * stamp above the base.  Its one purpose: 4 * 10^9 passes on one engine bring the base
+ * to the wrap guard of the 32-bit epochs (a domain that could reach 0xFFFFFFF0 clears
+ * the stamps and restarts at 0); this brings the guard within reach of a test. */
+int dymu_debug_raise_epoch_base(dymu_ctx* ctx, uint32_t value);
+
 /* Synthetic input generator on the device (bench/test data):
  *   F[k] = 1 + 4*u(seed, k),  u(s,k) = (splitmix64(s ^ k) >> 11) * 2^-53,
  *   obstacle (F = +inf) where u(obst_seed, k) < obst_frac, except the 3x3

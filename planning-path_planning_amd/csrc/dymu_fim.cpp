@@ -142,6 +142,7 @@ struct dymu_ctx {
   int map_mem = 2, ws_mem = 0, ec_mem = 0, key_mem = 0;
   double* d_ec = nullptr;
   uint64_t ec_cap = 0;  // tiles
+  std::vector<void*> parked;  // outgrown device buffers, freed by dymu_destroy (park)
   // windowed updates with increases: theta reset (0, default) or the raise front (1,
   // DYMU_RAISE=1: exact dependency cone, measured slower on config 5 -- 9.5 vs 4.1 ms
   // at 4096^2, profiles/r03/configs_4096_r03c.json); the last
@@ -201,30 +202,62 @@ hipError_t dev_alloc(P** p, size_t bytes, int kind) {
   return dev_alloc(reinterpret_cast<void**>(p), bytes, kind);
 }
 
-int ensure_tiles(dymu_ctx* c, uint32_t ntiles, hipStream_t st) {
-  if (ntiles <= c->tiles_cap) return DYMU_OK;
-  if (c->d_lists) (void)hipFree(c->d_lists);
-  if (c->d_tile_epoch) (void)hipFree(c->d_tile_epoch);
+// A buffer the engine has outgrown is kept until dymu_destroy, not freed: a solve whose
+// buffers were allocated where device memory had just been freed has returned wrong maps
+// (tools/history_probe.py, tests/test_gpu_engine_history.py).  A grown
+// capacity is at least twice the old one, so the parked buffers of a kind together stay
+// below the live one; if the doubled request does not fit, the exact one is tried.
+void park(dymu_ctx* c, void* p) {
+  if (p) c->parked.push_back(p);
+}
+uint64_t grown(uint64_t need, uint64_t cap, uint64_t limit) {
+  return std::min(std::max(need, 2 * cap), limit);
+}
+// alloc(n) for n = want, then n = need (want >= need): the capacity obtained, 0 if neither fits
+template <class Alloc>
+uint64_t alloc_grown(uint64_t want, uint64_t need, Alloc alloc) {
+  if (alloc(want) == hipSuccess) return want;
+  (void)hipGetLastError();
+  return want != need && alloc(need) == hipSuccess ? need : 0;
+}
+
+int ensure_tiles(dymu_ctx* c, uint32_t need, hipStream_t st) {
+  if (need <= c->tiles_cap) return DYMU_OK;
+  park(c, c->d_lists);
+  park(c, c->d_tile_epoch);
   c->d_lists = nullptr;
   c->d_tile_epoch = nullptr;
+  const uint64_t old = c->tiles_cap;
   c->tiles_cap = 0;
-  HIPC(c, dev_alloc(&c->d_lists, sizeof(uint32_t) * 3ull * kShards * ntiles, c->ws_mem));
-  HIPC(c, dev_alloc(&c->d_tile_epoch, sizeof(uint32_t) * (uint64_t)ntiles, c->ws_mem));
+  const uint32_t ntiles = (uint32_t)alloc_grown(grown(need, old, (1ull << 31) - 1), need, [&](uint64_t n) {
+    hipError_t e = dev_alloc(&c->d_lists, sizeof(uint32_t) * 3ull * kShards * n, c->ws_mem);
+    if (e != hipSuccess) return e;
+    e = dev_alloc(&c->d_tile_epoch, sizeof(uint32_t) * n, c->ws_mem);
+    if (e != hipSuccess) {
+      (void)hipFree(c->d_lists);  // never used: nothing was placed behind it
+      c->d_lists = nullptr;
+    }
+    return e;
+  });
+  if (!ntiles) return fail_hip(c, hipErrorOutOfMemory, "tile workspace");
   HIPC(c, hipMemsetAsync(c->d_tile_epoch, 0, sizeof(uint32_t) * (uint64_t)ntiles, st));
-  c->tiles_cap = ntiles;
-  c->epoch_base = 0;
+  c->tiles_cap = ntiles;  // epoch_base stays: every stamp of the new array is 0, below any base
   return DYMU_OK;
 }
 
-int ensure_prio(dymu_ctx* c, uint32_t ntiles) {
+int ensure_prio(dymu_ctx* c, uint32_t need) {
   // 3 list histograms + 2 rebuild buffers (deterministic mode)
   if (!c->d_hist) HIPC(c, hipMalloc(&c->d_hist, sizeof(uint32_t) * 5 * kShards * kBins));
   if (!c->d_prio) HIPC(c, hipMalloc(&c->d_prio, sizeof(unsigned long long) * 8));
-  if (ntiles <= c->keys_cap) return DYMU_OK;
-  if (c->d_keys) (void)hipFree(c->d_keys);
+  if (need <= c->keys_cap) return DYMU_OK;
+  park(c, c->d_keys);
   c->d_keys = nullptr;
+  const uint64_t old = c->keys_cap;
   c->keys_cap = 0;
-  HIPC(c, dev_alloc(&c->d_keys, sizeof(unsigned long long) * 3ull * ntiles, c->key_mem));
+  const uint32_t ntiles = (uint32_t)alloc_grown(grown(need, old, (1ull << 31) - 1), need, [&](uint64_t n) {
+    return dev_alloc(&c->d_keys, sizeof(unsigned long long) * 3ull * n, c->key_mem);
+  });
+  if (!ntiles) return fail_hip(c, hipErrorOutOfMemory, "tile keys");
   c->keys_cap = ntiles;
   return DYMU_OK;
 }
@@ -249,15 +282,26 @@ int ensure_xfer(dymu_ctx* c, uint64_t bytes) {
   return DYMU_OK;
 }
 
-int ensure_cells(dymu_ctx* c, uint64_t cells) {
-  if (cells <= c->cells_cap) return DYMU_OK;
+// the staged maps of the host path: outgrown ones are parked as well (see park)
+int ensure_cells(dymu_ctx* c, uint64_t need) {
+  if (need <= c->cells_cap) return DYMU_OK;
   c->host_valid = false;
-  if (c->d_F) (void)hipFree(c->d_F);
-  if (c->d_T) (void)hipFree(c->d_T);
+  park(c, c->d_F);
+  park(c, c->d_T);
   c->d_F = c->d_T = nullptr;
+  const uint64_t old = c->cells_cap;
   c->cells_cap = 0;
-  HIPC(c, dev_alloc(&c->d_F, sizeof(double) * cells, c->map_mem));
-  HIPC(c, dev_alloc(&c->d_T, sizeof(double) * cells, c->map_mem));
+  const uint64_t cells = alloc_grown(grown(need, old, ~0ull >> 4), need, [&](uint64_t n) {
+    hipError_t e = dev_alloc(&c->d_F, sizeof(double) * n, c->map_mem);
+    if (e != hipSuccess) return e;
+    e = dev_alloc(&c->d_T, sizeof(double) * n, c->map_mem);
+    if (e != hipSuccess) {
+      (void)hipFree(c->d_F);  // never used
+      c->d_F = nullptr;
+    }
+    return e;
+  });
+  if (!cells) return fail_hip(c, hipErrorOutOfMemory, "staged maps");
   c->cells_cap = cells;
   return DYMU_OK;
 }
@@ -335,7 +379,9 @@ int dom_begin(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t n
   D.ntiles = ntiles;
   D.max_passes = c->opts.max_passes > 0 ? (uint64_t)c->opts.max_passes : 4ull * ntiles + 1024ull;
   if ((uint64_t)c->epoch_base + D.max_passes + kPassSlack + 8 >= 0xFFFFFFF0ull) {
-    HIPC(c, hipMemsetAsync(c->d_tile_epoch, 0, sizeof(uint32_t) * (uint64_t)ntiles, st));
+    // the epochs wrap: every stamp of the array, not this domain's ntiles only -- a stamp
+    // left beyond them would keep its tile out of every list of a later, larger domain
+    HIPC(c, hipMemsetAsync(c->d_tile_epoch, 0, sizeof(uint32_t) * (uint64_t)c->tiles_cap, st));
     c->epoch_base = 0;
   }
   D.eb = c->epoch_base;
@@ -400,11 +446,15 @@ int dom_begin(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t n
   a.ec = nullptr;
   if (D.variant == 5 && c->use_ec) {
     if (c->ec_cap < ntiles) {
-      if (c->d_ec) (void)hipFree(c->d_ec);
+      park(c, c->d_ec);
       c->d_ec = nullptr;
+      const uint64_t old = c->ec_cap;
       c->ec_cap = 0;
-      HIPC(c, dev_alloc(&c->d_ec, sizeof(double) * 32 * (uint64_t)ntiles, c->ec_mem));
-      c->ec_cap = ntiles;
+      const uint64_t cap = alloc_grown(grown(ntiles, old, (1ull << 31) - 1), ntiles, [&](uint64_t n) {
+        return dev_alloc(&c->d_ec, sizeof(double) * 32 * n, c->ec_mem);
+      });
+      if (!cap) return fail_hip(c, hipErrorOutOfMemory, "edge columns");
+      c->ec_cap = cap;
     }
     a.ec = c->d_ec;
     if (cold) {
@@ -1619,6 +1669,7 @@ int dymu_destroy(dymu_ctx* c) {
   if (c->d_trace) (void)hipFree(c->d_trace);
   if (c->d_pstat) (void)hipFree(c->d_pstat);
   if (c->d_ec) (void)hipFree(c->d_ec);
+  for (void* p : c->parked) (void)hipFree(p);
   if (c->d_lut) (void)hipFree(c->d_lut);
   if (c->d_scratch) (void)hipFree(c->d_scratch);
   if (c->d_theta) (void)hipFree(c->d_theta);
@@ -2445,6 +2496,86 @@ int dymu_dom_min_key(dymu_ctx* c, void* stream, double* key) {
                          hipMemcpyDeviceToHost, st));
   HIPC(c, hipStreamSynchronize(st));
   std::memcpy(key, &c->h_probe[0], sizeof *key);
+  return DYMU_OK;
+}
+
+int dymu_dom_snapshot(dymu_ctx* c, void* stream, dymu_dom_state* s) {
+  if (!c || !s) return DYMU_ERR_ARG;
+  auto& D = c->dom;
+  if (!D.live) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  HIPC(c, hipStreamSynchronize(st));
+  const uint32_t nt = D.ntiles;
+  const bool keys = is_prio(D.variant);
+  s->eb = D.eb;
+  s->ntiles = nt;
+  s->tiles_cap = c->tiles_cap;
+  s->variant = D.variant;
+  s->p = D.p;
+  s->F = D.a.F;
+  s->T = D.a.T;
+  s->ld = (uint64_t)D.a.ld;
+  s->nx = (uint32_t)D.a.nx;
+  s->ny = (uint32_t)D.a.ny;
+  s->has_keys = keys ? 1 : 0;
+  s->has_ec = D.a.ec ? 1 : 0;
+  if ((s->tile_epoch && s->tile_epoch_cap < c->tiles_cap) ||
+      (s->keys && keys && s->keys_cap < 3ull * nt) || (s->ec && D.a.ec && s->ec_cap < 32ull * nt))
+    return DYMU_ERR_ARG;
+  auto d2h = [&](void* dst, const void* src, size_t bytes) {
+    return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+  };
+  uint32_t cnt[3 * kShards];
+  HIPC(c, d2h(cnt, c->d_counts, sizeof cnt));
+  if (s->counts) std::memcpy(s->counts, cnt, sizeof cnt);
+  const uint32_t* cin = cnt + (D.p % 3) * kShards;
+  s->list_n = 0;
+  for (int q = 0; q < kShards; ++q) {
+    if (cin[q] > nt) {
+      c->last_error = "snapshot: a shard counter exceeds the shard's capacity";
+      return DYMU_ERR_STATE;
+    }
+    s->list_n += cin[q];
+  }
+  if (s->list_raw || s->list_tile) {
+    if (s->list_cap < s->list_n) return DYMU_ERR_ARG;
+    std::vector<uint32_t> tmp;
+    uint32_t* raw = s->list_raw;
+    if (!raw) {
+      tmp.resize((size_t)s->list_n);
+      raw = tmp.data();
+    }
+    uint64_t at = 0;
+    for (int q = 0; q < kShards; ++q) {
+      HIPC(c, d2h(raw + at, D.lists[D.p % 3] + (uint64_t)q * nt, sizeof(uint32_t) * cin[q]));
+      at += cin[q];
+    }
+    if (s->list_tile)
+      for (uint64_t k = 0; k < s->list_n; ++k) s->list_tile[k] = raw[k] & kTileMask;
+  }
+  if (s->tile_epoch)
+    HIPC(c, d2h(s->tile_epoch, c->d_tile_epoch, sizeof(uint32_t) * (size_t)c->tiles_cap));
+  std::memset(s->minkey, 0, sizeof s->minkey);
+  std::memset(s->base, 0, sizeof s->base);
+  s->delta = 0.0;
+  if (keys) {
+    unsigned long long pr[8];
+    HIPC(c, d2h(pr, c->d_prio, sizeof pr));
+    std::memcpy(s->minkey, pr, sizeof s->minkey);
+    std::memcpy(s->base, pr + 3, sizeof s->base);
+    std::memcpy(&s->delta, pr + 6, sizeof s->delta);
+    if (s->keys) HIPC(c, d2h(s->keys, c->d_keys, sizeof(unsigned long long) * 3 * (size_t)nt));
+    if (s->hist) HIPC(c, d2h(s->hist, c->d_hist, sizeof(uint32_t) * 3 * kShards * kBins));
+  }
+  if (s->ec && D.a.ec) HIPC(c, d2h(s->ec, D.a.ec, sizeof(double) * 32 * (size_t)nt));
+  return DYMU_OK;
+}
+
+int dymu_debug_raise_epoch_base(dymu_ctx* c, uint32_t value) {
+  if (!c) return DYMU_ERR_ARG;
+  if (c->dom.live) return DYMU_ERR_STATE;
+  c->epoch_base = std::max(c->epoch_base, value);
   return DYMU_OK;
 }
 

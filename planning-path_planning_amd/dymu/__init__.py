@@ -119,6 +119,19 @@ class DymuStats(ctypes.Structure):
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 _u32, _u64, _i32, _vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p
 
+
+class DymuDomState(ctypes.Structure):
+    """dymu_dom_state (include/dymu_fim.h): scalars out, host buffers in."""
+    _fields_ = [
+        ("eb", _u32), ("ntiles", _u32), ("tiles_cap", _u32), ("variant", ctypes.c_int32),
+        ("p", _u64), ("F", _vp), ("T", _vp), ("ld", _u64), ("nx", _u32), ("ny", _u32),
+        ("has_keys", ctypes.c_int32), ("has_ec", ctypes.c_int32), ("list_n", _u64),
+        ("minkey", _u64 * 3), ("base", ctypes.c_double * 3), ("delta", ctypes.c_double),
+        ("tile_epoch", _vp), ("tile_epoch_cap", _u64), ("counts", _vp), ("list_raw", _vp),
+        ("list_tile", _vp), ("list_cap", _u64), ("keys", _vp), ("keys_cap", _u64),
+        ("hist", _vp), ("ec", _vp), ("ec_cap", _u64),
+    ]
+
 # name -> (restype, argtypes)
 # dymu_seed (include/dymu_fim.h): a source cell and its start value
 SEED_DTYPE = np.dtype([("i", np.uint32), ("j", np.uint32), ("t0", np.float64)], align=True)
@@ -174,6 +187,8 @@ FIM_SYMBOLS = {
                                   _vp]),
     "dymu_set_stepping": (_i32, [_vp, _i32]),
     "dymu_dom_min_key": (_i32, [_vp, _vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_dom_snapshot": (_i32, [_vp, _vp, _vp]),
+    "dymu_debug_raise_epoch_base": (_i32, [_vp, _u32]),
     "dymu_dom_finish": (_i32, [_vp, _vp, ctypes.POINTER(DymuStats)]),
     "dymu_last_pass_timing": (_i32, [_vp, ctypes.POINTER(ctypes.c_double),
                                      ctypes.POINTER(ctypes.c_uint64)]),
@@ -757,6 +772,49 @@ class Engine:
         k = ctypes.c_double()
         _check(self._lib.dymu_dom_min_key(self.ctx, stream or None, ctypes.byref(k)), self.ctx)
         return k.value
+
+    def dom_snapshot(self, stream: int = 0) -> dict:
+        """dymu_dom_snapshot: what the live domain starts from and carries between passes,
+        as numpy arrays and plain numbers (read-only; tests and diagnostics).  eb, p, ntiles,
+        tiles_cap, variant, F, T (device addresses), ld, nx, ny; tile_epoch [tiles_cap];
+        counts [3, 16]; list_raw / list_tile: the entries of the list the next pass reads,
+        as stored and with the key-bin field masked off.  Priority kernels: keys [3, ntiles]
+        (float64), hist [3, 16, 64], minkey [3] (float64), base [3], delta; the others
+        None.  ec [ntiles, 2, 16] for kernel 5 with edge columns, else None."""
+        s = DymuDomState()
+        _check(self._lib.dymu_dom_snapshot(self.ctx, stream or None, ctypes.addressof(s)),
+               self.ctx)
+        nt, keyed, ec = s.ntiles, bool(s.has_keys), bool(s.has_ec)
+        out = {
+            "tile_epoch": np.zeros(s.tiles_cap, dtype=np.uint32),
+            "counts": np.zeros((3, 16), dtype=np.uint32),
+            "list_raw": np.zeros(16 * nt, dtype=np.uint32),
+            "list_tile": np.zeros(16 * nt, dtype=np.uint32),
+            "keys": np.zeros((3, nt), dtype=np.uint64) if keyed else None,
+            "hist": np.zeros((3, 16, 64), dtype=np.uint32) if keyed else None,
+            "ec": np.zeros((nt, 2, 16)) if ec else None,
+        }
+        for name in out:
+            if out[name] is not None:
+                setattr(s, name, out[name].ctypes.data)
+        s.tile_epoch_cap, s.list_cap, s.keys_cap, s.ec_cap = s.tiles_cap, 16 * nt, 3 * nt, 32 * nt
+        _check(self._lib.dymu_dom_snapshot(self.ctx, stream or None, ctypes.addressof(s)),
+               self.ctx)
+        out["list_raw"] = out["list_raw"][:s.list_n].copy()
+        out["list_tile"] = out["list_tile"][:s.list_n].copy()
+        if keyed:
+            out["keys"] = out["keys"].view(np.float64)
+        out.update(eb=s.eb, p=s.p, ntiles=nt, tiles_cap=s.tiles_cap, variant=s.variant,
+                   F=s.F or 0, T=s.T or 0, ld=s.ld, nx=s.nx, ny=s.ny,
+                   minkey=np.array(s.minkey, dtype=np.uint64).view(np.float64) if keyed else None,
+                   base=np.array(s.base, dtype=np.float64) if keyed else None,
+                   delta=s.delta if keyed else None)
+        return out
+
+    def raise_epoch_base(self, value: int):
+        """dymu_debug_raise_epoch_base: the next domain's epoch base is at least `value`
+        (no domain may be live): brings the 32-bit epochs' wrap guard within reach."""
+        _check(self._lib.dymu_debug_raise_epoch_base(self.ctx, int(value)), self.ctx)
 
     def dom_finish(self, stream: int = 0) -> dict:
         st = DymuStats()
