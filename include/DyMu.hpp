@@ -407,7 +407,29 @@ class DyMuPathPlanner {
                                                       std::vector<int>* status = nullptr,
                                                       unsigned max_wp = 1u << 20,
                                                       unsigned stride = 1);
-  // whether the last getPaths ran on the device, and its kernel time (HIP events, ms)
+  // Per-path summaries: for each start the record of the path getPaths
+  // (stride 1) returns -- status, sink, waypoint count, length, last hop, and per sampled
+  // field the integral along the path, minimum, maximum and skipped samples, exactly as
+  // include/dymu_fim.h defines dymu_path_stat on the grid-local waypoints -- without the
+  // waypoints ever being stored or moved.  Field slot 0 is the speed map the solve used
+  // (risk inflation included; an obstacle's +inf counts as skipped), slot 1 the caller's
+  // optional row-major nx*ny `field` (hazard, clearance, elevation ...).  The route is
+  // getPaths': on the device (dymu_path_stats_device) while the device map is current,
+  // else -- or with host = true -- the same accumulation inside the host descent on the
+  // host threads; the records are bit-identical.  last_hop <= (2 + tau) * global_res
+  // tells a descent that arrived from one the reference's NaN rule cut short.
+  // Throws std::invalid_argument for max_wp = 0.
+  typedef dymu_path_stat PathStats;
+  std::vector<PathStats> getPathStats(const std::vector<base::Waypoint>& starts,
+                                      unsigned max_wp = 1u << 20, const double* field = nullptr,
+                                      bool host = false);
+  // ... on map b of the batch with goal b as the sink (always on the device; slot 0 is
+  // the speed the batch was solved with).  Throws std::invalid_argument for b >= batchCount().
+  std::vector<PathStats> getPathStatsTo(unsigned b, const std::vector<base::Waypoint>& starts,
+                                        unsigned max_wp = 1u << 20,
+                                        const double* field = nullptr);
+  // whether the last getPaths / getPathStats ran on the device, and its kernel time (HIP
+  // events, ms)
   bool lastPathsOnDevice() const { return last_paths_device_; }
   double lastPathsKernelMs() const { return last_paths_kernel_ms_; }
   // local-layer inspection: how many global nodes are subdivided (mask: ny*nx
@@ -529,8 +551,11 @@ class DyMuPathPlanner {
   // computeNextGlobalWaypoint / computeGlobalPath without member writes (getPaths'
   // host threads share them): descend returns getPaths' status
   base::Waypoint nextWaypoint(base::Waypoint& wPos, double tau) const;
+  // With acc (getPathStats) every waypoint that would be kept joins the record instead
+  // of `path`, which stays empty.
+  struct PathAccum;
   int descend(base::Waypoint wPos, std::vector<base::Waypoint>& path, uint64_t max_wp,
-              unsigned stride, int* sink = nullptr) const;
+              unsigned stride, int* sink = nullptr, PathAccum* acc = nullptr) const;
   // target: another device map of this grid and its sink (getPathsTo) in place of dT_
   // and the goal / goal set
   struct PathTarget {
@@ -542,6 +567,11 @@ class DyMuPathPlanner {
                      std::vector<std::vector<base::Waypoint>>& out, std::vector<int>& st,
                      std::vector<int>& sinks, unsigned max_wp, unsigned stride,
                      const PathTarget* target = nullptr);
+  void pathStatsOnDevice(const std::vector<base::Waypoint>& starts, std::vector<PathStats>& out,
+                         unsigned max_wp, const double* field, const PathTarget* target);
+  // getPathStats' copy of the caller's field on the device: dcells_ doubles, allocated on
+  // first use and kept until the map buffers go (dropLabels), never re-allocated per call
+  double* d_pfield_ = nullptr;
   // the batch (computeTotalCostMaps): its goals and the solved stack, plane b at
   // dT_batch_ + b * dymu_batch_plane_rows(ny_) * nx_ (pitch nx_)
   struct BatchGoal {

@@ -232,6 +232,51 @@ int dymu_extract_paths_goals_device(dymu_ctx* ctx, const double* dT, uint32_t nx
                                     const double* d_start_xy, uint32_t n_paths, uint32_t max_wp,
                                     uint32_t stride, double* d_out, int32_t* d_count,
                                     int32_t* d_status, void* stream, int32_t* d_sink);
+/* ---- per-path summaries (DyMuPathPlanner::getPathStats) ----
+ * The record of one path.  Let w_0 .. w_{n-1} be the waypoints dymu_extract_paths_device
+ * (stride 1) writes for the start, in grid-local metres, seg_k = dist(w_k, w_{k+1}) =
+ * sqrt(dx*dx + dy*dy), and for a sampled field f let v_k = f at w_k's nearest node
+ * (i, j) = (uint)(x / res + 0.5), (uint)(y / res + 0.5), a sample that counts when the
+ * node is on the grid (tested before the load) and v_k is finite.  Sums run in the order
+ * k = 0, 1, ... from 0.0, so host and device agree bit for bit.
+ *   status, sink  as dymu_extract_paths[_goals]_device (sink: 0 with a single sink, -1
+ *                 where status != 1); -3: the record covers the first max_wp waypoints
+ *   count         n (0 with status -1, and the record is then the empty one)
+ *   length        seg_0 + seg_1 + ...
+ *   last_hop      seg_{n-2} (0 for n < 2): at most (2 + tau) * res where the descent
+ *                 arrived, longer where it was cut short and jumped to the sink
+ *   integral[f]   the sum over k <= n-2 of v_k * seg_k, counting samples only
+ *   vmin[f], vmax[f]  over the counting samples, from +inf / -inf
+ *   skipped[f]    waypoints whose sample does not count
+ * A field slot that is not used keeps 0 / +inf / -inf / 0. */
+#define DYMU_PATH_FIELDS 4
+typedef struct dymu_path_stat {
+  int32_t status, sink;
+  uint32_t count, reserved;
+  double length, last_hop;
+  double integral[DYMU_PATH_FIELDS], vmin[DYMU_PATH_FIELDS], vmax[DYMU_PATH_FIELDS];
+  uint32_t skipped[DYMU_PATH_FIELDS];
+} dymu_path_stat;
+/* The descent of dymu_extract_paths_device (d_label NULL: the sink is (goal_i, goal_j))
+ * or of dymu_extract_paths_goals_device (d_label, d_goal_xy, n_goals as there; goal_i,
+ * goal_j ignored) for n_paths starts, storing no waypoint: d_stats[p] (device) = the
+ * record of path p over the fields d_fields[f] (HOST array of n_fields <= DYMU_PATH_FIELDS
+ * device maps of nx x ny doubles, pitch field_ld[f] >= nx, HOST array).  A batch plane is
+ * an ordinary map pointer.  The kernel runs n_lanes lanes (rounded up to whole waves, at
+ * most one per path; 0: the default, one lane per path); a lane that finishes a path
+ * takes the next one from a device counter, so any n_lanes gives the same records.  One call at a time per context (the counter and the timer are the context's).
+ * Asynchronous on `stream`.  DYMU_ERR_ARG: max_wp = 0, n_fields > DYMU_PATH_FIELDS, a
+ * NULL field or a pitch below nx, and what dymu_extract_paths[_goals]_device reject. */
+int dymu_path_stats_device(dymu_ctx* ctx, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
+                           double res, uint32_t goal_i, uint32_t goal_j, const uint32_t* d_label,
+                           const double* d_goal_xy, uint32_t n_goals, double tau,
+                           const double* d_start_xy, uint32_t n_paths, uint32_t max_wp,
+                           const double* const* d_fields, const uint64_t* field_ld,
+                           uint32_t n_fields, uint32_t n_lanes, dymu_path_stat* d_stats,
+                           void* stream);
+/* Device time (ms, HIP events) of the last dymu_path_stats_device kernel; waits for it.
+ * DYMU_ERR_STATE before the first one. */
+int dymu_last_path_stats_ms(dymu_ctx* ctx, double* ms);
 /* Device time (ms, HIP events) of the last dymu_goal_labels_device, first kernel to last.
  * DYMU_ERR_STATE before the first one. */
 int dymu_last_labels_ms(dymu_ctx* ctx, double* ms);

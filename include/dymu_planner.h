@@ -127,6 +127,18 @@ int dymu_planner_batch_level(dymu_planner* p, double* level);
  * two-call protocol, same status values.  DYMU_ERR_ARG for b >= batch_count. */
 int dymu_planner_get_paths_to(dymu_planner* p, uint32_t b, const double* starts_xyzh, int n,
                               int max_wp, int stride, double* out_xyzh, int* counts, int* status);
+/* getPathStats (extension, DyMu.hpp): out[q] = the dymu_path_stat record
+ * (include/dymu_fim.h) of the path dymu_planner_get_paths would return for start q, with
+ * no waypoint stored or moved.  Field slot 0 is the speed map the solve used, slot 1 the
+ * optional row-major ny x nx `field` (NULL: none).  The route is get_paths' unless host is
+ * non-zero, which runs the host descent; dymu_planner_last_paths_on_device / _kernel_ms
+ * report the call.  Returns n or a negative status (DYMU_ERR_ARG for max_wp <= 0). */
+int dymu_planner_get_path_stats(dymu_planner* p, const double* starts_xyzh, int n, int max_wp,
+                                const double* field, int host, dymu_path_stat* out);
+/* ... on map b of the batch with goal b as the sink (always on the device).
+ * DYMU_ERR_ARG for b >= batch_count. */
+int dymu_planner_get_path_stats_to(dymu_planner* p, uint32_t b, const double* starts_xyzh, int n,
+                                   int max_wp, const double* field, dymu_path_stat* out);
 /* goalI() / goalJ(): the single goal's cell (goal 0 of a goal set); 1 = written, 0 = no
  * goal set yet */
 int dymu_planner_goal_cell(dymu_planner* p, uint32_t* i, uint32_t* j);

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cmath>
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,6 +31,9 @@ struct dymu_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_path0 = nullptr, ev_path1 = nullptr;  // around the last k_extract_paths
   bool path_timed = false;
+  hipEvent_t ev_pstat0 = nullptr, ev_pstat1 = nullptr;  // around the last k_path_stats
+  bool pstat_timed = false;
+  uint32_t* d_pq = nullptr;  // k_path_stats' work queue: the next path index
   hipEvent_t ev_lab0 = nullptr, ev_lab1 = nullptr;  // around the last dymu_goal_labels_device
   bool lab_timed = false;
   uint32_t* d_lab_cnt = nullptr;  // kLabelRounds + 1 counters of unresolved label entries
@@ -1657,6 +1661,9 @@ int dymu_destroy(dymu_ctx* c) {
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev_path0) (void)hipEventDestroy(c->ev_path0);
   if (c->ev_path1) (void)hipEventDestroy(c->ev_path1);
+  if (c->ev_pstat0) (void)hipEventDestroy(c->ev_pstat0);
+  if (c->ev_pstat1) (void)hipEventDestroy(c->ev_pstat1);
+  if (c->d_pq) (void)hipFree(c->d_pq);
   if (c->ev_lab0) (void)hipEventDestroy(c->ev_lab0);
   if (c->ev_lab1) (void)hipEventDestroy(c->ev_lab1);
   if (c->d_lab_cnt) (void)hipFree(c->d_lab_cnt);
@@ -1915,6 +1922,87 @@ int dymu_extract_paths_goals_device(dymu_ctx* c, const double* dT, uint32_t nx, 
   if ((uint64_t)nx * ny >= (1ull << 31) || (n_paths && !d_sink)) return DYMU_ERR_ARG;
   return extract_paths(c, dT, nx, ny, ld, res, 0, 0, d_label, d_goal_xy, n_goals, tau, d_start_xy,
                        n_paths, max_wp, stride, d_out, d_count, d_status, d_sink, stream);
+}
+
+static_assert(sizeof(dymu_path_stat) == sizeof(PathStatRec) && DYMU_PATH_FIELDS == kPathFields &&
+                  offsetof(dymu_path_stat, skipped) == offsetof(PathStatRec, skipped),
+              "PathStatRec is dymu_path_stat's layout");
+
+int dymu_path_stats_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
+                           double res, uint32_t gi, uint32_t gj, const uint32_t* d_label,
+                           const double* d_goal_xy, uint32_t n_goals, double tau,
+                           const double* d_start_xy, uint32_t n_paths, uint32_t max_wp,
+                           const double* const* d_fields, const uint64_t* field_ld,
+                           uint32_t n_fields, uint32_t n_lanes, dymu_path_stat* d_stats,
+                           void* stream) {
+  if (!c || !dT || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
+  if (!(res > 0) || !(res < HUGE_VAL) || !(tau > 0) || !(tau < HUGE_VAL)) return DYMU_ERR_ARG;
+  if (max_wp == 0 || max_wp > 0x7fffffffu || n_paths > 0x7fffffffu) return DYMU_ERR_ARG;
+  if (d_label) {
+    if (!d_goal_xy || n_goals == 0 || n_goals >= (1u << 31)) return DYMU_ERR_ARG;
+    if ((uint64_t)nx * ny >= (1ull << 31)) return DYMU_ERR_ARG;
+    gi = gj = 0;
+  } else if (gi >= nx || gj >= ny) {
+    return DYMU_ERR_ARG;
+  }
+  if (n_fields > DYMU_PATH_FIELDS || (n_fields && (!d_fields || !field_ld))) return DYMU_ERR_ARG;
+  for (uint32_t f = 0; f < n_fields; ++f)
+    if (!d_fields[f] || field_ld[f] < nx) return DYMU_ERR_ARG;
+  if (n_paths && (!d_start_xy || !d_stats)) return DYMU_ERR_ARG;
+  if (n_paths == 0) return DYMU_OK;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  if (!c->ev_pstat0) HIPC(c, hipEventCreate(&c->ev_pstat0));
+  if (!c->ev_pstat1) HIPC(c, hipEventCreate(&c->ev_pstat1));
+  if (!c->d_pq) HIPC(c, hipMalloc(&c->d_pq, 256));
+  PathStatArgs a{};
+  a.T = dT;
+  a.ld = (int64_t)ld;
+  a.nx = nx;
+  a.ny = ny;
+  a.res = res;
+  // the host's expressions, as dymu_extract_paths_device forms them
+  a.res_tau = res * tau;
+  a.two_res = 2.0 * res;
+  a.stall = 0.01 * tau * res;
+  a.sink_x = res * (double)gi;
+  a.sink_y = res * (double)gj;
+  a.start_xy = d_start_xy;
+  a.n_paths = n_paths;
+  a.max_wp = max_wp;
+  a.label = d_label;
+  a.goal_xy = d_goal_xy;
+  a.n_goals = n_goals;
+  for (uint32_t f = 0; f < n_fields; ++f) {
+    a.field[f] = d_fields[f];
+    a.field_ld[f] = (int64_t)field_ld[f];
+  }
+  a.next = c->d_pq;
+  a.out = reinterpret_cast<PathStatRec*>(d_stats);
+  // The default is one lane per path: lanes that refill from the queue were slower than
+  // that where measured.  More lanes than paths would only fetch and
+  // leave; the fetches add at most n_paths + lanes < 2^32 to the counter.
+  const uint32_t whole = (n_paths + 63u) / 64u * 64u;
+  uint32_t lanes = n_lanes ? (n_lanes + 63u) / 64u * 64u : whole;
+  if (n_lanes > 0xffffffc0u || lanes > whole) lanes = whole;
+  c->pstat_timed = false;
+  HIPC(c, hipMemsetAsync(c->d_pq, 0, sizeof(uint32_t), st));
+  HIPC(c, hipEventRecord(c->ev_pstat0, st));
+  HIPC(c, launch_path_stats(a, n_fields, lanes, st));
+  HIPC(c, hipEventRecord(c->ev_pstat1, st));
+  c->pstat_timed = true;
+  return DYMU_OK;
+}
+
+int dymu_last_path_stats_ms(dymu_ctx* c, double* ms) {
+  if (!c || !ms) return DYMU_ERR_ARG;
+  if (!c->pstat_timed) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipEventSynchronize(c->ev_pstat1));
+  float f = 0.0f;
+  HIPC(c, hipEventElapsedTime(&f, c->ev_pstat0, c->ev_pstat1));
+  *ms = (double)f;
+  return DYMU_OK;
 }
 
 int dymu_solve_seeds_device(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t ny,

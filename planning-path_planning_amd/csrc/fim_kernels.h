@@ -400,6 +400,36 @@ hipError_t launch_extract_paths(const PathArgs& a, hipStream_t st);
 // the same descent with a per-path sink: the goal labelled on the cell the path is in
 hipError_t launch_extract_paths_goals(const PathArgs& a, hipStream_t st);
 
+// per-path summaries (path_stats_kernels.hip): the same descent, no
+// waypoint stored, one record per path.  PathStatRec is dymu_path_stat's layout.
+constexpr int kPathFields = 4;
+struct PathStatRec {
+  int32_t status, sink;
+  uint32_t count, reserved;
+  double length, last_hop;
+  double integral[kPathFields], vmin[kPathFields], vmax[kPathFields];
+  uint32_t skipped[kPathFields];
+};
+struct PathStatArgs {
+  const double* T;  // total cost, pitch ld
+  int64_t ld;
+  uint32_t nx, ny;
+  double res, res_tau, two_res, stall;  // as PathArgs
+  double sink_x, sink_y;
+  const double* start_xy;  // n_paths x 2
+  uint32_t n_paths, max_wp;
+  const uint32_t* label;  // null: the single sink (sink_x, sink_y); else as PathArgs
+  const double* goal_xy;
+  uint32_t n_goals;
+  const double* field[kPathFields];  // the sampled fields, pitch field_ld
+  int64_t field_ld[kPathFields];
+  uint32_t* next;    // the work queue: the next path index to hand out (zero at launch)
+  PathStatRec* out;  // n_paths records
+};
+// n_fields <= kPathFields fields; lanes: a multiple of 64, the size of the grid
+hipError_t launch_path_stats(const PathStatArgs& a, uint32_t n_fields, uint32_t lanes,
+                             hipStream_t st);
+
 // goal sets (goal_kernels.hip)
 struct GoalSeed {  // dymu_seed's layout
   uint32_t i, j;

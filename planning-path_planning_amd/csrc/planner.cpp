@@ -1792,6 +1792,62 @@ double bilinear(double a, double b, double g00, double g01, double g10, double g
 }
 }  // namespace
 
+// The record of one path while the host descent builds it (include/dymu_fim.h,
+// dymu_path_stat): k_path_stats (path_stats_kernels.hip) forms the same sums in the same
+// order.  Field f at node k is speed (slot 0: the packed speed the solve used, or the
+// node fields' speed where none was packed yet) or the caller's array (slot 1).
+struct DyMuPathPlanner::PathAccum {
+  dymu_path_stat r;
+  unsigned nf = 0;
+  const double* f[DYMU_PATH_FIELDS] = {nullptr, nullptr, nullptr, nullptr};
+  double px = 0, py = 0;
+  double pv[DYMU_PATH_FIELDS] = {0, 0, 0, 0};  // the previous waypoint's samples ...
+  unsigned ok = 0;                             // ... and which of them count
+  static dymu_path_stat empty() {
+    dymu_path_stat e{};
+    e.status = -1;
+    e.sink = -1;
+    for (int q = 0; q < DYMU_PATH_FIELDS; ++q) {
+      e.vmin[q] = kInf;
+      e.vmax[q] = -kInf;
+    }
+    return e;
+  }
+  PathAccum() : r(empty()) {}
+  void add(const DyMuPathPlanner& pl, double x, double y) {
+    if (r.count > 0) {
+      const double dx = px - x, dy = py - y;
+      const double seg = std::sqrt(dx * dx + dy * dy);
+      r.length = r.length + seg;
+      r.last_hop = seg;
+      for (unsigned q = 0; q < nf; ++q)
+        if (ok >> q & 1u) r.integral[q] = r.integral[q] + pv[q] * seg;
+    }
+    // nearestIndex's rule; nothing is read before the node is known to be on the grid
+    const uint32_t i = grid_u32(x / pl.global_res_ + 0.5), j = grid_u32(y / pl.global_res_ + 0.5);
+    const bool in = i < pl.nx_ && j < pl.ny_;
+    ok = 0;
+    for (unsigned q = 0; q < nf; ++q) {
+      double v = 0;
+      if (in) {
+        const uint64_t k = pl.idx(i, j);
+        v = f[q] ? f[q][k] : pl.is_obstacle_[k] ? kInf : pl.nodeSpeed(k);
+      }
+      if (in && v < kInf && v > -kInf) {
+        r.vmin[q] = v < r.vmin[q] ? v : r.vmin[q];
+        r.vmax[q] = v > r.vmax[q] ? v : r.vmax[q];
+        pv[q] = v;
+        ok |= 1u << q;
+      } else {
+        ++r.skipped[q];
+      }
+    }
+    px = x;
+    py = y;
+    ++r.count;
+  }
+};
+
 // The loop of computeGlobalPath into `path`, without member writes.  Returns getPaths'
 // status: 1 sink appended, 0 "ERROR in trajectory" (the waypoints so far kept), -1 the
 // first step is NaN (empty path), -3 more than max_wp waypoints (the first max_wp
@@ -1802,8 +1858,10 @@ double bilinear(double a, double b, double g00, double g01, double g10, double g
 // last one looked up, the sink becomes the goal labelled on that cell's node (no label:
 // the previous sink stays; none yet at the first step: -1).  *sink_out = the goal whose
 // sink was appended, -1 otherwise.
+// With acc the kept waypoints join its record (grid-local x, y) and `path` stays empty.
 int DyMuPathPlanner::descend(base::Waypoint wPos, std::vector<base::Waypoint>& path,
-                             uint64_t max_wp, unsigned stride, int* sink_out) const {
+                             uint64_t max_wp, unsigned stride, int* sink_out,
+                             PathAccum* acc) const {
   path.clear();
   if (sink_out) *sink_out = -1;
   if (!has_goal_) return -1;
@@ -1841,8 +1899,12 @@ int DyMuPathPlanner::descend(base::Waypoint wPos, std::vector<base::Waypoint>& p
   if (std::isnan(wNext.position[0]) || std::isnan(wNext.position[1])) return -1;
   if (sink_k < 0) return -1;
   unsigned phase = 0;
+  auto keep = [&](const base::Waypoint& w) {
+    if (acc) acc->add(*this, w.position[0], w.position[1]);
+    else path.push_back(w);
+  };
   auto push = [&](const base::Waypoint& w) {
-    if (phase == 0) path.push_back(w);
+    if (phase == 0) keep(w);
     if (++phase == stride) phase = 0;
   };
   push(wPos);
@@ -1859,8 +1921,8 @@ int DyMuPathPlanner::descend(base::Waypoint wPos, std::vector<base::Waypoint>& p
     if (dist(wPos, wNext) < 0.01 * tau * global_res_) return 0;
     wPos = wNext;
   }
-  if (path.size() >= max_wp) return -3;
-  path.push_back(sink);
+  if ((acc ? (uint64_t)acc->r.count : (uint64_t)path.size()) >= max_wp) return -3;
+  keep(sink);
   if (sink_out) *sink_out = sink_k;
   return 1;
 }
@@ -2182,6 +2244,108 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
   }
 }
 
+// ---- getPathStats: per-path summaries (extension) ----
+#pragma weak dymu_path_stats_device
+#pragma weak dymu_last_path_stats_ms
+
+std::vector<DyMuPathPlanner::PathStats> DyMuPathPlanner::getPathStats(
+    const std::vector<base::Waypoint>& starts, unsigned max_wp, const double* field, bool host) {
+  if (max_wp == 0) throw std::invalid_argument("getPathStats: max_wp >= 1");
+  const size_t n = starts.size();
+  std::vector<PathStats> out(n, PathAccum::empty());
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  if (!n || !has_goal_) return out;
+  if (!host && ctx_ && dT_ && dF_ && dev_map_current_ && speed_valid_ && n <= 0x7fffffffull &&
+      max_wp <= 0x7fffffffu && &dymu_path_stats_device && &dymu_last_path_stats_ms &&
+      (goals_.empty() || goalsOnDevice())) {
+    pathStatsOnDevice(starts, out, max_wp, field, nullptr);
+    last_paths_device_ = true;
+    return out;
+  }
+  if (!goals_.empty()) ensureHostLabels();
+  if (!speed_valid_ && globalRiskOn() && risk_stale_) refreshGlobalRisk();
+  const double* f0 = speed_valid_ ? speed_.data() : nullptr;
+  const unsigned nt = (unsigned)std::min<size_t>(host_threads(), n);
+  std::atomic<size_t> next{0};
+  parallel_tasks(nt, [&](unsigned) {
+    std::vector<base::Waypoint> none;
+    for (size_t q = next++; q < n; q = next++) {
+      base::Waypoint w = starts[q];
+      w.position[0] -= global_offset_[0];
+      w.position[1] -= global_offset_[1];
+      PathAccum acc;
+      acc.nf = field ? 2u : 1u;
+      acc.f[0] = f0;
+      acc.f[1] = field;
+      int sink = -1;
+      const int st = descend(w, none, max_wp, 1, &sink, &acc);
+      if (st == -1) continue;  // the empty record
+      acc.r.status = st;
+      acc.r.sink = st == 1 ? sink : -1;
+      out[q] = acc.r;
+    }
+  });
+  return out;
+}
+
+// The device route: the starts up, one k_path_stats launch, the records down.  The
+// caller's field goes through d_pfield_, a buffer of the map's size that is allocated
+// once and lives as long as the map buffers.
+void DyMuPathPlanner::pathStatsOnDevice(const std::vector<base::Waypoint>& starts,
+                                        std::vector<PathStats>& out, unsigned max_wp,
+                                        const double* field, const PathTarget* target) {
+  const size_t n = starts.size();
+  const double tau = std::min(0.4, risk_distance_);
+  auto check = [&](int rc, const char* what) {
+    if (rc != DYMU_OK)
+      throw std::runtime_error(std::string("dymu: getPathStats ") + what + " failed: " +
+                               dymu_strerror(rc) + " " + dymu_last_error(ctx_));
+  };
+  const double* map = target ? target->map : dT_;
+  const unsigned gi = target ? target->gi : goal_i_, gj = target ? target->gj : goal_j_;
+  const bool gs = !target && !goals_.empty();
+  DeviceScratch dev(ctx_);
+  double* d_gxy = nullptr;
+  if (gs) {
+    ensureDeviceLabels();
+    std::vector<double> gxy(2 * goals_.size());
+    for (size_t k = 0; k < goals_.size(); ++k) {
+      const base::Waypoint w = sinkWaypoint(k);
+      gxy[2 * k] = w.position[0];
+      gxy[2 * k + 1] = w.position[1];
+    }
+    d_gxy = dev.alloc<double>(gxy.size());
+    check(dymu_memcpy_h2d(ctx_, d_gxy, gxy.data(), sizeof(double) * gxy.size()), "upload");
+  }
+  if (field) {
+    if (!d_pfield_) {
+      void* p = nullptr;
+      check(dymu_device_alloc(ctx_, sizeof(double) * dcells_, &p), "field allocation");
+      d_pfield_ = static_cast<double*>(p);
+    }
+    check(dymu_memcpy_h2d(ctx_, d_pfield_, field, sizeof(double) * dcells_), "field upload");
+  }
+  std::vector<double> xy(2 * n);
+  for (size_t q = 0; q < n; ++q) {
+    xy[2 * q] = starts[q].position[0] - global_offset_[0];
+    xy[2 * q + 1] = starts[q].position[1] - global_offset_[1];
+  }
+  double* d_xy = dev.alloc<double>(2 * (uint64_t)n);
+  PathStats* d_rec = dev.alloc<PathStats>(n);
+  check(dymu_memcpy_h2d(ctx_, d_xy, xy.data(), sizeof(double) * xy.size()), "upload");
+  const double* fields[2] = {dF_, d_pfield_};
+  const uint64_t pitch[2] = {nx_, nx_};
+  check(dymu_path_stats_device(ctx_, map, nx_, ny_, nx_, global_res_, gi, gj,
+                               gs ? d_label_ : nullptr, d_gxy, gs ? (uint32_t)goals_.size() : 0u,
+                               tau, d_xy, (uint32_t)n, max_wp, fields, pitch, field ? 2u : 1u, 0u,
+                               d_rec, nullptr),
+        "kernel");
+  check(dymu_memcpy_d2h(ctx_, out.data(), d_rec, sizeof(PathStats) * n), "download");
+  double ms = 0.0;
+  if (dymu_last_path_stats_ms(ctx_, &ms) == DYMU_OK) last_paths_kernel_ms_ = ms;
+}
+
 // ---- goal sets (extension) ----
 
 // The goal-set entries of the engine C-ABI: null with an engine that predates them
@@ -2340,6 +2504,9 @@ void DyMuPathPlanner::dropLabels() {
   invalidateLabels();
   if (d_label_ && ctx_) (void)dymu_device_free(ctx_, d_label_);
   d_label_ = nullptr;
+  // getPathStats' field buffer goes where the label map goes: with the map buffers
+  if (d_pfield_ && ctx_) (void)dymu_device_free(ctx_, d_pfield_);
+  d_pfield_ = nullptr;
 }
 
 void DyMuPathPlanner::ensureDeviceLabels() {
@@ -3119,6 +3286,26 @@ std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getPathsTo(
     last_paths_device_ = true;
   }
   if (status) status->swap(st);
+  return out;
+}
+
+std::vector<DyMuPathPlanner::PathStats> DyMuPathPlanner::getPathStatsTo(
+    unsigned b, const std::vector<base::Waypoint>& starts, unsigned max_wp, const double* field) {
+  if (max_wp == 0) throw std::invalid_argument("getPathStatsTo: max_wp >= 1");
+  if (b >= batch_goals_.size() || !ctx_ || !dT_batch_ || starts.size() > 0x7fffffffull ||
+      max_wp > 0x7fffffffu || !&dymu_path_stats_device || !&dymu_last_path_stats_ms ||
+      !refreshBatch())
+    throw std::invalid_argument("getPathStatsTo: no such map in the batch");
+  std::vector<PathStats> out(starts.size(), PathAccum::empty());
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  if (!starts.empty()) {
+    const BatchGoal& g = batch_goals_[b];
+    const PathTarget tgt{dT_batch_ + (uint64_t)b * dymu_batch_plane_rows(ny_) * nx_, g.i, g.j,
+                         g.heading};
+    pathStatsOnDevice(starts, out, max_wp, field, &tgt);
+    last_paths_device_ = true;
+  }
   return out;
 }
 

@@ -532,6 +532,27 @@ int dymu_planner_get_paths_to(dymu_planner* p, uint32_t b, const double* starts,
   return n;
 }
 
+int dymu_planner_get_path_stats(dymu_planner* p, const double* starts, int n, int max_wp,
+                                const double* field, int host, dymu_path_stat* out) {
+  if (!p || n < 0 || max_wp <= 0 || (n > 0 && (!starts || !out))) return DYMU_ERR_ARG;
+  return guarded([&] {
+    const auto v = p->pl.getPathStats(wps(starts, n, 4), (unsigned)max_wp, field, host != 0);
+    std::copy(v.begin(), v.end(), out);
+    return n;
+  });
+}
+
+int dymu_planner_get_path_stats_to(dymu_planner* p, uint32_t b, const double* starts, int n,
+                                   int max_wp, const double* field, dymu_path_stat* out) {
+  if (!p || n < 0 || max_wp <= 0 || (n > 0 && (!starts || !out)) || b >= p->pl.batchCount())
+    return DYMU_ERR_ARG;
+  return guarded([&] {
+    const auto v = p->pl.getPathStatsTo(b, wps(starts, n, 4), (unsigned)max_wp, field);
+    std::copy(v.begin(), v.end(), out);
+    return n;
+  });
+}
+
 int dymu_planner_goal_cell(dymu_planner* p, uint32_t* i, uint32_t* j) {
   if (!p || !i || !j) return DYMU_ERR_ARG;
   if (!p->pl.hasGoal()) return 0;

@@ -147,6 +147,14 @@ BATCH_WINDOW_DTYPE = np.dtype([("plane", np.uint32), ("i0", np.uint32), ("j0", n
 CELL_DTYPE = np.dtype([("i", np.uint32), ("j", np.uint32)], align=True)
 BATCH_CELL_DTYPE = np.dtype([("plane", np.uint32), ("i", np.uint32), ("j", np.uint32),
                              ("reserved", np.uint32)], align=True)
+# dymu_path_stat: the record of one path (include/dymu_fim.h)
+PATH_FIELDS = 4
+PATH_STAT_DTYPE = np.dtype([("status", np.int32), ("sink", np.int32), ("count", np.uint32),
+                            ("reserved", np.uint32), ("length", np.float64),
+                            ("last_hop", np.float64), ("integral", np.float64, (PATH_FIELDS,)),
+                            ("vmin", np.float64, (PATH_FIELDS,)),
+                            ("vmax", np.float64, (PATH_FIELDS,)),
+                            ("skipped", np.uint32, (PATH_FIELDS,))], align=True)
 
 FIM_SYMBOLS = {
     "dymu_create": (_i32, [ctypes.POINTER(_vp), ctypes.POINTER(DymuOpts)]),
@@ -225,6 +233,10 @@ FIM_SYMBOLS = {
                                                _vp, _u32, ctypes.c_double, _vp, _u32, _u32, _u32,
                                                _vp, _vp, _vp, _vp, _vp]),
     "dymu_last_labels_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_path_stats_device": (_i32, [_vp, _vp, _u32, _u32, _u64, ctypes.c_double, _u32, _u32,
+                                      _vp, _vp, _u32, ctypes.c_double, _vp, _u32, _u32, _vp, _vp,
+                                      _u32, _u32, _vp, _vp]),
+    "dymu_last_path_stats_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "dymu_batch_plane_rows": (_u32, [_u32]),
     "dymu_stack_speed_device": (_i32, [_vp, _vp, _u64, _u64, _u32, _u32, _u32, _vp, _u64, _vp]),
     "dymu_solve_batch_device": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _u32, _vp,
@@ -566,6 +578,50 @@ class Engine:
         for q in range(n):  # slots past the count were never written
             out[q, max(cnt[q], 0):] = 0.0
         return out, cnt, st, sink
+
+    # -- per-path summaries --
+    def path_stats(self, dT: int, nx: int, ny: int, ld: int, res: float, goal_i: int,
+                   goal_j: int, tau: float, starts_xy, max_wp: int, fields=(), n_lanes: int = 0,
+                   d_label: int = 0, goals_ij=None, stream: int = 0) -> np.ndarray:
+        """dymu_path_stats_device on the device map dT for host starts (n, 2) in grid-local
+        metres: a PATH_STAT_DTYPE array of n records.  fields: up to PATH_FIELDS pairs
+        (device pointer, pitch) of sampled maps; n_lanes: the lanes of the kernel's grid (0:
+        the default); d_label with goals_ij (n_goals, 2): the sink follows the label map."""
+        xy = np.ascontiguousarray(starts_xy, dtype=np.float64).reshape(-1, 2)
+        n = len(xy)
+        out = np.zeros(n, dtype=PATH_STAT_DTYPE)
+        fp = (_vp * max(len(fields), 1))(*[int(f[0]) for f in fields])
+        fl = (_u64 * max(len(fields), 1))(*[int(f[1]) for f in fields])
+        gxy = None
+        if d_label:
+            gxy = res * np.ascontiguousarray(goals_ij, dtype=np.float64).reshape(-1, 2)
+        ptrs = [self.alloc(max(xy.nbytes, 8)), self.alloc(max(out.nbytes, 8))]
+        if gxy is not None:
+            ptrs.append(self.alloc(max(gxy.nbytes, 8)))
+        try:
+            if n:
+                self.h2d(ptrs[0], xy)
+            if gxy is not None and len(gxy):
+                self.h2d(ptrs[2], gxy)
+            _check(self._lib.dymu_path_stats_device(
+                self.ctx, dT, nx, ny, ld, res, goal_i, goal_j, d_label or None,
+                ptrs[2] if gxy is not None else None, len(gxy) if gxy is not None else 0, tau,
+                ptrs[0], n, max_wp, ctypes.cast(fp, _vp), ctypes.cast(fl, _vp), len(fields),
+                n_lanes, ptrs[1], stream or None), self.ctx)
+            if n:
+                if stream:  # d2h is ordered on the context stream only
+                    self.last_path_stats_ms()
+                self.d2h(out, ptrs[1])
+        finally:
+            for p in ptrs:
+                self.free(p)
+        return out
+
+    def last_path_stats_ms(self) -> float:
+        """Device time of the last path_stats kernel (waits for it)."""
+        ms = ctypes.c_double()
+        _check(self._lib.dymu_last_path_stats_ms(self.ctx, ctypes.byref(ms)), self.ctx)
+        return ms.value
 
     # -- batched solves (DESIGN.md s5.7) --
     def stack_speed(self, src: int, src_ld: int, src_plane_stride: int, nx: int, ny: int,
@@ -970,6 +1026,8 @@ PLANNER_SYMBOLS = {
     "dymu_planner_last_batch_stats": (_i32, [_vp, ctypes.POINTER(DymuStats)]),
     "dymu_planner_track_speed_changes": (_i32, [_vp, _i32]),
     "dymu_planner_last_batch_solve_kind": (_i32, [_vp]),
+    "dymu_planner_get_path_stats": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp]),
+    "dymu_planner_get_path_stats_to": (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp]),
     "dymu_planner_goal_cell": (_i32, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "dymu_planner_get_locomotion_mode": (_i32, [_vp, _d, _d, _d, _d, ctypes.c_char_p, _i32]),
     "dymu_planner_set_global_risk": (_i32, [_vp, _d, _d]),
@@ -1307,6 +1365,34 @@ class Planner:
                                                    None, None))
         ends = np.cumsum(cnt[:n])
         return [buf[e - c:e].copy() for e, c in zip(ends, cnt[:n])], st[:n].copy()
+
+    def _stats_args(self, starts, field):
+        s = np.ascontiguousarray([self._wp(w) for w in starts], dtype=np.float64).reshape(-1, 4)
+        f = None if field is None else self._grid(field)
+        out = np.zeros(len(s), dtype=PATH_STAT_DTYPE)
+        return s, f, out
+
+    def getPathStats(self, starts, max_wp: int = 1 << 20, field=None, host: bool = False):
+        """One record per start instead of its path (DyMuPathPlanner::getPathStats, DESIGN.md
+        s5.13): a PATH_STAT_DTYPE array with getPaths' status / sink / count, the length, the
+        last hop (<= (2 + tau) res where the descent arrived; longer where it was cut short
+        and jumped to the sink), and per field the integral along the path, min, max and
+        skipped samples -- slot 0 the speed map the solve used, slot 1 the optional [ny, nx]
+        `field`.  On the GPU while the device map is current (no waypoint is stored or
+        moved), else -- or with host=True -- on the host threads, bit-identically."""
+        s, f, out = self._stats_args(starts, field)
+        _b_int(self._lib.dymu_planner_get_path_stats(
+            self.h, s.ctypes.data, len(s), max_wp, None if f is None else f.ctypes.data,
+            int(bool(host)), out.ctypes.data))
+        return out
+
+    def getPathStatsTo(self, b: int, starts, max_wp: int = 1 << 20, field=None):
+        """getPathStats on map b of the batch, with goal b as the sink."""
+        s, f, out = self._stats_args(starts, field)
+        _b_int(self._lib.dymu_planner_get_path_stats_to(
+            self.h, b, s.ctypes.data, len(s), max_wp, None if f is None else f.ctypes.data,
+            out.ctypes.data))
+        return out
 
     def goalCell(self):
         """(goalI(), goalJ()): the single goal's cell (goal 0 of a goal set), or None."""
