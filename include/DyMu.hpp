@@ -45,6 +45,7 @@
 #pragma once
 
 #include <cstdint>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <optional>
@@ -273,6 +274,13 @@ class DyMuPathPlanner {
                               const double* hd);
   bool setTrafficabilityWindow(unsigned i0, unsigned j0, unsigned w, unsigned h,
                                const double* tr);
+  // setCostMap for the cells [i0, i0+w) x [j0, j0+h) only: w x h costs, row-major, each
+  // applied by setCostMap's per-cell rule.  false, and nothing changes: a null pointer or
+  // a box not inside the grid (as the windowed setters above).  Only the rows of the box
+  // are re-packed at the next solve, so a converged map follows by the windowed
+  // re-propagation; with setGlobalRisk on, obstacles the box adds reach R through the
+  // incremental update (below), an obstacle it frees through the whole recompute.
+  bool setCostMapWindow(unsigned i0, unsigned j0, unsigned w, unsigned h, const double* cost);
   // Narrow-band cells left by the last computeTotalCostMap (0 after a full solve).
   uint64_t lastBandSize() const { return band_cells_.size(); }
   // How the last computeTotalCostMap resolved the reference's order at its exit
@@ -458,6 +466,15 @@ class DyMuPathPlanner {
   double globalRiskRatio() const { return grisk_ratio_; }
   // R as [j][i] (recomputed first when stale); all zeros while the feature is off
   std::vector<std::vector<double>> getGlobalRiskMatrix();
+  // How R was last brought up to date: 0 not yet, 1 the whole clearance solve, 2 the
+  // incremental update after setCostMapWindow added obstacles (dymu_clearance_update_device:
+  // the box's speed uploaded, the field re-propagated from the new cells, the rows of the
+  // box the engine reports downloaded and re-packed).
+  int lastRiskUpdateKind() const { return risk_update_kind_; }
+  // ... the engine's statistics of that solve or update (ms: its device time), and the box
+  // {i0, j0, w, h} of R it rewrote: the whole grid, or what the incremental update reported
+  const dymu_stats& lastRiskStats() const { return risk_stats_; }
+  const uint32_t* lastRiskBox() const { return risk_box_; }
 
  private:
   // the global risk: on iff both are > 0; R (ny*nx, empty while off) belongs to the
@@ -466,14 +483,38 @@ class DyMuPathPlanner {
   std::vector<double> global_risk_;
   bool risk_stale_ = false;
   bool globalRiskOn() const { return grisk_distance_ > 0 && grisk_ratio_ > 0; }
+  // the obstacle mask (the raw speed), the constant work map and the clearance field,
+  // resident on the device: allocated at the first refresh of a grid, freed where dF_ /
+  // dT_ are.  risk_dev_valid_: they are those R was computed from
+  double *dMask_ = nullptr, *dW_ = nullptr, *dS_ = nullptr;
+  bool risk_dev_valid_ = false;
+  void dropRiskMaps();
+  // obstacles setCostMapWindow added since R was brought up to date: their bounding box
+  bool risk_pend_ = false;
+  unsigned rpend_i0_ = 0, rpend_i1_ = 0, rpend_j0_ = 0, rpend_j1_ = 0;
+  int risk_update_kind_ = 0;
+  dymu_stats risk_stats_{};
+  uint32_t risk_box_[4] = {0, 0, 0, 0};
+  // the speed without the risk factor, +inf for an obstacle node: the mask's source
+  double rawSpeed(uint64_t k) const {
+    return is_obstacle_[k] ? std::numeric_limits<double>::infinity()
+                           : global_res_ * cost_[k] * (2 + hazard_[k] - traff_[k]);
+  }
+  // R up to date: the whole recompute when stale, else the pending box incrementally
+  void syncGlobalRisk() {
+    if (!globalRiskOn()) return;
+    if (risk_stale_) refreshGlobalRisk();
+    else if (risk_pend_) updateGlobalRisk();
+  }
+  void updateGlobalRisk();
   // the speed of a non-obstacle node (:527-528), with the risk factor while that is on:
   // the one expression syncSpeed packs and propagateGlobalNode updates with
   double nodeSpeed(uint64_t k) const {
     const double f = global_res_ * cost_[k] * (2 + hazard_[k] - traff_[k]);
     return global_risk_.empty() ? f : f * (grisk_ratio_ * global_risk_[k] + 1.0);
   }
-  // R from the obstacles now on the map: the raw speed and the clearance field on
-  // temporary device maps, R = max(1 - S, 0); every row dirty
+  // R from the obstacles now on the map: the raw speed and the clearance field on the
+  // resident device maps, R = max(1 - S, 0); every row dirty
   void refreshGlobalRisk();
   uint64_t idx(unsigned i, unsigned j) const { return (uint64_t)j * nx_ + i; }
   // total cost of cell k: the device map, fetched into the host mirror in blocks

@@ -374,7 +374,8 @@ int dymu_solve_batch_until_device(dymu_ctx* ctx, const double* dF_stack, double*
  * (src/DyMu_LocalPathRepairing.cpp:493-576), here for the global layer.
  * dF: read only (by the seeding kernel alone).  dW: a caller-provided work map of nx x ny
  * doubles at pitch ld; the call fills it with c in every cell, obstacles included, and
- * solves on it; its contents afterwards are unspecified.  dS: the output.  On return every
+ * solves on it; the solve never writes the speed map, so on return it still holds c in every
+ * cell (what dymu_clearance_update_device starts from).  dS: the output.  On return every
  * cell whose converged value is <= 1 holds that value (within the parity bound
  * 1e-12 * max(1, S); an obstacle cell holds +0.0 exactly); every other cell holds an upper
  * bound of its converged value or +inf -- dymu_solve_seeds_until_device's contract with the
@@ -389,6 +390,34 @@ int dymu_solve_batch_until_device(dymu_ctx* ctx, const double* dF_stack, double*
  * until the exit. */
 int dymu_clearance_device(dymu_ctx* ctx, const double* dF, double* dW, double* dS, uint32_t nx,
                           uint32_t ny, uint64_t ld, double c, void* stream, dymu_stats* stats);
+/* The field after obstacles were ADDED inside a window, without a whole solve.
+ * Preconditions: dS meets dymu_clearance_device's contract for an old mask on the same grid,
+ * pitch and c; dW holds c in every cell, as that call left it; the obstacle set of dF
+ * (!(F < +inf)) is the old one plus cells inside the window [i0, i0+w) x [j0, j0+h), which
+ * is clipped to the grid.  Adding obstacles can only lower the field, so the old field is an
+ * upper bound of the new one and nothing is reset: the window's cells that are obstacles in
+ * dF and do not hold +0.0 yet are seeded at +0.0 (their tiles and, on a tile edge, the tiles
+ * across it queued with key 0, as the cold seeding does), and the priority passes run to the
+ * level 1 as in dymu_clearance_device.  They reach exactly as far as values change.
+ * Postcondition: dS meets the same contract for the new mask.  box (may be NULL) receives
+ * {i0, j0, w, h} in cells: the bounding box of the tiles (8 x 8 cells for kernel 4, 16 x 16
+ * for kernel 5) that a list of the call held, clipped to the grid; every cell of dS outside
+ * it is bit for bit what it was, the columns nx .. ld-1 included, and dF and dW are not
+ * written at all.  The box is reported, not derived: no geometric bound on how far a value
+ * <= 1 can change is proven for the discrete scheme.  With no new obstacle cell in the
+ * window: box = {i0, j0, 0, 0}, stats->passes = 0, nothing written.
+ * A cell of the window that is finite in dF but holds +0.0 in dS is a freed obstacle, which
+ * a decrease-only update cannot handle: DYMU_ERR_STATE, nothing written (the window is
+ * counted before it is seeded).  Obstacles freed or added outside the window are not seen.
+ * Always runs a priority kernel; deterministic and exact_sqrt as for any solve.  stats->ms
+ * covers the count, the seeding and the passes.  DYMU_ERR_ARG, before any device work: a
+ * null pointer (box and stats excepted), nx or ny = 0, ld < nx, c not > 0, NaN or infinite,
+ * w or h = 0, i0 >= nx, j0 >= ny.  DYMU_ERR_STATE while stepping is on.  Blocks until the
+ * exit. */
+int dymu_clearance_update_device(dymu_ctx* ctx, const double* dF, double* dW, double* dS,
+                                 uint32_t nx, uint32_t ny, uint64_t ld, double c, uint32_t i0,
+                                 uint32_t j0, uint32_t w, uint32_t h, void* stream,
+                                 uint32_t box[4], dymu_stats* stats);
 /* The risk folded into the speed, per cell and operation by operation:
  *   R = fmax(1.0 - S, 0.0);  out = F * (risk_ratio * R + 1.0)
  * so S > 1, S = +inf and risk_ratio = 0 give F bit for bit, and an obstacle stays +inf or

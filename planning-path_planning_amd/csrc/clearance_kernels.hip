@@ -14,6 +14,9 @@
 // histogram whose origin is 0: one launch, nothing depends on the order of arrival.  The
 // pass kernels run unchanged behind it.
 // k_inflate_speed folds the risk into the speed: out = F * (risk_ratio * R + 1).
+// k_seed_mask_window and k_claimed_box serve the incremental update after obstacles were
+// added inside a window: the new cells seeded into the old field, which is an upper bound
+// of the new one, and the bounding box of the tiles the passes behind it claimed.
 #include "fim_kernels.h"
 
 #include <algorithm>
@@ -117,6 +120,134 @@ __global__ __launch_bounds__(256) void k_seed_mask(const double* __restrict__ F,
   if (threadIdx.x == 0 && cells) atomicAdd(a.n_obst, cells);
 }
 
+// k_seed_mask for a warm field and a window of new obstacles (dymu_clearance_update_device):
+// the tiles that meet the clipped window, a workgroup on one tile at a time, one lane per
+// cell.  A cell of the window is NEW when it is an obstacle in F and S does not hold +0.0
+// yet, FREED when F is finite and S holds +0.0.  w.seed = 0 counts both and writes nothing
+// else; w.seed = 1 seeds the new cells as k_seed_mask seeds an obstacle cell: S = +0.0, the
+// edge-column entry, the tile and (priority kernels) the tiles across its edges claimed once
+// through tile_epoch, collected in LDS and published with one atomic per workgroup.
+__global__ __launch_bounds__(256) void k_seed_mask_window(const double* __restrict__ F,
+                                                          MaskSeedArgs a, MaskWindow w) {
+  __shared__ uint32_t s_q[kMaskQueue];
+  __shared__ uint32_t s_n, s_base;
+  __shared__ uint32_t s_edges[2];  // as in k_seed_mask
+  const uint32_t shard = blockIdx.x % kShards;
+  const uint32_t cj = threadIdx.x / a.tw, ci = threadIdx.x - cj * a.tw;
+  unsigned long long n_new = 0, n_freed = 0;  // lane 0
+  if (threadIdx.x == 0) s_n = s_edges[0] = s_edges[1] = 0u;
+  __syncthreads();
+  auto flush = [&]() {
+    const uint32_t n = s_n;
+    if (threadIdx.x == 0) {
+      s_base = atomicAdd(&a.counts[shard], n);
+      if (a.hist) atomicAdd(&a.hist[shard * kBins], n);  // key_bin(0, base = 0) = 0
+    }
+    __syncthreads();
+    const uint32_t base = s_base;
+    for (uint32_t k = threadIdx.x; k < n; k += blockDim.x)
+      a.list[(uint64_t)shard * a.shard_cap + base + k] = s_q[k];
+    __syncthreads();
+    if (threadIdx.x == 0) s_n = 0u;
+    __syncthreads();
+  };
+  const uint32_t nwt = w.ntwx * w.ntwy;
+  uint32_t it = 0;
+  for (uint32_t q = blockIdx.x; q < nwt; q += gridDim.x, ++it) {
+    uint32_t* edges = &s_edges[it & 1u];
+    if (threadIdx.x == 0) s_edges[(it + 1u) & 1u] = 0u;
+    const uint32_t wy = q / w.ntwx, wx = q - wy * w.ntwx;
+    const uint32_t tx = w.tx0 + wx, ty = w.ty0 + wy, tile = ty * a.ntx + tx;
+    const uint32_t i = tx * a.tw + ci, j = ty * a.th + cj;
+    bool fresh = false, freed = false;
+    if (i >= w.i0 && i < w.i1 && j >= w.j0 && j < w.j1) {  // i1 <= nx, j1 <= ny
+      const int64_t k = (int64_t)j * a.ld + i;
+      const bool obst = !(F[k] < kInfD);
+      const bool zero = __double_as_longlong(a.T[k]) == 0ll;
+      fresh = obst && !zero;
+      freed = !obst && zero;
+    }
+    if (!w.seed) {
+      const int nn = __syncthreads_count(fresh), nf = __syncthreads_count(freed);
+      if (threadIdx.x == 0u) n_new += (unsigned long long)nn, n_freed += (unsigned long long)nf;
+      continue;
+    }
+    if (fresh) {
+      a.T[(int64_t)j * a.ld + i] = 0.0;
+      uint32_t e = 0u;
+      if (ci == 0u && i > 0u) e |= 1u;
+      if (ci == a.tw - 1u && i + 1u < a.nx) e |= 2u;
+      if (cj == 0u && j > 0u) e |= 4u;
+      if (cj == a.th - 1u && j + 1u < a.ny) e |= 8u;
+      if (e) atomicOr(edges, e);
+      if (a.ec && (ci == 0u || ci == 15u))
+        a.ec[(uint64_t)tile * 32u + (ci ? 16u : 0u) + cj] = 0.0;
+    }
+    const int n_fresh = __syncthreads_count(fresh);
+    if (n_fresh && threadIdx.x < 5u) {
+      const uint32_t e = *edges;
+      uint32_t t = tile;
+      bool want = true;  // lane 0: the tile itself; 1..4: the tiles across its W, E, N, S edge
+      if (threadIdx.x == 1u) want = e & 1u, t = tile - 1u;
+      if (threadIdx.x == 2u) want = e & 2u, t = tile + 1u;
+      if (threadIdx.x == 3u) want = e & 4u, t = tile - a.ntx;
+      if (threadIdx.x == 4u) want = e & 8u, t = tile + a.ntx;
+      if (threadIdx.x > 0u && !a.keys) want = false;
+      if (want) {
+        if (a.keys) a.keys[t] = 0ull;
+        if (atomicMax(&a.tile_epoch[t], a.epoch) < a.epoch) s_q[atomicAdd(&s_n, 1u)] = t;
+      }
+    }
+    __syncthreads();
+    if (s_n > kMaskQueue - 8u) flush();
+  }
+  if (w.seed) {
+    if (s_n > 0u) flush();
+  } else if (threadIdx.x == 0) {
+    if (n_new) atomicAdd(a.n_obst, n_new);
+    if (n_freed) atomicAdd(w.n_freed, n_freed);
+  }
+}
+
+// box = {x0, y0, x1, y1} in tiles (x1, y1 exclusive; from {~0, ~0, 0, 0}) over the tiles whose
+// stamp is at least epoch_lo, the first epoch of the domain that just ran: the tiles some
+// list of it held.  A lane's tiles by grid stride, a shuffle reduction per wave, the waves'
+// results through LDS, one atomic per word and workgroup.
+__global__ __launch_bounds__(256) void k_claimed_box(const uint32_t* __restrict__ tile_epoch,
+                                                     uint32_t ntiles, uint32_t ntx,
+                                                     uint32_t epoch_lo, uint32_t* box) {
+  __shared__ uint32_t s_box[8][4];  // up to 8 waves of 32
+  uint32_t x0 = ~0u, y0 = ~0u, x1 = 0u, y1 = 0u;
+  for (uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x; t < ntiles;
+       t += (uint64_t)gridDim.x * 256u)
+    if (tile_epoch[t] >= epoch_lo) {
+      const uint32_t ty = (uint32_t)t / ntx, tx = (uint32_t)t - ty * ntx;
+      x0 = min(x0, tx), y0 = min(y0, ty), x1 = max(x1, tx + 1u), y1 = max(y1, ty + 1u);
+    }
+  for (int off = warpSize / 2; off > 0; off >>= 1) {
+    x0 = min(x0, (uint32_t)__shfl_xor((int)x0, off));
+    y0 = min(y0, (uint32_t)__shfl_xor((int)y0, off));
+    x1 = max(x1, (uint32_t)__shfl_xor((int)x1, off));
+    y1 = max(y1, (uint32_t)__shfl_xor((int)y1, off));
+  }
+  const uint32_t wave = threadIdx.x / warpSize, nwaves = blockDim.x / warpSize;
+  if (threadIdx.x % warpSize == 0u)
+    s_box[wave][0] = x0, s_box[wave][1] = y0, s_box[wave][2] = x1, s_box[wave][3] = y1;
+  __syncthreads();
+  if (threadIdx.x == 0u) {
+    for (uint32_t v = 1; v < nwaves; ++v) {
+      x0 = min(x0, s_box[v][0]), y0 = min(y0, s_box[v][1]);
+      x1 = max(x1, s_box[v][2]), y1 = max(y1, s_box[v][3]);
+    }
+    if (x1) {
+      atomicMin(&box[0], x0);
+      atomicMin(&box[1], y0);
+      atomicMax(&box[2], x1);
+      atomicMax(&box[3], y1);
+    }
+  }
+}
+
 // a wave on 64 consecutive doubles of a row, 2-D grid stride; out may be F (every cell is
 // read and written by its own lane)
 __global__ __launch_bounds__(256) void k_inflate_speed(const double* F, const double* S,
@@ -150,6 +281,22 @@ hipError_t launch_seed_mask(const double* F, const MaskSeedArgs& a, uint32_t nti
                             hipStream_t st) {
   hipLaunchKernelGGL(k_seed_mask, dim3(std::min(ntiles, std::max(blocks, 1u))), dim3(a.tw * a.th),
                      0, st, F, a, ntiles);
+  return hipGetLastError();
+}
+
+hipError_t launch_seed_mask_window(const double* F, const MaskSeedArgs& a, const MaskWindow& w,
+                                   uint32_t blocks, hipStream_t st) {
+  const uint32_t nwt = w.ntwx * w.ntwy;
+  hipLaunchKernelGGL(k_seed_mask_window, dim3(std::min(nwt, std::max(blocks, 1u))),
+                     dim3(a.tw * a.th), 0, st, F, a, w);
+  return hipGetLastError();
+}
+
+hipError_t launch_claimed_box(const uint32_t* tile_epoch, uint32_t ntiles, uint32_t ntx,
+                              uint32_t epoch_lo, uint32_t* box, hipStream_t st) {
+  const unsigned blocks = (unsigned)std::min<uint64_t>(((uint64_t)ntiles + 255u) / 256u, 1024u);
+  hipLaunchKernelGGL(k_claimed_box, dim3(blocks), dim3(256), 0, st, tile_epoch, ntiles, ntx,
+                     epoch_lo, box);
   return hipGetLastError();
 }
 

@@ -2233,6 +2233,126 @@ int dymu_clearance_device(dymu_ctx* c, const double* dF, double* dW, double* dS,
   return converge_level(c, st, stats, 1.0);
 }
 
+// The field after obstacles were added inside a window: a warm, decrease-only start on
+// (dW, dS) -- the old field bounds the new one from above, so nothing is reset -- from the
+// new obstacle cells, the passes under converge_level, then the box of the claimed tiles.
+int dymu_clearance_update_device(dymu_ctx* c, const double* dF, double* dW, double* dS,
+                                 uint32_t nx, uint32_t ny, uint64_t ld, double step, uint32_t i0,
+                                 uint32_t j0, uint32_t w, uint32_t h, void* stream,
+                                 uint32_t box[4], dymu_stats* stats) {
+  if (!c || !dF || !dW || !dS || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
+  if (!(step > 0.0) || !(step < __builtin_inf())) return DYMU_ERR_ARG;
+  if (w == 0 || h == 0 || i0 >= nx || j0 >= ny) return DYMU_ERR_ARG;
+  if (c->stepping) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  HIPC(c, hipEventRecord(c->ev0, st));
+  const int variant = dom_variant(c, nx, ny, /*need_keys=*/true);
+  MaskSeedArgs a{};
+  a.T = dS;
+  a.ld = (int64_t)ld;
+  a.nx = nx;
+  a.ny = ny;
+  a.tw = (uint32_t)tile_w(variant);
+  a.th = (uint32_t)tile_h(variant);
+  a.ntx = (nx + a.tw - 1u) / a.tw;
+  a.n_obst = c->d_scratch + 4;
+  MaskWindow win{};
+  win.i0 = i0;
+  win.j0 = j0;
+  win.i1 = (uint32_t)std::min<uint64_t>((uint64_t)i0 + w, nx);
+  win.j1 = (uint32_t)std::min<uint64_t>((uint64_t)j0 + h, ny);
+  win.tx0 = i0 / a.tw;
+  win.ty0 = j0 / a.th;
+  win.ntwx = (win.i1 - 1u) / a.tw - win.tx0 + 1u;
+  win.ntwy = (win.j1 - 1u) / a.th - win.ty0 + 1u;
+  win.n_freed = c->d_scratch + 5;
+  if ((uint64_t)win.ntwx * win.ntwy >= (1ull << 31)) return DYMU_ERR_ARG;  // as dom_begin's tiles
+  const uint32_t blocks = (uint32_t)c->cu_count * 8u;
+  // count first: the new obstacle cells and the freed ones, nothing written
+  hipError_t e = hipMemsetAsync(c->d_scratch + 4, 0, 2 * sizeof(unsigned long long), st);
+  if (e == hipSuccess) e = launch_seed_mask_window(dF, a, win, blocks, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(c->h_probe, c->d_scratch + 4, 2 * sizeof(unsigned long long),
+                       hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail_hip(c, e, "obstacle window count");
+  if (c->h_probe[1] != 0ull) {
+    c->last_error = "clearance update: the window frees an obstacle cell";
+    return DYMU_ERR_STATE;
+  }
+  if (c->h_probe[0] == 0ull) {  // nothing new: the field stands
+    HIPC(c, hipEventRecord(c->ev1, st));
+    HIPC(c, hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (box) box[0] = i0, box[1] = j0, box[2] = box[3] = 0u;
+    if (stats) {
+      std::memset(stats, 0, sizeof *stats);
+      stats->ms = ms;
+      stats->tile_w = (int)a.tw;
+      stats->tile_h = (int)a.th;
+      stats->kernel = variant;
+    }
+    return DYMU_OK;
+  }
+  // A per-pass target of one tile: every pass relaxes the lowest non-empty key bin only
+  // (pass_scan's b*), so the tiles are visited in key order and none whose key lies above
+  // the bin of the level is visited before the stop test sees it.  With the solves' target
+  // a list shorter than the target is relaxed whole, whatever its keys: every pass then
+  // lowers one more ring of tiles of a field that is +inf beyond the level, and the box
+  // grows by a tile per pass (512x64 wall map, a block at column 300: 54 visits and a box
+  // of 13 tiles instead of the 4 tiles within the level's reach plus their ring).
+  const uint32_t saved_target = c->prio_target;
+  c->prio_target = 1u;
+  int rc = dom_begin(c, dW, dS, nx, ny, ld, 0, 0, -1, -1, st, /*cold=*/false, /*need_keys=*/true);
+  c->prio_target = saved_target;
+  if (rc) return rc;
+  auto& D = c->dom;
+  a.list = D.lists[0];
+  a.counts = D.counts[0];
+  a.shard_cap = D.ntiles;
+  a.tile_epoch = c->d_tile_epoch;
+  a.epoch = D.eb + 1;
+  a.keys = prio_keys(c, 0);
+  a.hist = prio_hist(c, 0);
+  a.ec = D.a.ec;
+  win.seed = 1u;
+  const uint32_t eb = D.eb, ntiles = D.ntiles, ntx = (uint32_t)D.a.ntx;
+  e = launch_store_u64(prio_minkey(c, 0), 0ull, st);
+  if (e == hipSuccess)
+    e = launch_store_u64(reinterpret_cast<unsigned long long*>(prio_base(c, 0)), 0ull, st);
+  // the edge columns belong to whatever domain ran last: from the old field, then the
+  // seeding kernel adds the new cells'
+  if (e == hipSuccess && D.a.ec) e = launch_ec_rebuild(dS, ld, nx, ny, D.a.ec, ntx, 0, ntiles, st);
+  if (e == hipSuccess) e = launch_seed_mask_window(dF, a, win, blocks, st);
+  if (e != hipSuccess) {
+    dom_retire(c);
+    return fail_hip(c, e, "obstacle window seeding");
+  }
+  rc = converge_level(c, st, stats, 1.0);
+  if (rc) return rc;
+  // every tile a list of this domain held carries a stamp above eb; the stamps are left to
+  // the next domain, whose epochs lie above them
+  uint32_t* dbox = reinterpret_cast<uint32_t*>(c->d_scratch + 2);
+  e = launch_store_u64(c->d_scratch + 2, ~0ull, st);
+  if (e == hipSuccess) e = launch_store_u64(c->d_scratch + 3, 0ull, st);
+  if (e == hipSuccess) e = launch_claimed_box(c->d_tile_epoch, ntiles, ntx, eb + 1u, dbox, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(c->h_probe, dbox, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail_hip(c, e, "claimed-tile box");
+  if (box) {
+    uint32_t t[4];
+    std::memcpy(t, c->h_probe, sizeof t);
+    const uint32_t bi0 = t[0] * a.tw, bj0 = t[1] * a.th;
+    const uint32_t bi1 = (uint32_t)std::min<uint64_t>((uint64_t)t[2] * a.tw, nx);
+    const uint32_t bj1 = (uint32_t)std::min<uint64_t>((uint64_t)t[3] * a.th, ny);
+    box[0] = bi0, box[1] = bj0, box[2] = bi1 - bi0, box[3] = bj1 - bj0;
+  }
+  return DYMU_OK;
+}
+
 int dymu_inflate_speed_device(dymu_ctx* c, const double* dF, const double* dS, double* dOut,
                               uint32_t nx, uint32_t ny, uint64_t ld, double risk_ratio,
                               void* stream) {

@@ -518,6 +518,23 @@ hipError_t launch_fill_const(double* W, uint64_t ld, uint32_t nx, uint32_t ny, d
 // bin 0.  `blocks` workgroups, each on one tile at a time.
 hipError_t launch_seed_mask(const double* F, const MaskSeedArgs& a, uint32_t ntiles, uint32_t blocks,
                             hipStream_t st);
+// The window of dymu_clearance_update_device: cells [i0, i1) x [j0, j1), clipped to the
+// grid, and the ntwx x ntwy tiles from (tx0, ty0) that meet it.
+struct MaskWindow {
+  uint32_t i0, j0, i1, j1;
+  uint32_t tx0, ty0, ntwx, ntwy;
+  uint32_t seed;                // 0: count only; 1: seed the new obstacle cells
+  unsigned long long* n_freed;  // count only: += the cells finite in F that hold +0.0
+};
+// seed = 0: *a.n_obst += the window's cells that are obstacles in F and do not hold +0.0 in
+// a.T, *w.n_freed += its cells finite in F that hold +0.0; nothing else is written.
+// seed = 1: k_seed_mask's seeding for exactly the former cells (a.n_obst is not used).
+hipError_t launch_seed_mask_window(const double* F, const MaskSeedArgs& a, const MaskWindow& w,
+                                   uint32_t blocks, hipStream_t st);
+// box[0..3] (from {~0, ~0, 0, 0}) = min tx, min ty, max tx + 1, max ty + 1 over the tiles with
+// tile_epoch >= epoch_lo
+hipError_t launch_claimed_box(const uint32_t* tile_epoch, uint32_t ntiles, uint32_t ntx,
+                              uint32_t epoch_lo, uint32_t* box, hipStream_t st);
 // out = F * (risk_ratio * max(1 - S, 0) + 1) per cell, operation by operation; out may be F
 hipError_t launch_inflate_speed(const double* F, const double* S, double* out, uint64_t ld,
                                 uint32_t nx, uint32_t ny, double risk_ratio, hipStream_t st);

@@ -61,6 +61,7 @@ void release_engine(dymu_ctx*& ctx, double*& dF, double*& dT, void*& reg, uint64
 DyMuPathPlanner::~DyMuPathPlanner() {
   dropLabels();
   dropBatch();
+  dropRiskMaps();
   release_engine(ctx_, dF_, dT_, registered_, dcells_);
 }
 
@@ -71,6 +72,7 @@ void DyMuPathPlanner::setEngineOptions(const dymu_opts& o) {
   if (ctx_ && dT_ && blk_missing_) fetchAll();
   dropLabels();
   dropBatch();
+  dropRiskMaps();
   release_engine(ctx_, dF_, dT_, registered_, dcells_);
   dev_map_current_ = false;
   solved_ = false, gs_seeds_.clear();
@@ -158,6 +160,49 @@ bool DyMuPathPlanner::setCostMap(std::vector<std::vector<double>> cost_map) {
   }
   risk_stale_ = true;
   markDirty(0, ny_);
+  return true;
+}
+
+#pragma weak dymu_clearance_update_device
+
+// setCostMap's per-cell rule on the cells of the box alone.  With the global risk on, the
+// obstacle mask is that of the raw speed (refreshGlobalRisk): a cell the box turns into an
+// obstacle joins the pending box of the incremental update; a cell it frees, or a field
+// on the device that is not the one R belongs to, leaves the whole recompute.
+bool DyMuPathPlanner::setCostMapWindow(unsigned i0, unsigned j0, unsigned w, unsigned h,
+                                       const double* cost) {
+  if (!cost || (uint64_t)i0 + w > nx_ || (uint64_t)j0 + h > ny_) return false;
+  const bool risk = globalRiskOn();
+  bool added = false, freed = false;
+  for (unsigned r = 0; r < h; ++r)
+    for (unsigned q = 0; q < w; ++q) {
+      const double c = cost[(uint64_t)r * w + q];
+      const uint64_t k = idx(i0 + q, j0 + r);
+      const bool was = risk && !(rawSpeed(k) < kInf);
+      cost_[k] = c;
+      if (c <= 0) {
+        is_obstacle_[k] = 1;
+        traff_[k] = 0.0;
+        hazard_[k] = 1.0;
+      }
+      if (risk) {
+        const bool now = !(rawSpeed(k) < kInf);
+        added = added || (now && !was);
+        freed = freed || (was && !now);
+      }
+    }
+  markDirty(j0, j0 + h);
+  if (freed || (added && (risk_stale_ || !risk_dev_valid_ || !&dymu_clearance_update_device))) {
+    risk_stale_ = true;
+  } else if (added) {
+    if (!risk_pend_) {
+      rpend_i0_ = i0, rpend_i1_ = i0 + w, rpend_j0_ = j0, rpend_j1_ = j0 + h;
+    } else {
+      rpend_i0_ = std::min(rpend_i0_, i0), rpend_i1_ = std::max(rpend_i1_, i0 + w);
+      rpend_j0_ = std::min(rpend_j0_, j0), rpend_j1_ = std::max(rpend_j1_, j0 + h);
+    }
+    risk_pend_ = true;
+  }
   return true;
 }
 
@@ -531,6 +576,7 @@ void DyMuPathPlanner::ensureEngine() {
     dF_ = dT_ = nullptr;
     dropLabels();
     dropBatch();
+    dropRiskMaps();
     dcells_ = 0;
     dev_map_current_ = false;
     void *f = nullptr, *t = nullptr;
@@ -559,7 +605,7 @@ void DyMuPathPlanner::ensureEngine() {
 // F = global_res * cost * (2 + hazard - traff) (:527-528), +inf for obstacles,
 // re-packed for the dirty rows; the rows whose F changed are uploaded.
 bool DyMuPathPlanner::syncSpeed(unsigned& i0, unsigned& i1, unsigned& j0, unsigned& j1) {
-  if (globalRiskOn() && risk_stale_) refreshGlobalRisk();
+  syncGlobalRisk();
   i0 = nx_;
   i1 = 0;
   j0 = ny_;
@@ -629,52 +675,115 @@ bool DyMuPathPlanner::setGlobalRisk(double risk_distance, double risk_ratio) {
     risk_stale_ = true;
   } else {
     std::vector<double>().swap(global_risk_);
+    dropRiskMaps();
   }
   if (on || was_on) markDirty(0, ny_);
   return true;
 }
 
+void DyMuPathPlanner::dropRiskMaps() {
+  for (double** p : {&dMask_, &dW_, &dS_}) {
+    if (*p && ctx_) (void)dymu_device_free(ctx_, *p);
+    *p = nullptr;
+  }
+  risk_dev_valid_ = false;
+  if (risk_pend_) risk_stale_ = true;  // the field the pending box would update is gone
+  risk_pend_ = false;
+}
+
 void DyMuPathPlanner::refreshGlobalRisk() {
   ensureEngine();
   const uint64_t n = (uint64_t)nx_ * ny_;
+  risk_pend_ = false;  // the whole recompute sees every obstacle
   if (n == 0) {
     risk_stale_ = false;
     return;
   }
-  // the raw speed, through R's own buffer, into a temporary map: the obstacle mask the
+  // the raw speed, through R's own buffer, into the mask map: the obstacle mask the
   // seeding kernel reads.  dF_ is not touched: it stays the upload of speed_, the speed
   // the solved maps belong to and the next diff is taken against
   global_risk_.resize(n);
-  for (uint64_t k = 0; k < n; ++k)
-    global_risk_[k] =
-        is_obstacle_[k] ? kInf : global_res_ * cost_[k] * (2 + hazard_[k] - traff_[k]);
-  void *f = nullptr, *w = nullptr, *s = nullptr;
-  int rc = dymu_device_alloc(ctx_, sizeof(double) * n, &f);
-  if (rc == DYMU_OK) rc = dymu_device_alloc(ctx_, sizeof(double) * n, &w);
-  if (rc == DYMU_OK) rc = dymu_device_alloc(ctx_, sizeof(double) * n, &s);
-  if (rc == DYMU_OK) rc = dymu_memcpy_h2d(ctx_, f, global_risk_.data(), sizeof(double) * n);
+  for (uint64_t k = 0; k < n; ++k) global_risk_[k] = rawSpeed(k);
+  risk_dev_valid_ = false;
+  int rc = DYMU_OK;
+  for (double** p : {&dMask_, &dW_, &dS_}) {
+    void* q = *p;
+    if (!q && rc == DYMU_OK) rc = dymu_device_alloc(ctx_, sizeof(double) * n, &q);
+    *p = static_cast<double*>(q);
+  }
+  if (rc == DYMU_OK) rc = dymu_memcpy_h2d(ctx_, dMask_, global_risk_.data(), sizeof(double) * n);
   dymu_stats st{};
   if (rc == DYMU_OK)
-    rc = dymu_clearance_device(ctx_, static_cast<double*>(f), static_cast<double*>(w),
-                               static_cast<double*>(s), nx_, ny_, nx_,
+    rc = dymu_clearance_device(ctx_, dMask_, dW_, dS_, nx_, ny_, nx_,
                                global_res_ / grisk_distance_, nullptr, &st);
-  if (rc == DYMU_OK) rc = dymu_memcpy_d2h(ctx_, global_risk_.data(), s, sizeof(double) * n);
-  const std::string err = rc == DYMU_OK ? "" : dymu_last_error(ctx_);
-  for (void* p : {f, w, s})
-    if (p) (void)dymu_device_free(ctx_, p);
+  if (rc == DYMU_OK) rc = dymu_memcpy_d2h(ctx_, global_risk_.data(), dS_, sizeof(double) * n);
   if (rc != DYMU_OK) {  // still stale: the next synchronisation tries again
+    const std::string err = dymu_last_error(ctx_);
     std::fill(global_risk_.begin(), global_risk_.end(), 0.0);
     throw std::runtime_error(std::string("dymu: global risk: ") + dymu_strerror(rc) + " " + err);
   }
   for (uint64_t k = 0; k < n; ++k) global_risk_[k] = std::fmax(1.0 - global_risk_[k], 0.0);
   risk_stale_ = false;
+  risk_dev_valid_ = true;
+  risk_update_kind_ = 1;
+  risk_stats_ = st;
+  risk_box_[0] = risk_box_[1] = 0, risk_box_[2] = nx_, risk_box_[3] = ny_;
   markDirty(0, ny_);
+}
+
+// R after setCostMapWindow added obstacles inside the pending box, R being current but for
+// them: the box's rows of the raw speed into the mask map, the field re-propagated from the new
+// cells (dymu_clearance_update_device), and the box the engine reports -- no cell of the
+// field outside it moved -- downloaded, turned into R and re-packed.  Whatever the engine
+// refuses (a freed cell it finds itself, an error) leaves the whole recompute.
+void DyMuPathPlanner::updateGlobalRisk() {
+  ensureEngine();  // a new grid or engine drops the maps and turns the box into risk_stale_
+  if (risk_stale_ || !risk_pend_ || !risk_dev_valid_ || !&dymu_clearance_update_device) {
+    risk_stale_ = true;
+    refreshGlobalRisk();
+    return;
+  }
+  risk_pend_ = false;
+  const unsigned i0 = rpend_i0_, j0 = rpend_j0_, w = rpend_i1_ - i0, h = rpend_j1_ - j0;
+  // whole rows, one contiguous copy: outside the box they differ from the mask map in
+  // finite values at most, and the engine reads the window's cells only
+  std::vector<double> raw((uint64_t)nx_ * h);
+  for (uint64_t k = 0; k < raw.size(); ++k) raw[k] = rawSpeed(idx(0, j0) + k);
+  int rc = dymu_memcpy_h2d(ctx_, dMask_ + idx(0, j0), raw.data(), sizeof(double) * raw.size());
+  uint32_t box[4] = {0, 0, 0, 0};
+  dymu_stats st{};
+  if (rc == DYMU_OK)
+    rc = dymu_clearance_update_device(ctx_, dMask_, dW_, dS_, nx_, ny_, nx_,
+                                      global_res_ / grisk_distance_, i0, j0, w, h, nullptr, box,
+                                      &st);
+  if (rc == DYMU_OK && box[2] && box[3]) {
+    const uint64_t o = idx(box[0], box[1]);
+    rc = dymu_memcpy2d_d2h(ctx_, &global_risk_[o], sizeof(double) * nx_, dS_ + o,
+                           sizeof(double) * nx_, sizeof(double) * box[2], box[3]);
+    if (rc != DYMU_OK) {  // R's box holds a partial download
+      risk_dev_valid_ = false;
+    } else {
+      for (unsigned r = 0; r < box[3]; ++r) {
+        double* g = &global_risk_[idx(box[0], box[1] + r)];
+        for (unsigned q = 0; q < box[2]; ++q) g[q] = std::fmax(1.0 - g[q], 0.0);
+      }
+      markDirty(box[1], box[1] + box[3]);
+    }
+  }
+  if (rc != DYMU_OK) {
+    risk_stale_ = true;
+    refreshGlobalRisk();
+    return;
+  }
+  risk_update_kind_ = 2;
+  risk_stats_ = st;
+  std::copy(box, box + 4, risk_box_);
 }
 
 std::vector<std::vector<double>> DyMuPathPlanner::getGlobalRiskMatrix() {
   std::vector<std::vector<double>> m(ny_, std::vector<double>(nx_, 0.0));
   if (!globalRiskOn()) return m;
-  if (risk_stale_) refreshGlobalRisk();
+  syncGlobalRisk();
   for (unsigned j = 0; j < ny_; ++j)
     for (unsigned i = 0; i < nx_; ++i) m[j][i] = global_risk_[idx(i, j)];
   return m;
@@ -2264,7 +2373,7 @@ std::vector<DyMuPathPlanner::PathStats> DyMuPathPlanner::getPathStats(
     return out;
   }
   if (!goals_.empty()) ensureHostLabels();
-  if (!speed_valid_ && globalRiskOn() && risk_stale_) refreshGlobalRisk();
+  if (!speed_valid_) syncGlobalRisk();
   const double* f0 = speed_valid_ ? speed_.data() : nullptr;
   const unsigned nt = (unsigned)std::min<size_t>(host_threads(), n);
   std::atomic<size_t> next{0};
@@ -2788,7 +2897,7 @@ void DyMuPathPlanner::propagateGlobalNode(unsigned i, unsigned j) {
     Tx = n2 ? t[k + 1] : kInf;
   else
     Tx = t[k - 1];
-  if (globalRiskOn() && risk_stale_) refreshGlobalRisk();
+  syncGlobalRisk();
   const double C = nodeSpeed(k);  // :527-528, times the global risk's factor (s5.11)
   double Tn;
   if ((std::fabs(Tx - Ty) < C) && (Tx < kInf) && (Ty < kInf))

@@ -1,6 +1,7 @@
 // planner_capi.cpp -- extern "C" forwarding layer (include/dymu_planner.h)
 // over PathPlanning_lib::DyMuPathPlanner.  Exceptions never cross the ABI:
 // an engine failure becomes DYMU_ERR_NO_DEVICE / DYMU_ERR_HIP.
+#include <algorithm>
 #include <cstring>
 #include <exception>
 #include <new>
@@ -248,6 +249,24 @@ int dymu_planner_set_hazard_density_window(dymu_planner* p, uint32_t i0, uint32_
                                            uint32_t h, const double* hd) {
   if (!p || !hd) return DYMU_ERR_ARG;
   return guarded([&] { return (int)p->pl.setHazardDensityWindow(i0, j0, w, h, hd); });
+}
+
+int dymu_planner_set_cost_map_window(dymu_planner* p, uint32_t i0, uint32_t j0, uint32_t w,
+                                     uint32_t h, const double* cost) {
+  if (!p || !cost) return DYMU_ERR_ARG;
+  return guarded([&] { return (int)p->pl.setCostMapWindow(i0, j0, w, h, cost); });
+}
+
+int dymu_planner_last_risk_update_kind(dymu_planner* p) {
+  if (!p) return DYMU_ERR_ARG;
+  return p->pl.lastRiskUpdateKind();
+}
+
+int dymu_planner_last_risk_update(dymu_planner* p, dymu_stats* out, uint32_t box[4]) {
+  if (!p) return DYMU_ERR_ARG;
+  if (out) *out = p->pl.lastRiskStats();
+  if (box) std::copy(p->pl.lastRiskBox(), p->pl.lastRiskBox() + 4, box);
+  return DYMU_OK;
 }
 
 int dymu_planner_set_trafficability_window(dymu_planner* p, uint32_t i0, uint32_t j0, uint32_t w,

@@ -256,6 +256,9 @@ FIM_SYMBOLS = {
                                              _vp, ctypes.POINTER(DymuStats)]),
     "dymu_clearance_device": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, ctypes.c_double, _vp,
                                      ctypes.POINTER(DymuStats)]),
+    "dymu_clearance_update_device": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, ctypes.c_double,
+                                            _u32, _u32, _u32, _u32, _vp, ctypes.POINTER(_u32),
+                                            ctypes.POINTER(DymuStats)]),
     "dymu_inflate_speed_device": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, ctypes.c_double,
                                          _vp]),
     "dymu_device_alloc_cached": (_i32, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
@@ -693,6 +696,22 @@ class Engine:
                                                stream or None, ctypes.byref(st)), self.ctx)
         return st.as_dict()
 
+    def clearance_update_device(self, dF: int, dW: int, dS: int, nx: int, ny: int, ld: int,
+                                c: float, i0: int, j0: int, w: int, h: int,
+                                stream: int = 0) -> dict:
+        """dymu_clearance_update_device: dS, the field clearance_device left for an old mask
+        (dW still holding c), brought to the mask of dF, which adds obstacle cells inside
+        the window only.  Returns the stats with "box": (i0, j0, w, h) of the cells the call
+        may have written."""
+        st = DymuStats()
+        box = (_u32 * 4)()
+        _check(self._lib.dymu_clearance_update_device(self.ctx, dF, dW, dS, nx, ny, ld, c, i0, j0,
+                                                      w, h, stream or None, box,
+                                                      ctypes.byref(st)), self.ctx)
+        d = st.as_dict()
+        d["box"] = tuple(int(v) for v in box)
+        return d
+
     def inflate_speed(self, dF: int, dS: int, dOut: int, nx: int, ny: int, ld: int,
                       risk_ratio: float, stream: int = 0):
         """dymu_inflate_speed_device: dOut = dF * (risk_ratio * max(1 - dS, 0) + 1); dOut may
@@ -1041,6 +1060,10 @@ PLANNER_SYMBOLS = {
     "dymu_planner_get_node_states": (_i32, [_vp, _vp]),
     "dymu_planner_set_hazard_density_window": (_i32, [_vp, _u32, _u32, _u32, _u32, _dp]),
     "dymu_planner_set_trafficability_window": (_i32, [_vp, _u32, _u32, _u32, _u32, _dp]),
+    "dymu_planner_set_cost_map_window": (_i32, [_vp, _u32, _u32, _u32, _u32, _dp]),
+    "dymu_planner_last_risk_update_kind": (_i32, [_vp]),
+    "dymu_planner_last_risk_update": (_i32, [_vp, ctypes.POINTER(DymuStats),
+                                             ctypes.POINTER(_u32)]),
     "dymu_planner_last_band_size": (ctypes.c_int64, [_vp]),
     "dymu_planner_get_global_node": (_i32, [_vp, _u32, _u32, _vp]),
     "dymu_planner_is_safe_node": (_i32, [_vp, _u32, _u32]),
@@ -1462,6 +1485,28 @@ class Planner:
         a = np.ascontiguousarray(tr, dtype=np.float64)
         h, w = a.shape
         return _b(self._lib.dymu_planner_set_trafficability_window(self.h, i0, j0, w, h, a))
+
+    def setCostMapWindow(self, i0: int, j0: int, cost) -> bool:
+        """setCostMap's per-cell rule for the box of `cost` (2-D, [j][i]) at (i0, j0) only:
+        the rows of the box alone are re-packed, and with the global risk on obstacles the
+        box adds reach R through the incremental update."""
+        a = np.ascontiguousarray(cost, dtype=np.float64)
+        h, w = a.shape
+        return _b(self._lib.dymu_planner_set_cost_map_window(self.h, i0, j0, w, h, a))
+
+    def lastRiskUpdateKind(self) -> int:
+        """How R was last brought up to date: 0 not yet, 1 whole solve, 2 incremental."""
+        return _b_int(self._lib.dymu_planner_last_risk_update_kind(self.h))
+
+    def lastRiskUpdate(self) -> dict:
+        """The engine's statistics of the last clearance solve or update, with "box": the
+        (i0, j0, w, h) of R it rewrote."""
+        st = DymuStats()
+        box = (_u32 * 4)()
+        _check(self._lib.dymu_planner_last_risk_update(self.h, ctypes.byref(st), box))
+        d = st.as_dict()
+        d["box"] = tuple(int(v) for v in box)
+        return d
 
     def lastBandSize(self) -> int:
         """Narrow-band cells left by the last computeTotalCostMap (0 after a full solve)."""
