@@ -408,6 +408,52 @@ class DyMuPathPlanner {
                        const std::vector<base::Waypoint>& targets, std::vector<double>& out);
   // +inf for a complete batch and with no batch
   double batchLevel() const { return batch_level_; }
+  // Combining the maps of the batch cell by cell on the device (DESIGN.md s5.14;
+  // dymu_batch_reduce_device in include/dymu_fim.h defines the fold, its order and its tie
+  // rules): op over the listed planes (empty: all, in order), each optionally weighted
+  // and offset (empty, or one value per listed plane).  The combined map and, for MAX / MIN,
+  // the map of the plane that gave each cell stay on the device; summary describes the
+  // combined map (its minimum below +inf, that cell, the cells below +inf).  Like the other
+  // batch readers it first completes a truncated batch and, with trackSpeedChanges,
+  // re-propagates a pending box.  False, with nothing changed: no batch, no device engine,
+  // an engine without the entry, a plane >= batchCount(), list lengths that do not match, a
+  // weight not finite or not > 0, an offset negative or not finite.
+  enum CombineOp { COMBINE_SUM = 0, COMBINE_MAX = 1, COMBINE_MIN = 2 };
+  typedef dymu_reduce_summary CombineSummary;
+  bool combineTotalCostMaps(CombineOp op, const std::vector<uint32_t>& planes,
+                            const std::vector<double>& weights, const std::vector<double>& offsets,
+                            CombineSummary* summary = nullptr);
+  // The combined map (ny*nx, row-major) raw (+inf) or as getTotalCostMatrix (-1), and the
+  // plane map of the last MAX / MIN (0xFFFFFFFF: a MIN cell no plane reaches).  False once
+  // the combined map no longer belongs to the batch: after dropBatch, after any solve or
+  // refresh that rewrote the stack (lastBatchSolveKind() 0 or 1), after a new grid or new
+  // engine options; copyCombinedPlanes also after a SUM.  A reuse (kind 2) keeps it.
+  bool copyCombinedTotalCost(double* out, bool raw);
+  bool copyCombinedPlanes(uint32_t* out);
+  // The corridor between goals a and b of the batch: the via field T_a + T_b (the cost of
+  // the best a-b route through each cell; left as the combined map), D_min its discrete
+  // minimum (the a-b traverse cost), bound = D_min * (1.0 + slack), and mask (ny*nx bytes)
+  // = 1 where the via field is <= bound -- relative to the field's own minimum, so the
+  // corridor is never empty.  False, with nothing written: a or b >= batchCount(), slack
+  // negative or not finite, no finite cell in the via field, or what combineTotalCostMaps
+  // refuses.
+  struct CorridorInfo {
+    double D_min;
+    uint32_t min_i, min_j;        // a cell that attains it (the lowest row-major one)
+    uint64_t count;               // marked cells
+    uint32_t i0, j0, i1, j1;      // their inclusive box
+    double bound;
+  };
+  bool viaCorridor(unsigned a, unsigned b, double slack, uint8_t* mask, CorridorInfo* info);
+  // Where the listed planes' rovers should meet: the cell that minimises the MAX (minimax:
+  // everyone there soonest) or the SUM (least total effort) of their weighted, offset maps,
+  // and that value; the lowest row-major cell among equals.  False when no cell is finite.
+  // Leaves the combined map as combineTotalCostMaps would.
+  bool rendezvous(const std::vector<uint32_t>& planes, const std::vector<double>& weights,
+                  const std::vector<double>& offsets, bool minimax, unsigned* i, unsigned* j,
+                  double* value);
+  // the kernel time (HIP events, ms) of the last combine, 0 before the first
+  double lastCombineKernelMs() const { return last_combine_ms_; }
   // getPaths on map b with goal b as the sink (always on the device; sinks are 0).
   // Throws std::invalid_argument for b >= batchCount().
   std::vector<std::vector<base::Waypoint>> getPathsTo(unsigned b,
@@ -626,6 +672,19 @@ class DyMuPathPlanner {
   // (+inf: a complete batch, or none)
   double batch_level_ = __builtin_inf();
   void dropBatch();
+  // the combined map (combineTotalCostMaps): nx_*ny_ doubles, the arg map and viaCorridor's
+  // byte mask, pitch nx_; allocated on first use, kept for the grid (dropCombined frees them
+  // where the map buffers go); comb_valid_: the combined map is that of the held stack
+  double* d_comb_ = nullptr;
+  uint32_t* d_comb_arg_ = nullptr;
+  uint8_t* d_comb_mask_ = nullptr;
+  bool comb_valid_ = false, comb_arg_valid_ = false;
+  double last_combine_ms_ = 0.0;
+  void dropCombined();
+  // the held batch brought up to date and the reduction run into d_comb_ / d_comb_arg_
+  bool combineOnDevice(int op, const std::vector<uint32_t>& planes,
+                       const std::vector<double>& weights, const std::vector<double>& offsets,
+                       dymu_reduce_summary& s);
   // computeTotalCostMaps' preamble: the goals validated into bg, the engine made, the
   // speed synchronised (a change found is passed on as there); false: rejected
   bool prepareBatch(const std::vector<base::Waypoint>& goals, std::vector<BatchGoal>& bg);

@@ -325,6 +325,59 @@ int dymu_gather_costs_device(dymu_ctx* ctx, const double* dT_stack, uint32_t nx,
                              uint32_t B, uint64_t ld, double res, const double* d_xy, uint32_t M,
                              double* d_out, void* stream);
 
+/* ---- combining the planes of a stack: via fields, rendezvous, nearest plane ----
+ * d_out[j * out_ld + i] = one left-to-right fold over the listed planes p_0 .. p_{n-1} of
+ * cell (i, j), in fp64, operation by operation:
+ *   term_k = T[p_k]                    neither weights nor offsets
+ *            w_k * T[p_k]              weights only
+ *            T[p_k] + o_k              offsets only
+ *            w_k * T[p_k] + o_k        both (two roundings)
+ *   acc = term_0, arg = p_0; then for k = 1 .. n-1
+ *     SUM  acc = acc + term_k
+ *     MAX  if (term_k > acc) acc = term_k, arg = p_k
+ *     MIN  if (term_k < acc) acc = term_k, arg = p_k
+ * so equal terms keep the earlier listed plane, +inf propagates by arithmetic, and the same
+ * loop on the host gives the same bits.  A MIN cell that ends at +inf gets arg = 0xFFFFFFFF
+ * (no plane reaches it, as DYMU_LABEL_NONE).  d_arg (MAX / MIN only; may be NULL; not
+ * written for SUM) receives arg.  planes: HOST list of n_planes <= 65536 plane indices < B,
+ * duplicates and any order allowed (the order is part of a SUM's bits); NULL: 0 .. B-1.
+ * weights (finite, > 0) and offsets (finite, >= 0): HOST, one per listed plane, or NULL.
+ * Only rows 0 .. ny-1 of a plane are read -- never a wall row -- and only columns
+ * 0 .. nx-1 of d_out and d_arg are written.  The stack is read only.
+ * summary (HOST, may be NULL) describes d_out; equal minima resolve to the lowest row-major
+ * cell whatever order the workgroups finish in (per-workgroup partials and a final pass, no
+ * atomics).  Without it the call is asynchronous on `stream`; with it, it synchronises.  One
+ * call at a time per context (the staged list and the partials are the context's).
+ * DYMU_ERR_ARG, before any device work: a null ctx, dT_stack or d_out; nx, ny or B = 0; ld,
+ * out_ld or (with d_arg) arg_ld below nx; an unknown op; n_planes = 0 with a list, or above
+ * 65536 (B above 65536 without one); a listed plane >= B; a weight not finite or not > 0; an
+ * offset negative, NaN or infinite; B * P not fitting in uint32_t; d_out or d_arg overlapping
+ * the stack's address range. */
+typedef enum { DYMU_REDUCE_SUM = 0, DYMU_REDUCE_MAX = 1, DYMU_REDUCE_MIN = 2 } dymu_reduce_op;
+typedef struct dymu_reduce_summary {
+  double   min_value;      /* smallest value of out below +inf; +inf when there is none          */
+  uint32_t min_i, min_j;   /* its cell: the lowest j*nx+i among equals; 0xFFFFFFFF when none      */
+  uint32_t min_plane;      /* d_arg at that cell (MAX/MIN); 0xFFFFFFFF for SUM or when none       */
+  uint32_t reserved;
+  uint64_t n_finite;       /* cells of out below +inf                                             */
+} dymu_reduce_summary;
+int dymu_batch_reduce_device(dymu_ctx* ctx, const double* dT_stack, uint32_t nx, uint32_t ny,
+                             uint32_t B, uint64_t ld, int op, const uint32_t* planes,
+                             uint32_t n_planes, const double* weights, const double* offsets,
+                             double* d_out, uint64_t out_ld, uint32_t* d_arg, uint64_t arg_ld,
+                             dymu_reduce_summary* summary, void* stream);
+/* Device time (ms, HIP events) of the last dymu_batch_reduce_device's kernels; waits for
+ * them.  DYMU_ERR_STATE before the first one. */
+int dymu_last_reduce_ms(dymu_ctx* ctx, double* ms);
+/* The sub-level set of a map: d_mask[j * mask_ld + i] = d_map[j * ld + i] <= bound ? 1 : 0
+ * (device bytes, columns 0 .. nx-1 only).  out (HOST, may be NULL): the inclusive box i0, j0,
+ * i1, j1 of the marked cells (i0 > i1 when there is none), n_range = their number,
+ * r_const = 0.  Asynchronous on `stream` without out, synchronises with it.  DYMU_ERR_ARG: a
+ * null ctx, d_map or d_mask, nx or ny = 0, ld or mask_ld below nx, bound NaN or infinite. */
+int dymu_level_mask_device(dymu_ctx* ctx, const double* d_map, uint32_t nx, uint32_t ny,
+                           uint64_t ld, double bound, uint8_t* d_mask, uint64_t mask_ld,
+                           dymu_region* out, void* stream);
+
 /* ---- early exit on target cells for seeded and batched solves ----
  * The cold solves of dymu_solve_seeds_device / dymu_solve_batch_device with a stop test
  * over a list of target cells (HOST array, like the seeds).  A target COUNTS when its

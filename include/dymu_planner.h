@@ -151,6 +151,40 @@ int dymu_planner_last_batch_stats(dymu_planner* p, dymu_stats* out);
 int dymu_planner_track_speed_changes(dymu_planner* p, int on);
 /* lastBatchSolveKind(): 0 cold solve, 1 windowed re-propagation, 2 batch reused */
 int dymu_planner_last_batch_solve_kind(dymu_planner* p);
+/* ---- combining the maps of the batch (DyMuPathPlanner::combineTotalCostMaps, DESIGN.md
+ * s5.14; the fold, its order and its tie rules: dymu_batch_reduce_device) ----
+ * op (dymu_reduce_op) over the listed maps -- planes: n_planes indices, NULL: all maps in
+ * order -- with optional weights and offsets, one per listed map (per map of the batch
+ * without a list), or NULL.  The combined map and the MAX / MIN plane map stay on the
+ * device; summary (may be NULL) describes the combined map.  1 = combined, 0 = refused
+ * (no batch, no device engine, a bad list: nothing changed). */
+int dymu_planner_combine_total_cost_maps(dymu_planner* p, int op, const uint32_t* planes,
+                                         uint32_t n_planes, const double* weights,
+                                         const double* offsets, dymu_reduce_summary* summary);
+/* the combined map (ny*nx doubles; raw != 0: +inf, else -1) and the plane map of the last
+ * MAX / MIN (ny*nx words).  1 = copied, 0 = none that belongs to the held batch: it ends
+ * with the batch and with every solve or refresh that rewrites the stack. */
+int dymu_planner_copy_combined_total_cost(dymu_planner* p, double* out, int raw);
+int dymu_planner_copy_combined_planes(dymu_planner* p, uint32_t* out);
+/* viaCorridor: mask (ny*nx bytes) = 1 where T_a + T_b <= bound = D_min * (1 + slack), D_min
+ * the minimum of that sum; info as DyMuPathPlanner::CorridorInfo.  1 = written, 0 = refused
+ * (a or b >= batch_count, slack negative or not finite, no finite cell: nothing written). */
+typedef struct dymu_corridor_info {
+  double d_min;
+  uint32_t min_i, min_j;
+  uint64_t count;
+  uint32_t i0, j0, i1, j1;
+  double bound;
+} dymu_corridor_info;
+int dymu_planner_via_corridor(dymu_planner* p, uint32_t a, uint32_t b, double slack, uint8_t* mask,
+                              dymu_corridor_info* info);
+/* rendezvous: the cell minimising the MAX (minimax != 0) or the SUM of the listed maps
+ * (lists as for combine) and that value.  1 = written, 0 = refused or no finite cell. */
+int dymu_planner_rendezvous(dymu_planner* p, const uint32_t* planes, uint32_t n_planes,
+                            const double* weights, const double* offsets, int minimax, uint32_t* i,
+                            uint32_t* j, double* value);
+/* kernel time (HIP events, ms) of the last combine; 0 before the first */
+int dymu_planner_last_combine_kernel_ms(dymu_planner* p, double* ms);
 /* getLocomotionMode (:788-795) into buf (NUL-terminated) */
 int dymu_planner_get_locomotion_mode(dymu_planner* p, double x, double y, double z, double heading,
                                      char* buf, int buflen);

@@ -102,6 +102,19 @@ struct dymu_ctx {
   void* d_xfer = nullptr;       // its device address
   uint64_t xfer_cap = 0;        // bytes
   unsigned long long* d_region = nullptr;  // dymu_region_stats' 8 device words
+  // dymu_batch_reduce_device / dymu_level_mask_device (reduce_kernels.hip):
+  // the term list staged in pinned memory and copied to the device on the call's stream
+  // (ev_red_copy: the copy has read the pinned list, which the next call rewrites); one
+  // partial per workgroup, then the summary record and the level mask's words; 64 pinned
+  // bytes for the results
+  ReduceTerm* h_red_terms = nullptr;
+  ReduceTerm* d_red_terms = nullptr;
+  uint32_t red_cap = 0;
+  ReducePartial* d_red_part = nullptr;
+  uint32_t red_blocks = 0;
+  void* h_red_res = nullptr;
+  hipEvent_t ev_red_copy = nullptr, ev_red0 = nullptr, ev_red1 = nullptr;
+  bool red_copy_pending = false, red_timed = false;
   unsigned long long* d_scratch = nullptr;  // 8 words of per-call device scalars
   double* d_lut = nullptr;      // computeCostMap LUT (device copy)
   size_t lut_cap = 0;
@@ -1691,6 +1704,13 @@ int dymu_destroy(dymu_ctx* c) {
   if (c->d_band) (void)hipFree(c->d_band);
   if (c->h_xfer) (void)hipHostFree(c->h_xfer);
   if (c->d_region) (void)hipFree(c->d_region);
+  if (c->ev_red_copy) (void)hipEventDestroy(c->ev_red_copy);
+  if (c->ev_red0) (void)hipEventDestroy(c->ev_red0);
+  if (c->ev_red1) (void)hipEventDestroy(c->ev_red1);
+  if (c->h_red_terms) (void)hipHostFree(c->h_red_terms);
+  if (c->h_red_res) (void)hipHostFree(c->h_red_res);
+  if (c->d_red_terms) (void)hipFree(c->d_red_terms);
+  if (c->d_red_part) (void)hipFree(c->d_red_part);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return DYMU_OK;
@@ -2373,6 +2393,169 @@ int dymu_gather_costs_device(dymu_ctx* c, const double* dT_stack, uint32_t nx, u
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, launch_gather_costs(dT_stack, ld, nx, ny, B, dymu_batch_plane_rows(ny), res, d_xy, M,
                               d_out, pick_stream(c, stream)));
+  return DYMU_OK;
+}
+
+/* ---- plane reduction and level mask (reduce_kernels.hip) ---- */
+
+namespace {
+// the pinned result words, the partials (one per workgroup of the largest grid, then the
+// summary record, then the level mask's words) and the events
+int ensure_reduce(dymu_ctx* c) {
+  if (!c->ev_red_copy) HIPC(c, hipEventCreateWithFlags(&c->ev_red_copy, hipEventDisableTiming));
+  if (!c->ev_red0) HIPC(c, hipEventCreate(&c->ev_red0));
+  if (!c->ev_red1) HIPC(c, hipEventCreate(&c->ev_red1));
+  if (!c->h_red_res) HIPC(c, hipHostMalloc(&c->h_red_res, 64, hipHostMallocDefault));
+  if (!c->d_red_part) {
+    c->red_blocks = (uint32_t)std::max(c->cu_count, 1) * 8u;
+    HIPC(c, hipMalloc(&c->d_red_part, sizeof(ReducePartial) * (c->red_blocks + 2ull)));
+  }
+  return DYMU_OK;
+}
+// [a, a + na) and [b, b + nb) share a byte
+bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + nb && pb < pa + na;
+}
+// bytes from a pitched map's first cell to the end of its last row's nx cells
+uint64_t map_span(uint64_t rows, uint64_t ld, uint32_t nx, uint64_t elem) {
+  return ((rows - 1) * ld + nx) * elem;
+}
+}  // namespace
+
+int dymu_batch_reduce_device(dymu_ctx* c, const double* dT_stack, uint32_t nx, uint32_t ny,
+                             uint32_t B, uint64_t ld, int op, const uint32_t* planes,
+                             uint32_t n_planes, const double* weights, const double* offsets,
+                             double* d_out, uint64_t out_ld, uint32_t* d_arg, uint64_t arg_ld,
+                             dymu_reduce_summary* summary, void* stream) {
+  uint32_t rows = 0;
+  if (!c || !dT_stack || !d_out || !batch_rows(nx, ny, B, ld, &rows)) return DYMU_ERR_ARG;
+  if (out_ld < nx || (d_arg && arg_ld < nx)) return DYMU_ERR_ARG;
+  if (op != DYMU_REDUCE_SUM && op != DYMU_REDUCE_MAX && op != DYMU_REDUCE_MIN) return DYMU_ERR_ARG;
+  const uint32_t n = planes ? n_planes : B;
+  if (n == 0 || n > 65536u) return DYMU_ERR_ARG;
+  for (uint32_t k = 0; k < n; ++k) {
+    if (planes && planes[k] >= B) return DYMU_ERR_ARG;
+    if (weights && (!(weights[k] > 0.0) || !(weights[k] < __builtin_inf()))) return DYMU_ERR_ARG;
+    if (offsets && (!(offsets[k] >= 0.0) || !(offsets[k] < __builtin_inf()))) return DYMU_ERR_ARG;
+  }
+  const uint64_t stack_bytes = map_span(rows, ld, nx, sizeof(double));
+  if (ranges_overlap(d_out, map_span(ny, out_ld, nx, sizeof(double)), dT_stack, stack_bytes) ||
+      (d_arg && ranges_overlap(d_arg, map_span(ny, arg_ld, nx, sizeof(uint32_t)), dT_stack,
+                               stack_bytes)))
+    return DYMU_ERR_ARG;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  int rc = ensure_reduce(c);
+  if (rc) return rc;
+  // the previous call's copy has read the pinned list
+  if (c->red_copy_pending) HIPC(c, hipEventSynchronize(c->ev_red_copy));
+  c->red_copy_pending = false;
+  if (n > c->red_cap) {
+    const uint32_t cap = std::max<uint32_t>(n, std::max<uint32_t>(2 * c->red_cap, 64u));
+    if (c->h_red_terms) HIPC(c, hipHostFree(c->h_red_terms));
+    c->h_red_terms = nullptr;
+    park(c, c->d_red_terms);  // a queued kernel may still read it
+    c->d_red_terms = nullptr;
+    c->red_cap = 0;
+    HIPC(c, hipHostMalloc(&c->h_red_terms, sizeof(ReduceTerm) * cap, hipHostMallocDefault));
+    HIPC(c, hipMalloc(&c->d_red_terms, sizeof(ReduceTerm) * cap));
+    c->red_cap = cap;
+  }
+  const uint64_t plane_elems = (uint64_t)dymu_batch_plane_rows(ny) * ld;
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t p = planes ? planes[k] : k;
+    c->h_red_terms[k] = ReduceTerm{p * plane_elems, weights ? weights[k] : 1.0,
+                                   offsets ? offsets[k] : 0.0, p, 0u};
+  }
+  HIPC(c, hipMemcpyAsync(c->d_red_terms, c->h_red_terms, sizeof(ReduceTerm) * n,
+                         hipMemcpyHostToDevice, st));
+  HIPC(c, hipEventRecord(c->ev_red_copy, st));
+  c->red_copy_pending = true;
+  ReduceArgs a{};
+  a.T = dT_stack;
+  a.ld = ld;
+  a.nx = nx;
+  a.ny = ny;
+  a.terms = c->d_red_terms;
+  a.n = n;
+  a.flags = (weights ? 1u : 0u) | (offsets ? 2u : 0u);
+  a.out = d_out;
+  a.out_ld = out_ld;
+  a.arg = d_arg;
+  a.arg_ld = arg_ld;
+  a.part = summary ? c->d_red_part : nullptr;
+  a.walk = tile_walk(dT_stack, ld, nx, ny);
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>(a.walk.ntiles, c->red_blocks);
+  ReducePartial* d_sum = c->d_red_part + c->red_blocks;
+  c->red_timed = false;
+  HIPC(c, hipEventRecord(c->ev_red0, st));
+  HIPC(c, launch_batch_reduce(a, op, blocks, d_sum, st));
+  HIPC(c, hipEventRecord(c->ev_red1, st));
+  c->red_timed = true;
+  if (!summary) return DYMU_OK;
+  HIPC(c, hipMemcpyAsync(c->h_red_res, d_sum, sizeof(ReducePartial), hipMemcpyDeviceToHost, st));
+  HIPC(c, hipStreamSynchronize(st));
+  ReducePartial r;
+  std::memcpy(&r, c->h_red_res, sizeof r);
+  std::memset(summary, 0, sizeof *summary);
+  summary->min_value = r.v;
+  summary->n_finite = r.n;
+  summary->min_i = summary->min_j = summary->min_plane = 0xFFFFFFFFu;
+  if (r.cell != ~0ull) {
+    summary->min_i = (uint32_t)(r.cell % nx);
+    summary->min_j = (uint32_t)(r.cell / nx);
+    if (op != DYMU_REDUCE_SUM) summary->min_plane = r.arg;
+  }
+  return DYMU_OK;
+}
+
+int dymu_last_reduce_ms(dymu_ctx* c, double* ms) {
+  if (!c || !ms) return DYMU_ERR_ARG;
+  if (!c->red_timed) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipEventSynchronize(c->ev_red1));
+  float f = 0.0f;
+  HIPC(c, hipEventElapsedTime(&f, c->ev_red0, c->ev_red1));
+  *ms = (double)f;
+  return DYMU_OK;
+}
+
+int dymu_level_mask_device(dymu_ctx* c, const double* d_map, uint32_t nx, uint32_t ny, uint64_t ld,
+                           double bound, uint8_t* d_mask, uint64_t mask_ld, dymu_region* out,
+                           void* stream) {
+  if (!c || !d_map || !d_mask || nx == 0 || ny == 0 || ld < nx || mask_ld < nx)
+    return DYMU_ERR_ARG;
+  if (!(bound > -__builtin_inf()) || !(bound < __builtin_inf())) return DYMU_ERR_ARG;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  int rc = ensure_reduce(c);
+  if (rc) return rc;
+  const TileWalk walk = tile_walk(d_map, ld, nx, ny);
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>(walk.ntiles, c->red_blocks);
+  uint32_t* box = reinterpret_cast<uint32_t*>(c->d_red_part + c->red_blocks + 1);
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(box + 4);
+  if (out) {
+    HIPC(c, hipMemsetAsync(box, 0xFF, 2 * sizeof(uint32_t), st));
+    HIPC(c, hipMemsetAsync(box + 2, 0, 2 * sizeof(uint32_t) + sizeof(unsigned long long), st));
+  }
+  HIPC(c, launch_level_mask(d_map, ld, nx, ny, bound, d_mask, mask_ld, walk, blocks,
+                            out ? box : nullptr, cnt, st));
+  if (!out) return DYMU_OK;
+  char* h = static_cast<char*>(c->h_red_res) + 32;
+  HIPC(c, hipMemcpyAsync(h, box, 24, hipMemcpyDeviceToHost, st));
+  HIPC(c, hipStreamSynchronize(st));
+  uint32_t b[4];
+  unsigned long long m = 0;
+  std::memcpy(b, h, sizeof b);
+  std::memcpy(&m, h + 16, sizeof m);
+  std::memset(out, 0, sizeof *out);
+  out->n_range = m;
+  if (m == 0) {  // no cell at or below the bound
+    out->i0 = 1;
+    return DYMU_OK;
+  }
+  out->i0 = b[0], out->j0 = b[1], out->i1 = b[2], out->j1 = b[3];
   return DYMU_OK;
 }
 

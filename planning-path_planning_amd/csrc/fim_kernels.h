@@ -539,6 +539,49 @@ hipError_t launch_claimed_box(const uint32_t* tile_epoch, uint32_t ntiles, uint3
 hipError_t launch_inflate_speed(const double* F, const double* S, double* out, uint64_t ld,
                                 uint32_t nx, uint32_t ny, double risk_ratio, hipStream_t st);
 
+// ---- plane reduction and level mask (reduce_kernels.hip) ----
+// How 256-thread workgroups walk an nx x ny map at `base` with pitch ld two cells at a time:
+// a row takes 2^lanes_log2 lanes of a tile (256: `chunks` tiles per row), ntiles in all.
+struct TileWalk {
+  uint64_t ntiles;
+  uint32_t chunks, lanes_log2;
+};
+TileWalk tile_walk(const void* base, uint64_t ld, uint32_t nx, uint32_t ny);
+// one listed plane: its offset in the stack in elements (plane * P * ld), weight, offset
+struct ReduceTerm {
+  uint64_t off;
+  double w, o;
+  uint32_t plane, reserved;
+};
+// a workgroup's share of the summary, and the summary itself: the smallest value below +inf,
+// its cell j * nx + i (~0: none; the lowest among equals), the cells below +inf, the arg there
+struct ReducePartial {
+  double v;
+  uint64_t cell, n;
+  uint32_t arg, reserved;
+};
+struct ReduceArgs {
+  const double* T;          // the stack, plane 0
+  uint64_t ld;
+  uint32_t nx, ny;
+  const ReduceTerm* terms;  // device, n entries
+  uint32_t n, flags;        // flags: 1 weights, 2 offsets
+  double* out;
+  uint64_t out_ld;
+  uint32_t* arg;            // may be null
+  uint64_t arg_ld;
+  ReducePartial* part;      // one record per workgroup, or null: no summary
+  TileWalk walk;
+};
+// op: 0 sum, 1 max, 2 min.  With a.part the partials are folded into *d_sum by a second launch.
+hipError_t launch_batch_reduce(const ReduceArgs& a, int op, uint32_t blocks, ReducePartial* d_sum,
+                               hipStream_t st);
+// mask = map <= bound; box (null: none) = {min i, min j, max i, max j} from {~0, ~0, 0, 0} and
+// *cnt += the marked cells
+hipError_t launch_level_mask(const double* map, uint64_t ld, uint32_t nx, uint32_t ny, double bound,
+                             uint8_t* mask, uint64_t mask_ld, const TileWalk& walk, uint32_t blocks,
+                             uint32_t* box, unsigned long long* cnt, hipStream_t st);
+
 hipError_t launch_prio_init(const double* F, int64_t ld, int64_t nx, int64_t ny,
                            unsigned long long* keys, uint64_t nkeys, uint32_t* hist, uint64_t nhist,
                            unsigned long long* minkey, double* base, double* delta, double kappa,

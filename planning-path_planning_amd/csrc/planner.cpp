@@ -61,6 +61,7 @@ void release_engine(dymu_ctx*& ctx, double*& dF, double*& dT, void*& reg, uint64
 DyMuPathPlanner::~DyMuPathPlanner() {
   dropLabels();
   dropBatch();
+  dropCombined();
   dropRiskMaps();
   release_engine(ctx_, dF_, dT_, registered_, dcells_);
 }
@@ -72,6 +73,7 @@ void DyMuPathPlanner::setEngineOptions(const dymu_opts& o) {
   if (ctx_ && dT_ && blk_missing_) fetchAll();
   dropLabels();
   dropBatch();
+  dropCombined();
   dropRiskMaps();
   release_engine(ctx_, dF_, dT_, registered_, dcells_);
   dev_map_current_ = false;
@@ -115,6 +117,7 @@ bool DyMuPathPlanner::initGlobalLayer(double globalres, double localres, unsigne
   goals_.clear();
   dropLabels();
   dropBatch();
+  dropCombined();
   pend_ = false;
   current_path.clear();
   // a new grid: new device buffers and an empty total-cost map (every node
@@ -576,6 +579,7 @@ void DyMuPathPlanner::ensureEngine() {
     dF_ = dT_ = nullptr;
     dropLabels();
     dropBatch();
+    dropCombined();
     dropRiskMaps();
     dcells_ = 0;
     dev_map_current_ = false;
@@ -3092,6 +3096,7 @@ void DyMuPathPlanner::dropBatch() {
   batch_kind_ = 0;
   batch_level_ = kInf;
   bpend_ = false;
+  comb_valid_ = comb_arg_valid_ = false;  // the combined map was that of this stack
 }
 
 void DyMuPathPlanner::trackSpeedChanges(bool on) {
@@ -3251,6 +3256,7 @@ bool DyMuPathPlanner::refreshBatch() {
       bpend_ = false;
       batch_stats_ = st;
       batch_kind_ = 1;
+      comb_valid_ = comb_arg_valid_ = false;  // the stack was rewritten
       return true;
     }
   }
@@ -3269,6 +3275,138 @@ bool DyMuPathPlanner::copyBatchTotalCost(unsigned b, double* out, bool raw) {
   if (!raw)
     for (uint64_t k = 0; k < n; ++k)
       if (out[k] == kInf) out[k] = -1.0;
+  return true;
+}
+
+// ---- combining the planes of the batch (extension) ----
+
+// null with an engine that predates them: the methods below then return false
+#pragma weak dymu_batch_reduce_device
+#pragma weak dymu_level_mask_device
+#pragma weak dymu_last_reduce_ms
+
+void DyMuPathPlanner::dropCombined() {
+  if (ctx_) {
+    if (d_comb_) (void)dymu_device_free(ctx_, d_comb_);
+    if (d_comb_arg_) (void)dymu_device_free(ctx_, d_comb_arg_);
+    if (d_comb_mask_) (void)dymu_device_free(ctx_, d_comb_mask_);
+  }
+  d_comb_ = nullptr;
+  d_comb_arg_ = nullptr;
+  d_comb_mask_ = nullptr;
+  comb_valid_ = comb_arg_valid_ = false;
+}
+
+bool DyMuPathPlanner::combineOnDevice(int op, const std::vector<uint32_t>& planes,
+                                      const std::vector<double>& weights,
+                                      const std::vector<double>& offsets, dymu_reduce_summary& s) {
+  if (batch_goals_.empty() || !ctx_ || !dT_batch_ || !&dymu_batch_reduce_device) return false;
+  const size_t B = batch_goals_.size(), n = planes.empty() ? B : planes.size();
+  if (op < 0 || op > 2 || n > 65536 || (!weights.empty() && weights.size() != n) ||
+      (!offsets.empty() && offsets.size() != n))
+    return false;
+  for (uint32_t p : planes)
+    if (p >= B) return false;
+  for (double w : weights)
+    if (!(w > 0.0) || !(w < kInf)) return false;
+  for (double o : offsets)
+    if (!(o >= 0.0) || !(o < kInf)) return false;
+  if (!refreshBatch()) return false;
+  const uint64_t cells = (uint64_t)nx_ * ny_;
+  if (!d_comb_) {
+    void* q = nullptr;
+    if (dymu_device_alloc(ctx_, sizeof(double) * cells, &q) != DYMU_OK) return false;
+    d_comb_ = static_cast<double*>(q);
+  }
+  if (op != 0 && !d_comb_arg_) {
+    void* q = nullptr;
+    if (dymu_device_alloc(ctx_, sizeof(uint32_t) * cells, &q) != DYMU_OK) return false;
+    d_comb_arg_ = static_cast<uint32_t*>(q);
+  }
+  comb_valid_ = comb_arg_valid_ = false;
+  const int rc = dymu_batch_reduce_device(
+      ctx_, dT_batch_, nx_, ny_, (uint32_t)B, nx_, op, planes.empty() ? nullptr : planes.data(),
+      (uint32_t)n, weights.empty() ? nullptr : weights.data(),
+      offsets.empty() ? nullptr : offsets.data(), d_comb_, nx_, op != 0 ? d_comb_arg_ : nullptr,
+      nx_, &s, nullptr);
+  if (rc != DYMU_OK) return false;
+  comb_valid_ = true;
+  comb_arg_valid_ = op != 0;
+  double ms = 0.0;
+  if (&dymu_last_reduce_ms && dymu_last_reduce_ms(ctx_, &ms) == DYMU_OK) last_combine_ms_ = ms;
+  return true;
+}
+
+bool DyMuPathPlanner::combineTotalCostMaps(CombineOp op, const std::vector<uint32_t>& planes,
+                                           const std::vector<double>& weights,
+                                           const std::vector<double>& offsets,
+                                           CombineSummary* summary) {
+  dymu_reduce_summary s{};
+  if (!combineOnDevice((int)op, planes, weights, offsets, s)) return false;
+  if (summary) *summary = s;
+  return true;
+}
+
+bool DyMuPathPlanner::copyCombinedTotalCost(double* out, bool raw) {
+  // with a change pending the combined map is that of an older speed
+  if (!out || !ctx_ || !dT_batch_ || !d_comb_ || !comb_valid_ || bpend_) return false;
+  const uint64_t n = (uint64_t)nx_ * ny_;
+  if (dymu_memcpy_d2h(ctx_, out, d_comb_, sizeof(double) * n) != DYMU_OK)
+    throw std::runtime_error(std::string("dymu: combined map download failed: ") +
+                             dymu_last_error(ctx_));
+  if (!raw)
+    for (uint64_t k = 0; k < n; ++k)
+      if (out[k] == kInf) out[k] = -1.0;
+  return true;
+}
+
+bool DyMuPathPlanner::copyCombinedPlanes(uint32_t* out) {
+  if (!out || !ctx_ || !dT_batch_ || !d_comb_arg_ || !comb_valid_ || !comb_arg_valid_ || bpend_)
+    return false;
+  if (dymu_memcpy_d2h(ctx_, out, d_comb_arg_, sizeof(uint32_t) * (uint64_t)nx_ * ny_) != DYMU_OK)
+    throw std::runtime_error(std::string("dymu: plane map download failed: ") +
+                             dymu_last_error(ctx_));
+  return true;
+}
+
+bool DyMuPathPlanner::viaCorridor(unsigned a, unsigned b, double slack, uint8_t* mask,
+                                  CorridorInfo* info) {
+  if (!mask || a >= batch_goals_.size() || b >= batch_goals_.size() || !(slack >= 0.0) ||
+      !(slack < kInf) || !&dymu_level_mask_device)
+    return false;
+  dymu_reduce_summary s{};
+  if (!combineOnDevice(0, {a, b}, {}, {}, s) || s.n_finite == 0) return false;
+  const double bound = s.min_value * (1.0 + slack);
+  if (!(bound < kInf)) return false;
+  const uint64_t cells = (uint64_t)nx_ * ny_;
+  if (!d_comb_mask_) {
+    void* q = nullptr;
+    if (dymu_device_alloc(ctx_, cells, &q) != DYMU_OK) return false;
+    d_comb_mask_ = static_cast<uint8_t*>(q);
+  }
+  dymu_region box{};
+  if (dymu_level_mask_device(ctx_, d_comb_, nx_, ny_, nx_, bound, d_comb_mask_, nx_, &box,
+                             nullptr) != DYMU_OK)
+    return false;
+  if (dymu_memcpy_d2h(ctx_, mask, d_comb_mask_, cells) != DYMU_OK)
+    throw std::runtime_error(std::string("dymu: corridor mask download failed: ") +
+                             dymu_last_error(ctx_));
+  if (info)
+    *info = CorridorInfo{s.min_value, s.min_i, s.min_j, box.n_range, box.i0,
+                         box.j0,      box.i1,  box.j1,  bound};
+  return true;
+}
+
+bool DyMuPathPlanner::rendezvous(const std::vector<uint32_t>& planes,
+                                 const std::vector<double>& weights,
+                                 const std::vector<double>& offsets, bool minimax, unsigned* i,
+                                 unsigned* j, double* value) {
+  dymu_reduce_summary s{};
+  if (!combineOnDevice(minimax ? 1 : 0, planes, weights, offsets, s) || s.n_finite == 0)
+    return false;
+  if (i) *i = s.min_i;
+  if (j) *j = s.min_j;
+  if (value) *value = s.min_value;
   return true;
 }
 

@@ -597,6 +597,75 @@ int dymu_planner_last_batch_solve_kind(dymu_planner* p) {
   return p->pl.lastBatchSolveKind();
 }
 
+namespace {
+// the flat lists of the combine entries as the vectors the planner takes (planes NULL: all
+// maps, one weight / offset per map of the batch)
+struct CombineLists {
+  std::vector<uint32_t> planes;
+  std::vector<double> weights, offsets;
+  CombineLists(dymu_planner* p, const uint32_t* pl, uint32_t n_planes, const double* w,
+               const double* o) {
+    const size_t n = pl ? n_planes : p->pl.batchCount();
+    if (pl) planes.assign(pl, pl + n);
+    if (w) weights.assign(w, w + n);
+    if (o) offsets.assign(o, o + n);
+  }
+};
+}  // namespace
+
+int dymu_planner_combine_total_cost_maps(dymu_planner* p, int op, const uint32_t* planes,
+                                         uint32_t n_planes, const double* weights,
+                                         const double* offsets, dymu_reduce_summary* summary) {
+  if (!p || op < 0 || op > 2 || (planes && n_planes == 0)) return DYMU_ERR_ARG;
+  return guarded([&] {
+    const CombineLists l(p, planes, n_planes, weights, offsets);
+    return (int)p->pl.combineTotalCostMaps((DyMuPathPlanner::CombineOp)op, l.planes, l.weights,
+                                           l.offsets, summary);
+  });
+}
+
+int dymu_planner_copy_combined_total_cost(dymu_planner* p, double* out, int raw) {
+  if (!p || !out) return DYMU_ERR_ARG;
+  return guarded([&] { return (int)p->pl.copyCombinedTotalCost(out, raw != 0); });
+}
+
+int dymu_planner_copy_combined_planes(dymu_planner* p, uint32_t* out) {
+  if (!p || !out) return DYMU_ERR_ARG;
+  return guarded([&] { return (int)p->pl.copyCombinedPlanes(out); });
+}
+
+int dymu_planner_via_corridor(dymu_planner* p, uint32_t a, uint32_t b, double slack, uint8_t* mask,
+                              dymu_corridor_info* info) {
+  if (!p || !mask || !info) return DYMU_ERR_ARG;
+  return guarded([&] {
+    DyMuPathPlanner::CorridorInfo ci{};
+    if (!p->pl.viaCorridor(a, b, slack, mask, &ci)) return 0;
+    *info = dymu_corridor_info{ci.D_min, ci.min_i, ci.min_j, ci.count, ci.i0,
+                               ci.j0,    ci.i1,    ci.j1,    ci.bound};
+    return 1;
+  });
+}
+
+int dymu_planner_rendezvous(dymu_planner* p, const uint32_t* planes, uint32_t n_planes,
+                            const double* weights, const double* offsets, int minimax, uint32_t* i,
+                            uint32_t* j, double* value) {
+  if (!p || !i || !j || !value || (planes && n_planes == 0)) return DYMU_ERR_ARG;
+  return guarded([&] {
+    const CombineLists l(p, planes, n_planes, weights, offsets);
+    unsigned ci = 0, cj = 0;
+    double v = 0.0;
+    if (!p->pl.rendezvous(l.planes, l.weights, l.offsets, minimax != 0, &ci, &cj, &v)) return 0;
+    *i = ci, *j = cj, *value = v;
+    return 1;
+  });
+}
+
+int dymu_planner_last_combine_kernel_ms(dymu_planner* p, double* ms) {
+  if (!p || !ms) return DYMU_ERR_ARG;
+  *ms = p->pl.lastCombineKernelMs();
+  return DYMU_OK;
+}
+
 int dymu_planner_set_goals(dymu_planner* p, const double* xyzh, const double* offsets, int n) {
   if (!p || !xyzh || n <= 0) return DYMU_ERR_ARG;
   return guarded([&] {

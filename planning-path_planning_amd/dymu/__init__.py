@@ -96,6 +96,32 @@ class DymuRegion(ctypes.Structure):
                 ("j1", ctypes.c_uint32), ("n_range", ctypes.c_uint64), ("r_const", ctypes.c_double)]
 
 
+class DymuReduceSummary(ctypes.Structure):
+    """dymu_reduce_summary (include/dymu_fim.h)."""
+    _fields_ = [("min_value", ctypes.c_double), ("min_i", ctypes.c_uint32),
+                ("min_j", ctypes.c_uint32), ("min_plane", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("n_finite", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {"min_value": self.min_value, "min_i": self.min_i, "min_j": self.min_j,
+                "min_plane": self.min_plane, "n_finite": self.n_finite}
+
+
+class DymuCorridorInfo(ctypes.Structure):
+    """dymu_corridor_info (include/dymu_planner.h)."""
+    _fields_ = [("d_min", ctypes.c_double), ("min_i", ctypes.c_uint32), ("min_j", ctypes.c_uint32),
+                ("count", ctypes.c_uint64), ("i0", ctypes.c_uint32), ("j0", ctypes.c_uint32),
+                ("i1", ctypes.c_uint32), ("j1", ctypes.c_uint32), ("bound", ctypes.c_double)]
+
+
+REDUCE_SUM, REDUCE_MAX, REDUCE_MIN = 0, 1, 2
+_REDUCE_OPS = {"sum": REDUCE_SUM, "max": REDUCE_MAX, "min": REDUCE_MIN}
+
+
+def _reduce_op(op) -> int:
+    return _REDUCE_OPS[op.lower()] if isinstance(op, str) else int(op)
+
+
 class DymuStats(ctypes.Structure):
     _fields_ = [
         ("passes", ctypes.c_uint64),
@@ -261,6 +287,12 @@ FIM_SYMBOLS = {
                                             ctypes.POINTER(DymuStats)]),
     "dymu_inflate_speed_device": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, ctypes.c_double,
                                          _vp]),
+    "dymu_batch_reduce_device": (_i32, [_vp, _vp, _u32, _u32, _u32, _u64, _i32, _vp, _u32, _vp, _vp,
+                                        _vp, _u64, _vp, _u64, ctypes.POINTER(DymuReduceSummary),
+                                        _vp]),
+    "dymu_last_reduce_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_level_mask_device": (_i32, [_vp, _vp, _u32, _u32, _u64, ctypes.c_double, _vp, _u64,
+                                      ctypes.POINTER(DymuRegion), _vp]),
     "dymu_device_alloc_cached": (_i32, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "dymu_memcpy2d_d2h": (_i32, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
                                  ctypes.c_size_t, ctypes.c_size_t]),
@@ -771,6 +803,53 @@ class Engine:
                 self.free(p)
         return out
 
+    # -- plane reduction and level mask --
+    def batch_reduce(self, dT_stack: int, nx: int, ny: int, B: int, ld: int, op, planes=None,
+                     weights=None, offsets=None, d_out: int = 0, out_ld: int = 0, d_arg: int = 0,
+                     arg_ld: int = 0, summary: bool = True, stream: int = 0):
+        """dymu_batch_reduce_device: d_out = the fold `op` ("sum" / "max" / "min" or 0 / 1 / 2)
+        of every cell over the listed planes of the stack (None: all), each optionally
+        weighted and offset; d_arg (MAX / MIN, optional) the plane that gave the cell.
+        Returns the summary of d_out as a dict (the call then synchronises), or None with
+        summary=False (asynchronous)."""
+        pl = None if planes is None else np.ascontiguousarray(planes, dtype=np.uint32).ravel()
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        o = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.float64).ravel()
+        n = B if pl is None else len(pl)
+        for a in (w, o):
+            if a is not None and len(a) != n:
+                raise DymuError(-1, "one weight / offset per listed plane")
+        # an empty list stays a list (n_planes = 0 with a list is an argument error)
+        keep = np.zeros(1, dtype=np.uint32) if pl is not None and len(pl) == 0 else pl
+        s = DymuReduceSummary()
+        _check(self._lib.dymu_batch_reduce_device(
+            self.ctx, dT_stack, nx, ny, B, ld, _reduce_op(op),
+            None if keep is None else keep.ctypes.data, 0 if pl is None else len(pl),
+            None if w is None else w.ctypes.data, None if o is None else o.ctypes.data,
+            d_out or None, out_ld, d_arg or None, arg_ld, ctypes.byref(s) if summary else None,
+            stream or None), self.ctx)
+        return s.as_dict() if summary else None
+
+    def last_reduce_ms(self) -> float:
+        """Device time (HIP events, ms) of the last batch_reduce's kernels."""
+        v = ctypes.c_double()
+        _check(self._lib.dymu_last_reduce_ms(self.ctx, ctypes.byref(v)), self.ctx)
+        return v.value
+
+    def level_mask(self, d_map: int, nx: int, ny: int, ld: int, bound: float, d_mask: int,
+                   mask_ld: int, region: bool = True, stream: int = 0):
+        """dymu_level_mask_device: d_mask (bytes) = d_map <= bound; returns {"box": (i0, j0,
+        i1, j1) inclusive, i0 > i1 when empty, "n_range": marked cells} (synchronises), or
+        None with region=False (asynchronous)."""
+        r = DymuRegion()
+        _check(self._lib.dymu_level_mask_device(self.ctx, d_map or None, nx, ny, ld, bound,
+                                                d_mask or None, mask_ld,
+                                                ctypes.byref(r) if region else None,
+                                                stream or None), self.ctx)
+        if not region:
+            return None
+        return {"box": (r.i0, r.j0, r.i1, r.j1), "n_range": r.n_range, "r_const": r.r_const}
+
     def alloc(self, nbytes: int) -> int:
         p = _vp()
         _check(self._lib.dymu_device_alloc(self.ctx, nbytes, ctypes.byref(p)), self.ctx)
@@ -1045,6 +1124,15 @@ PLANNER_SYMBOLS = {
     "dymu_planner_last_batch_stats": (_i32, [_vp, ctypes.POINTER(DymuStats)]),
     "dymu_planner_track_speed_changes": (_i32, [_vp, _i32]),
     "dymu_planner_last_batch_solve_kind": (_i32, [_vp]),
+    "dymu_planner_combine_total_cost_maps": (_i32, [_vp, _i32, _vp, _u32, _vp, _vp,
+                                                    ctypes.POINTER(DymuReduceSummary)]),
+    "dymu_planner_copy_combined_total_cost": (_i32, [_vp, _vp, _i32]),
+    "dymu_planner_copy_combined_planes": (_i32, [_vp, _vp]),
+    "dymu_planner_via_corridor": (_i32, [_vp, _u32, _u32, ctypes.c_double, _vp,
+                                         ctypes.POINTER(DymuCorridorInfo)]),
+    "dymu_planner_rendezvous": (_i32, [_vp, _vp, _u32, _vp, _vp, _i32, ctypes.POINTER(_u32),
+                                       ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_double)]),
+    "dymu_planner_last_combine_kernel_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "dymu_planner_get_path_stats": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp]),
     "dymu_planner_get_path_stats_to": (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp]),
     "dymu_planner_goal_cell": (_i32, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
@@ -1335,6 +1423,98 @@ class Planner:
         if b < 0 or not _b(self._lib.dymu_planner_copy_batch_total_cost(self.h, b, out, int(raw))):
             return None
         return out
+
+    # -- combining the maps of the batch --
+    def _combine_lists(self, planes, weights, offsets):
+        """The lists as arrays (None stays None), or False where their lengths do not fit."""
+        pl = None if planes is None else np.ascontiguousarray(planes, dtype=np.int64).ravel()
+        n = self.batchCount() if pl is None else len(pl)
+        if n == 0 or (pl is not None and ((pl < 0) | (pl > 0xFFFFFFFF)).any()):
+            return False
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        o = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.float64).ravel()
+        if any(a is not None and len(a) != n for a in (w, o)):
+            return False
+        return (None if pl is None else pl.astype(np.uint32)), w, o, n
+
+    @staticmethod
+    def _ptr(a):
+        return None if a is None else a.ctypes.data
+
+    def combineTotalCostMaps(self, op, planes=None, weights=None, offsets=None):
+        """The maps of the batch combined cell by cell on the device: op ("sum" / "max" /
+        "min" or 0 / 1 / 2) over the listed maps (None: all), each optionally weighted and
+        offset.  Returns the summary of the combined map as a dict (min_value, min_i, min_j,
+        min_plane, n_finite), or False (nothing changed) without a batch or a device engine
+        and for a bad list."""
+        l = self._combine_lists(planes, weights, offsets)
+        if l is False:
+            return False
+        pl, w, o, n = l
+        s = DymuReduceSummary()
+        if not _b(self._lib.dymu_planner_combine_total_cost_maps(
+                self.h, _reduce_op(op), self._ptr(pl), n if pl is not None else 0, self._ptr(w),
+                self._ptr(o), ctypes.byref(s))):
+            return False
+        return s.as_dict()
+
+    def _out(self, out, dtype):
+        """A caller's C-contiguous [ny, nx] array of dtype to fill, or a fresh one."""
+        if out is None:
+            return np.empty((self.ny, self.nx), dtype=dtype)
+        if out.shape != (self.ny, self.nx) or out.dtype != dtype or not out.flags.c_contiguous:
+            raise ValueError(f"expected a C-contiguous [{self.ny}, {self.nx}] {dtype} array")
+        return out
+
+    def combinedTotalCost(self, raw: bool = True, out=None):
+        """The combined map, [ny, nx] (+inf; raw=False: -1), or False once it no longer
+        belongs to the held batch.  out: an array to fill instead of a new one."""
+        out = self._out(out, np.float64)
+        if not _b(self._lib.dymu_planner_copy_combined_total_cost(self.h, out.ctypes.data,
+                                                                  int(raw))):
+            return False
+        return out
+
+    def combinedPlanes(self, out=None):
+        """The plane that gave each cell of the last MAX / MIN, [ny, nx] uint32 (LABEL_NONE:
+        a MIN cell no plane reaches), or False.  out: an array to fill instead of a new one."""
+        out = self._out(out, np.uint32)
+        if not _b(self._lib.dymu_planner_copy_combined_planes(self.h, out.ctypes.data)):
+            return False
+        return out
+
+    def viaCorridor(self, a: int, b: int, slack: float, mask=None):
+        """(mask [ny, nx] uint8, info dict) of the corridor between goals a and b: the cells
+        whose via cost T_a + T_b is within (1 + slack) of its minimum D_min; or False (a
+        caller's mask is then left as it was)."""
+        if a < 0 or b < 0 or a > 0xFFFFFFFF or b > 0xFFFFFFFF:
+            return False
+        mask = self._out(mask, np.uint8)
+        ci = DymuCorridorInfo()
+        if not _b(self._lib.dymu_planner_via_corridor(self.h, a, b, float(slack), mask.ctypes.data,
+                                                      ctypes.byref(ci))):
+            return False
+        return mask, {"D_min": ci.d_min, "cell": (ci.min_i, ci.min_j), "count": ci.count,
+                      "box": (ci.i0, ci.j0, ci.i1, ci.j1), "bound": ci.bound}
+
+    def rendezvous(self, planes=None, weights=None, offsets=None, minimax: bool = True):
+        """(i, j, value): the cell minimising the MAX (minimax) or the SUM of the listed maps,
+        the lowest row-major one among equals; False when there is none."""
+        l = self._combine_lists(planes, weights, offsets)
+        if l is False:
+            return False
+        pl, w, o, n = l
+        i, j, v = _u32(), _u32(), ctypes.c_double()
+        if not _b(self._lib.dymu_planner_rendezvous(
+                self.h, self._ptr(pl), n if pl is not None else 0, self._ptr(w), self._ptr(o),
+                int(bool(minimax)), ctypes.byref(i), ctypes.byref(j), ctypes.byref(v))):
+            return False
+        return i.value, j.value, v.value
+
+    def lastCombineKernelMs(self) -> float:
+        v = ctypes.c_double()
+        _check(self._lib.dymu_planner_last_combine_kernel_ms(self.h, ctypes.byref(v)))
+        return v.value
 
     @staticmethod
     def _xy(points) -> np.ndarray:
