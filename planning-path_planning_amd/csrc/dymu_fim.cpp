@@ -548,6 +548,32 @@ int dom_begin(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t n
   return DYMU_OK;
 }
 
+template <class A>
+auto bind_hist(A& a, uint32_t* hist, int) -> decltype((void)(a.hist = hist)) {
+  a.hist = hist;
+}
+template <class A>
+void bind_hist(A&, uint32_t*, long) {}  // PlaneUpdateArgs: list 0 is re-binned, no histogram
+
+// List 0 of the live domain in the argument struct of a seeding kernel (UpdateArgs,
+// SeedArgs, PlaneUpdateArgs, MaskSeedArgs): the list, its counters and stamps, the tile
+// geometry and, for the priority kernels, the keys and the histogram.  The epoch of list 0
+// is eb + 1: dom_launch stamps eb + p + 2 for list p + 1, which pass p fills.
+template <class A>
+void bind_list0(dymu_ctx* c, A& a) {
+  auto& D = c->dom;
+  a.list = D.lists[0];
+  a.counts = D.counts[0];
+  a.shard_cap = D.ntiles;
+  a.tile_epoch = c->d_tile_epoch;
+  a.epoch = D.eb + 1;
+  a.tw = (uint32_t)tile_w(D.variant);
+  a.th = (uint32_t)tile_h(D.variant);
+  a.ntx = (uint32_t)D.a.ntx;
+  a.keys = is_prio(D.variant) ? prio_keys(c, 0) : nullptr;
+  bind_hist(a, is_prio(D.variant) ? prio_hist(c, 0) : nullptr, 0);
+}
+
 // report_seq != 0: the batch's first pass posts (report_seq, tiles pending) to the mailbox
 int dom_launch(dymu_ctx* c, uint64_t K, hipStream_t st, uint32_t report_seq = 0) {
   auto& D = c->dom;
@@ -838,39 +864,57 @@ int dom_finish(dymu_ctx* c, hipStream_t st, dymu_stats* stats, double ms) {
   return DYMU_OK;
 }
 
-// passes until no tile is queued, then statistics (the domain must be live).
-// probe (priority kernels only): also stop as soon as the probe cells are final --
-// every queued tile's key exceeds their largest value -- and return that value in
-// *t_probe (+inf if a probe cell is unreachable; then the solve runs to the end).
-int converge(dymu_ctx* c, hipStream_t st, dymu_stats* stats, const ProbeCells* probe = nullptr,
-             double* t_probe = nullptr) {
-  HIPC(c, hipEventRecord(c->ev0, st));
-  uint64_t K = c->opts.passes_per_check > 0 ? (uint64_t)c->opts.passes_per_check : c->first_batch;
+// the time from event a to event b, once b has passed
+int event_ms(dymu_ctx* c, hipEvent_t a, hipEvent_t b, double* ms) {
+  HIPC(c, hipEventSynchronize(b));
+  float f = 0.f;
+  HIPC(c, hipEventElapsedTime(&f, a, b));
+  *ms = (double)f;
+  return DYMU_OK;
+}
+
+// a dymu_last_*_ms getter: the time between the event pair of the last call of its kind
+int elapsed_ms(dymu_ctx* c, bool dymu_ctx::*timed, hipEvent_t dymu_ctx::*ev_a,
+               hipEvent_t dymu_ctx::*ev_b, double* ms) {
+  if (!c || !ms) return DYMU_ERR_ARG;
+  if (!(c->*timed)) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  return event_ms(c, c->*ev_a, c->*ev_b, ms);
+}
+
+// the end of a timed call: ev1 behind the work queued so far, the time since ev0, and the
+// live domain's statistics
+int finish_timed(dymu_ctx* c, hipStream_t st, dymu_stats* stats) {
+  HIPC(c, hipEventRecord(c->ev1, st));
+  double ms = 0.0;
+  const int rc = event_ms(c, c->ev0, c->ev1, &ms);
+  return rc ? rc : dom_finish(c, st, stats, ms);
+}
+
+// The host-checked convergence loop (the domain must be live): K passes, queue_test()
+// puts the caller's stop test on the stream behind them, dom_pending synchronises, and
+// stop(pending) -- with the words the test read back into c->h_probe -- decides.  Then the
+// statistics.  Any error retires the domain.
+// K: passes_per_check when given; else first_batch passes before the first check, then
+// `later` between checks, or doubling up to 64 for later = kDoubling.
+// record_ev0 = false: the caller has recorded ev0 before its preparation.
+constexpr uint64_t kDoubling = 0;
+template <class Queue, class Stop>
+int converge_checked(dymu_ctx* c, hipStream_t st, dymu_stats* stats, uint64_t later,
+                     bool record_ev0, const char* what, Queue queue_test, Stop stop) {
+  if (record_ev0) HIPC(c, hipEventRecord(c->ev0, st));
+  const bool fixed = c->opts.passes_per_check > 0;
+  uint64_t K = fixed ? (uint64_t)c->opts.passes_per_check : c->first_batch;
   for (;;) {
     int rc = dom_launch(c, K, st);
-    if (rc == DYMU_OK && probe) {
-      auto& D = c->dom;
-      const hipError_t e = launch_probe(D.a.T, D.a.ld, *probe, prio_minkey(c, D.p % 3),
-                                        c->d_scratch + 2, st);
-      rc = e == hipSuccess ? DYMU_OK : fail_hip(c, e, "launch_probe");
-      if (rc == DYMU_OK) {
-        const hipError_t e2 = hipMemcpyAsync(c->h_probe, c->d_scratch + 2,
-                                             2 * sizeof(unsigned long long),
-                                             hipMemcpyDeviceToHost, st);
-        if (e2 != hipSuccess) rc = fail_hip(c, e2, "probe read-back");
-      }
+    if (rc == DYMU_OK) {
+      const hipError_t e = queue_test();
+      if (e != hipSuccess) rc = fail_hip(c, e, what);
     }
     if (rc == DYMU_OK) {
       uint64_t pending = 0;
       rc = dom_pending(c, st, &pending);
-      if (rc == DYMU_OK && probe) {
-        double tmax, kmin;
-        std::memcpy(&tmax, &c->h_probe[0], sizeof tmax);
-        std::memcpy(&kmin, &c->h_probe[1], sizeof kmin);
-        *t_probe = tmax;
-        if (kmin > tmax) break;  // no pass can lower a value <= tmax any more
-      }
-      if (rc == DYMU_OK && pending == 0) break;
+      if (rc == DYMU_OK && stop(pending)) break;
     }
     if (rc == DYMU_OK && c->dom.p >= c->dom.max_passes) {
       c->last_error = "pass cap reached before convergence";
@@ -880,13 +924,38 @@ int converge(dymu_ctx* c, hipStream_t st, dymu_stats* stats, const ProbeCells* p
       dom_retire(c);
       return rc;
     }
-    if (c->opts.passes_per_check <= 0) K = std::min<uint64_t>(K * 2, 64);
+    if (!fixed) K = later == kDoubling ? std::min<uint64_t>(K * 2, 64) : later;
   }
-  HIPC(c, hipEventRecord(c->ev1, st));
-  HIPC(c, hipEventSynchronize(c->ev1));
-  float ms = 0.f;
-  HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  return dom_finish(c, st, stats, ms);
+  return finish_timed(c, st, stats);
+}
+
+// passes until no tile is queued, then statistics.
+// probe (priority kernels only): also stop as soon as the probe cells are final --
+// every queued tile's key exceeds their largest value -- and return that value in
+// *t_probe (+inf if a probe cell is unreachable; then the solve runs to the end).
+int converge(dymu_ctx* c, hipStream_t st, dymu_stats* stats, const ProbeCells* probe = nullptr,
+             double* t_probe = nullptr) {
+  auto queue_test = [&]() -> hipError_t {
+    if (!probe) return hipSuccess;
+    auto& D = c->dom;
+    const hipError_t e =
+        launch_probe(D.a.T, D.a.ld, *probe, prio_minkey(c, D.p % 3), c->d_scratch + 2, st);
+    if (e != hipSuccess) return e;
+    return hipMemcpyAsync(c->h_probe, c->d_scratch + 2, 2 * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, st);
+  };
+  auto stop = [&](uint64_t pending) {
+    if (probe) {
+      double tmax, kmin;
+      std::memcpy(&tmax, &c->h_probe[0], sizeof tmax);
+      std::memcpy(&kmin, &c->h_probe[1], sizeof kmin);
+      *t_probe = tmax;
+      if (kmin > tmax) return true;  // no pass can lower a value <= tmax any more
+    }
+    return pending == 0;
+  };
+  return converge_checked(c, st, stats, kDoubling, /*record_ev0=*/true, "start probe", queue_test,
+                          stop);
 }
 
 // Wait for the mailbox post seq (converge_pipelined, converge_stream).  The host spins on
@@ -959,11 +1028,7 @@ int converge_pipelined(dymu_ctx* c, hipStream_t st, dymu_stats* stats) {
     (void)hipStreamSynchronize(st);
     return rc;
   }
-  HIPC(c, hipEventRecord(c->ev1, st));
-  HIPC(c, hipEventSynchronize(c->ev1));
-  float ms = 0.f;
-  HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  return dom_finish(c, st, stats, ms);
+  return finish_timed(c, st, stats);
 }
 
 // Streaming variant (DYMU_PIPELINE=2): every pass posts, and the host keeps
@@ -1107,18 +1172,16 @@ int resolve_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_
   u.gi = gi;
   u.gj = gj;
   u.theta_bits = theta;
-  u.shard_cap = D.ntiles;
-  u.tile_epoch = c->d_tile_epoch;
   const bool raise = !decrease_only && c->raise;
   if (raise) {
     // the raise passes use the domain's lists and epochs (plain FIM lists, 16x16 tiles)
     const uint32_t ntx16 = (nx + 15) / 16, nty16 = (ny + 15) / 16;
-    u.list = D.lists[0];
-    u.counts = D.counts[0];
-    u.epoch = D.eb + 1;
+    bind_list0(c, u);
     u.tw = u.th = 16;
     u.ntx = ntx16;
-    HIPC(c, launch_seed_window(u, i0, j0, i0 + w, j0 + h, st));  // no keys: u.keys null
+    u.keys = nullptr;  // no keys, no histogram: the raise front has no order
+    u.hist = nullptr;
+    HIPC(c, launch_seed_window(u, i0, j0, i0 + w, j0 + h, st));
     unsigned long long* rst = c->d_scratch + 5;  // [visits, cells]
     HIPC(c, hipMemsetAsync(rst, 0, 2 * sizeof(unsigned long long), st));
     RaiseArgs ra{};
@@ -1171,18 +1234,8 @@ int resolve_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_
     // a fresh domain for the re-solve: epochs above every raise epoch (dom_retire)
     rc = dom_begin(c, dF, dT, nx, ny, ld, 0, 0, -1, -1, st, /*cold=*/false);
     if (rc) return rc;
-    u.shard_cap = D.ntiles;
   }
-  u.list = D.lists[0];
-  u.counts = D.counts[0];
-  u.epoch = D.eb + 1;  // the epoch of list 0 (dom_launch: eb + p + 2 for list p + 1)
-  u.tw = (uint32_t)tile_w(D.variant);
-  u.th = (uint32_t)tile_h(D.variant);
-  u.ntx = (uint32_t)D.a.ntx;
-  if (is_prio(D.variant)) {
-    u.keys = prio_keys(c, 0);
-    u.hist = prio_hist(c, 0);
-  }
+  bind_list0(c, u);
   if (raise) {  // the cone's boundary, then the window (decreases inside it)
     uint32_t* hist0 = u.hist;
     u.hist = nullptr;  // binned below from the final keys (they differ per tile)
@@ -1395,14 +1448,12 @@ int update_planes_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, u
                        bool decrease_only, hipStream_t st, dymu_stats* stats) {
   std::memset(c->last_update, 0, sizeof c->last_update);
   const uint32_t rows = planes * P;  // fits (callers)
-  HIPC(c, hipStreamSynchronize(st));  // no earlier kernel still uses the transfer buffer
   const uint64_t seed_bytes = sizeof(GoalSeed) * (uint64_t)n_seeds;
-  int rc = ensure_xfer(c, seed_bytes + sizeof(BatchWindow) * (uint64_t)n_wins);
+  const GoalSeed* d_seeds = nullptr;  // on stacked rows, checked by the callers already
+  int rc = stage_seeds(c, nx, rows, seeds, n_seeds, st, &d_seeds, nullptr,
+                       sizeof(BatchWindow) * (uint64_t)n_wins);
   if (rc) return rc;
-  GoalSeed* hs = static_cast<GoalSeed*>(c->h_xfer);
-  for (uint32_t k = 0; k < n_seeds; ++k) hs[k] = GoalSeed{seeds[k].i, seeds[k].j, seeds[k].t0 + 0.0};
   std::memcpy(static_cast<char*>(c->h_xfer) + seed_bytes, wins, sizeof(BatchWindow) * (size_t)n_wins);
-  const GoalSeed* d_seeds = static_cast<const GoalSeed*>(c->d_xfer);
   const BatchWindow* d_wins =
       reinterpret_cast<const BatchWindow*>(static_cast<const char*>(c->d_xfer) + seed_bytes);
   uint64_t max_cells = 0;
@@ -1431,15 +1482,7 @@ int update_planes_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, u
   u.theta = c->d_theta;
   u.win = d_wins;
   u.n_win = n_wins;
-  u.list = D.lists[0];
-  u.counts = D.counts[0];
-  u.shard_cap = D.ntiles;
-  u.tile_epoch = c->d_tile_epoch;
-  u.epoch = D.eb + 1;  // the epoch of list 0 (dom_launch: eb + p + 2 for list p + 1)
-  u.tw = (uint32_t)tile_w(D.variant);
-  u.th = (uint32_t)tile_h(D.variant);
-  u.ntx = (uint32_t)D.a.ntx;
-  u.keys = is_prio(D.variant) ? prio_keys(c, 0) : nullptr;
+  bind_list0(c, u);
   u.n_reset = n_reset;
   hipError_t e = launch_fill_u64(c->d_theta, planes, 0x7FF0000000000000ull, st);  // +inf bits
   if (e == hipSuccess) e = launch_store_u64(n_reset, 0ull, st);
@@ -1455,15 +1498,8 @@ int update_planes_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, u
     a.ld = (int64_t)ld;
     a.nx = nx;
     a.ny = rows;
-    a.tw = u.tw;
-    a.th = u.th;
-    a.ntx = u.ntx;
-    a.list = u.list;
-    a.counts = u.counts;
-    a.shard_cap = u.shard_cap;
-    a.tile_epoch = u.tile_epoch;
-    a.epoch = u.epoch;
-    a.keys = u.keys;  // no histogram here: list 0 is binned below, the edge columns rebuilt
+    bind_list0(c, a);
+    a.hist = nullptr;  // no histogram here: list 0 is binned below, the edge columns rebuilt
     if (e == hipSuccess) e = launch_seed_goals(a, st);
   }
   if (e == hipSuccess && is_prio(D.variant)) {
@@ -2015,14 +2051,7 @@ int dymu_path_stats_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t 
 }
 
 int dymu_last_path_stats_ms(dymu_ctx* c, double* ms) {
-  if (!c || !ms) return DYMU_ERR_ARG;
-  if (!c->pstat_timed) return DYMU_ERR_STATE;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipEventSynchronize(c->ev_pstat1));
-  float f = 0.0f;
-  HIPC(c, hipEventElapsedTime(&f, c->ev_pstat0, c->ev_pstat1));
-  *ms = (double)f;
-  return DYMU_OK;
+  return elapsed_ms(c, &dymu_ctx::pstat_timed, &dymu_ctx::ev_pstat0, &dymu_ctx::ev_pstat1, ms);
 }
 
 int dymu_solve_seeds_device(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t ny,
@@ -2158,45 +2187,22 @@ int dymu_solve_seeds_until_device(dymu_ctx* c, const double* dF, double* dT, uin
 /* ---- obstacle clearance field and risk-inflated speed ---- */
 
 namespace {
-// converge_targets with a constant level instead of a probe over target cells: K passes,
-// the key bound read back with the counters, compare.  Ends at the first check at which
-// every queued tile's key exceeds `level` (no pass can lower a value at or below it any
-// more), or with nothing queued.  The caller has recorded ev0 before its preparation.
+// converge_targets with a constant level instead of a probe over target cells: the key
+// bound read back with the counters, compare.  Ends at the first check at which every
+// queued tile's key exceeds `level` (no pass can lower a value at or below it any more),
+// or with nothing queued.  The caller has recorded ev0 before its preparation.
 int converge_level(dymu_ctx* c, hipStream_t st, dymu_stats* stats, double level) {
-  const bool fixed = c->opts.passes_per_check > 0;
-  uint64_t K = fixed ? (uint64_t)c->opts.passes_per_check : c->first_batch;
-  for (;;) {
-    int rc = dom_launch(c, K, st);
-    if (rc == DYMU_OK) {
-      const hipError_t e =
-          hipMemcpyAsync(c->h_probe + 1, prio_minkey(c, c->dom.p % 3), sizeof(unsigned long long),
-                         hipMemcpyDeviceToHost, st);
-      if (e != hipSuccess) rc = fail_hip(c, e, "key bound read-back");
-    }
-    if (rc == DYMU_OK) {
-      uint64_t pending = 0;
-      rc = dom_pending(c, st, &pending);  // synchronises: the key bound is here too
-      if (rc == DYMU_OK) {
-        double kmin;
-        std::memcpy(&kmin, &c->h_probe[1], sizeof kmin);
-        if (kmin > level || pending == 0) break;
-      }
-    }
-    if (rc == DYMU_OK && c->dom.p >= c->dom.max_passes) {
-      c->last_error = "pass cap reached before convergence";
-      rc = DYMU_ERR_NOT_CONVERGED;
-    }
-    if (rc) {
-      dom_retire(c);
-      return rc;
-    }
-    if (!fixed) K = c->until_batch;
-  }
-  HIPC(c, hipEventRecord(c->ev1, st));
-  HIPC(c, hipEventSynchronize(c->ev1));
-  float ms = 0.f;
-  HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  return dom_finish(c, st, stats, ms);
+  auto queue_test = [&]() {
+    return hipMemcpyAsync(c->h_probe + 1, prio_minkey(c, c->dom.p % 3),
+                          sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+  };
+  auto stop = [&](uint64_t pending) {
+    double kmin;
+    std::memcpy(&kmin, &c->h_probe[1], sizeof kmin);
+    return kmin > level || pending == 0;
+  };
+  return converge_checked(c, st, stats, c->until_batch, /*record_ev0=*/false,
+                          "key bound read-back", queue_test, stop);
 }
 }  // namespace
 
@@ -2217,16 +2223,7 @@ int dymu_clearance_device(dymu_ctx* c, const double* dF, double* dW, double* dS,
   a.ld = (int64_t)ld;
   a.nx = nx;
   a.ny = ny;
-  a.tw = (uint32_t)tile_w(D.variant);
-  a.th = (uint32_t)tile_h(D.variant);
-  a.ntx = (uint32_t)D.a.ntx;
-  a.list = D.lists[0];
-  a.counts = D.counts[0];
-  a.shard_cap = D.ntiles;
-  a.tile_epoch = c->d_tile_epoch;
-  a.epoch = D.eb + 1;  // the epoch of list 0 (solve_seeds_core)
-  a.keys = prio_keys(c, 0);
-  a.hist = prio_hist(c, 0);
+  bind_list0(c, a);  // a priority kernel (need_keys): keys and histogram
   a.ec = D.a.ec;
   a.n_obst = c->d_scratch + 4;
   // list 0's smallest key and histogram origin: +0.0, the value of every seed
@@ -2243,13 +2240,8 @@ int dymu_clearance_device(dymu_ctx* c, const double* dF, double* dW, double* dS,
     dom_retire(c);
     return fail_hip(c, e, "obstacle seeding");
   }
-  if (c->h_probe[0] == 0ull) {  // no obstacle: the field is +inf everywhere, no pass runs
-    HIPC(c, hipEventRecord(c->ev1, st));
-    HIPC(c, hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    return dom_finish(c, st, stats, ms);
-  }
+  // no obstacle: the field is +inf everywhere, no pass runs
+  if (c->h_probe[0] == 0ull) return finish_timed(c, st, stats);
   return converge_level(c, st, stats, 1.0);
 }
 
@@ -2301,11 +2293,11 @@ int dymu_clearance_update_device(dymu_ctx* c, const double* dF, double* dW, doub
     c->last_error = "clearance update: the window frees an obstacle cell";
     return DYMU_ERR_STATE;
   }
-  if (c->h_probe[0] == 0ull) {  // nothing new: the field stands
+  if (c->h_probe[0] == 0ull) {  // nothing new: the field stands, and no domain to finish
     HIPC(c, hipEventRecord(c->ev1, st));
-    HIPC(c, hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    double ms = 0.0;
+    const int rc = event_ms(c, c->ev0, c->ev1, &ms);
+    if (rc) return rc;
     if (box) box[0] = i0, box[1] = j0, box[2] = box[3] = 0u;
     if (stats) {
       std::memset(stats, 0, sizeof *stats);
@@ -2329,13 +2321,7 @@ int dymu_clearance_update_device(dymu_ctx* c, const double* dF, double* dW, doub
   c->prio_target = saved_target;
   if (rc) return rc;
   auto& D = c->dom;
-  a.list = D.lists[0];
-  a.counts = D.counts[0];
-  a.shard_cap = D.ntiles;
-  a.tile_epoch = c->d_tile_epoch;
-  a.epoch = D.eb + 1;
-  a.keys = prio_keys(c, 0);
-  a.hist = prio_hist(c, 0);
+  bind_list0(c, a);  // tw, th, ntx: the domain's, which the count above anticipated
   a.ec = D.a.ec;
   win.seed = 1u;
   const uint32_t eb = D.eb, ntiles = D.ntiles, ntx = (uint32_t)D.a.ntx;
@@ -2511,14 +2497,7 @@ int dymu_batch_reduce_device(dymu_ctx* c, const double* dT_stack, uint32_t nx, u
 }
 
 int dymu_last_reduce_ms(dymu_ctx* c, double* ms) {
-  if (!c || !ms) return DYMU_ERR_ARG;
-  if (!c->red_timed) return DYMU_ERR_STATE;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipEventSynchronize(c->ev_red1));
-  float f = 0.0f;
-  HIPC(c, hipEventElapsedTime(&f, c->ev_red0, c->ev_red1));
-  *ms = (double)f;
-  return DYMU_OK;
+  return elapsed_ms(c, &dymu_ctx::red_timed, &dymu_ctx::ev_red0, &dymu_ctx::ev_red1, ms);
 }
 
 int dymu_level_mask_device(dymu_ctx* c, const double* d_map, uint32_t nx, uint32_t ny, uint64_t ld,
@@ -2622,14 +2601,7 @@ int dymu_goal_labels_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t
 }
 
 int dymu_last_labels_ms(dymu_ctx* c, double* ms) {
-  if (!c || !ms) return DYMU_ERR_ARG;
-  if (!c->lab_timed) return DYMU_ERR_STATE;
-  HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipEventSynchronize(c->ev_lab1));
-  float f = 0.0f;
-  HIPC(c, hipEventElapsedTime(&f, c->ev_lab0, c->ev_lab1));
-  *ms = (double)f;
-  return DYMU_OK;
+  return elapsed_ms(c, &dymu_ctx::lab_timed, &dymu_ctx::ev_lab0, &dymu_ctx::ev_lab1, ms);
 }
 
 int dymu_last_paths_ms(dymu_ctx* c, double* ms) {
