@@ -482,7 +482,34 @@ class DyMuPathPlanner {
   std::vector<PathStats> getPathStatsTo(unsigned b, const std::vector<base::Waypoint>& starts,
                                         unsigned max_wp = 1u << 20,
                                         const double* field = nullptr);
-  // whether the last getPaths / getPathStats ran on the device, and its kernel time (HIP
+  // The arriving descent: paths that pass obstacles and end on the goal's
+  // node.  getPaths' descent ends where a cell has an obstacle corner (its direction is NaN
+  // there) and jumps to the sink; this one takes the same continuous step wherever that step
+  // is valid and a node-to-node step on the total cost wherever it is not, never enters an
+  // obstacle node's square, and on a converged map arrives from every start on a finite
+  // node (include/dymu_fim.h states the rule with dymu_arrive_stat).  Waypoints, status,
+  // max_wp, stride and sinks are getPaths'; status -1 is a start whose node is off the grid,
+  // an obstacle or (goal set) without a label.  stats (optional, one per start): the
+  // record -- status, sink, waypoints and hops at stride 1, length, T at the start's node.
+  // The route is getPaths' (dymu_arrive_paths_device while the device map is current, else
+  // the same rule on the host threads; bit-identical).  current_path is not touched.
+  typedef dymu_arrive_stat ArriveStats;
+  std::vector<std::vector<base::Waypoint>> getArrivingPaths(
+      const std::vector<base::Waypoint>& starts, std::vector<int>* status = nullptr,
+      unsigned max_wp = 1u << 20, unsigned stride = 1, std::vector<int>* sinks = nullptr,
+      std::vector<ArriveStats>* stats = nullptr);
+  // ... on map b of the batch with goal b as the sink (always on the device).  Throws
+  // std::invalid_argument for b >= batchCount().
+  std::vector<std::vector<base::Waypoint>> getArrivingPathsTo(
+      unsigned b, const std::vector<base::Waypoint>& starts, std::vector<int>* status = nullptr,
+      unsigned max_wp = 1u << 20, unsigned stride = 1, std::vector<ArriveStats>* stats = nullptr);
+  // the records alone: no waypoint is stored or moved (host = true: the host route)
+  std::vector<ArriveStats> getArrivingStats(const std::vector<base::Waypoint>& starts,
+                                            unsigned max_wp = 1u << 20, bool host = false);
+  std::vector<ArriveStats> getArrivingStatsTo(unsigned b,
+                                              const std::vector<base::Waypoint>& starts,
+                                              unsigned max_wp = 1u << 20);
+  // whether the last getPaths / getPathStats / getArriving* ran on the device, and its kernel time (HIP
   // events, ms)
   bool lastPathsOnDevice() const { return last_paths_device_; }
   double lastPathsKernelMs() const { return last_paths_kernel_ms_; }
@@ -650,10 +677,25 @@ class DyMuPathPlanner {
     unsigned gi, gj;
     double heading;
   };
+  // arrive: the arriving descent (dymu_arrive_paths_device) in place of the reference's,
+  // its records into *arrive
   void pathsOnDevice(const std::vector<base::Waypoint>& starts,
                      std::vector<std::vector<base::Waypoint>>& out, std::vector<int>& st,
                      std::vector<int>& sinks, unsigned max_wp, unsigned stride,
-                     const PathTarget* target = nullptr);
+                     const PathTarget* target = nullptr,
+                     std::vector<ArriveStats>* arrive = nullptr);
+  // getPaths' host post-pass: c slots (x, y, dcx, dcy; grid-local) of a path with this
+  // status into waypoints -- z from the elevation, heading from the direction, the
+  // offsets added; slot 0 keeps the start's z and heading, a status-1 path ends on `sink`
+  void slotsToPath(const double* slots, uint64_t c, int status, const base::Waypoint& start,
+                   const base::Waypoint& sink, std::vector<base::Waypoint>& path) const;
+  // the arriving descent from grid-local (x, y) on T() (labels_ under a goal set): the
+  // kept slots into *slots (null: none stored), the record into rec; returns the status
+  int descendArriving(double x, double y, uint64_t max_wp, unsigned stride,
+                      std::vector<double>* slots, ArriveStats& rec) const;
+  void arriveStatsOnDevice(const std::vector<base::Waypoint>& starts,
+                           std::vector<ArriveStats>& out, unsigned max_wp,
+                           const PathTarget* target);
   void pathStatsOnDevice(const std::vector<base::Waypoint>& starts, std::vector<PathStats>& out,
                          unsigned max_wp, const double* field, const PathTarget* target);
   // getPathStats' copy of the caller's field on the device: dcells_ doubles, allocated on

@@ -277,6 +277,58 @@ int dymu_path_stats_device(dymu_ctx* ctx, const double* dT, uint32_t nx, uint32_
 /* Device time (ms, HIP events) of the last dymu_path_stats_device kernel; waits for it.
  * DYMU_ERR_STATE before the first one. */
 int dymu_last_path_stats_ms(dymu_ctx* ctx, double* ms);
+/* ---- the arriving descent (DyMuPathPlanner::getArrivingPaths) ----
+ * A descent that passes obstacles and ends on the sink's node: the continuous step of
+ * dymu_extract_paths_device wherever it is valid, a node-to-node step on T wherever it is
+ * not.  node(p) = ((uint)(x / res + 0.5), (uint)(y / res + 0.5)), on the grid iff i < nx
+ * and j < ny (a negative or NaN coordinate is off it; tested before any load).  Per path:
+ * the position p, its node n, and `same`, the accepted continuous steps since n changed.
+ *   start   n = node(start) off the grid, T[n] = +inf, or (goal set) n without a label:
+ *           status -1, the empty record, no waypoint.  Else waypoint 0 is the start.
+ *   loop    at most max_wp * stride steps, each:
+ *     1. n is the sink's node (goal set: label[n] = k < n_goals and goal k's node is n):
+ *        the sink is appended, status 1.
+ *     2. c = the continuous step from p and m = node(c).  c is taken iff it is not NaN,
+ *        dist(p, c) >= 0.01 tau res, m is on the grid with T[m] finite and within one
+ *        node of n in i and in j; for m = n, same < 8; for m != n, T[m] < T[n]; for a
+ *        diagonal m, T is finite on both side nodes (m.i, n.j) and (n.i, m.j).
+ *        Then p = c, same = (m == n) ? same + 1 : 0, n = m; the stored direction is the
+ *        step's (dcx, dcy).
+ *     3. else a hop: among the in-grid 8-neighbours m of n in the order (i,j-1), (i-1,j),
+ *        (i+1,j), (i,j+1), (i-1,j-1), (i+1,j-1), (i-1,j+1), (i+1,j+1) with T[m] < T[n], a
+ *        diagonal only with both side nodes finite, the first one of the largest score
+ *        T[n] - T[m] (a diagonal: (T[n] - T[m]) * 0.7071067811865476).  None: status 0,
+ *        the waypoints so far kept.  Else p = (res m.i, res m.j), n = m, same = 0, one more
+ *        hop; the stored direction is (n_old.i - m.i, n_old.j - m.j).
+ *     4. p is kept under dymu_extract_paths_device's stride rule; status -3 when max_wp
+ *        waypoints are kept before the sink.
+ * T[n] never rises and falls whenever n changes, so the walk ends; on a converged map a
+ * start on a finite node arrives.  The record (count, hops and length are those of
+ * stride 1, whatever the stride; -3: it covers the waypoints walked): */
+typedef struct dymu_arrive_stat { /* 32 bytes */
+  int32_t status, sink;  /* as dymu_extract_paths[_goals]_device; sink -1 where status != 1 */
+  uint32_t count, hops;  /* waypoints at stride 1 (sink included); node-to-node steps */
+  double length;         /* seg_0 + seg_1 + ... from 0.0 in order, sqrt(dx*dx + dy*dy) each */
+  double start_cost;     /* T at the start's node (0 with status -1) */
+} dymu_arrive_stat;
+/* d_label NULL: the sink is (goal_i, goal_j); else d_label, d_goal_xy, n_goals as for
+ * dymu_extract_paths_goals_device (goal_i, goal_j ignored; the label is read at the node).
+ * d_out NULL: no waypoint is stored (records only, d_count may be NULL); else the slot
+ * layout of dymu_extract_paths_device (x, y, dcx, dcy; max_wp slots per path) and
+ * d_count[p] = slots written.  d_stats[p] (device) = the record.  A batch plane is an
+ * ordinary map pointer.  Built like the host rule (no contraction): x, y, the counts, the
+ * hops and the length are bit-identical to DyMuPathPlanner's host loop on the same T.
+ * Argument errors are those of dymu_extract_paths[_goals]_device.  Asynchronous on
+ * `stream`; one call at a time per context (the timer is the context's). */
+int dymu_arrive_paths_device(dymu_ctx* ctx, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
+                             double res, uint32_t goal_i, uint32_t goal_j,
+                             const uint32_t* d_label, const double* d_goal_xy, uint32_t n_goals,
+                             double tau, const double* d_start_xy, uint32_t n_paths,
+                             uint32_t max_wp, uint32_t stride, double* d_out, int32_t* d_count,
+                             dymu_arrive_stat* d_stats, void* stream);
+/* Device time (ms, HIP events) of the last dymu_arrive_paths_device kernel; waits for it.
+ * DYMU_ERR_STATE before the first one. */
+int dymu_last_arrive_ms(dymu_ctx* ctx, double* ms);
 /* Device time (ms, HIP events) of the last dymu_goal_labels_device, first kernel to last.
  * DYMU_ERR_STATE before the first one. */
 int dymu_last_labels_ms(dymu_ctx* ctx, double* ms);

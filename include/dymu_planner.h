@@ -139,6 +139,26 @@ int dymu_planner_get_path_stats(dymu_planner* p, const double* starts_xyzh, int 
  * DYMU_ERR_ARG for b >= batch_count. */
 int dymu_planner_get_path_stats_to(dymu_planner* p, uint32_t b, const double* starts_xyzh, int n,
                                    int max_wp, const double* field, dymu_path_stat* out);
+/* getArrivingPaths (extension, DyMu.hpp): dymu_planner_get_paths with the
+ * arriving descent -- paths that pass obstacles and end on the goal's node (the rule is
+ * stated with dymu_arrive_stat in include/dymu_fim.h).  Same arguments, same two-call
+ * protocol, same status values (-1: the start's node is off the grid, an obstacle or
+ * without a label); stats (may be NULL; first call only) receives n records.
+ * dymu_planner_last_path_sinks / _last_paths_on_device / _kernel_ms report the call. */
+int dymu_planner_get_arriving_paths(dymu_planner* p, const double* starts_xyzh, int n, int max_wp,
+                                    int stride, double* out_xyzh, int* counts, int* status,
+                                    dymu_arrive_stat* stats);
+/* ... on map b of the batch with goal b as the sink (always on the device).
+ * DYMU_ERR_ARG for b >= batch_count. */
+int dymu_planner_get_arriving_paths_to(dymu_planner* p, uint32_t b, const double* starts_xyzh,
+                                       int n, int max_wp, int stride, double* out_xyzh,
+                                       int* counts, int* status, dymu_arrive_stat* stats);
+/* getArrivingStats: out[q] = the record of start q, no waypoint stored or moved.  The route
+ * is get_paths' unless host is non-zero.  Returns n or a negative status. */
+int dymu_planner_get_arriving_stats(dymu_planner* p, const double* starts_xyzh, int n, int max_wp,
+                                    int host, dymu_arrive_stat* out);
+int dymu_planner_get_arriving_stats_to(dymu_planner* p, uint32_t b, const double* starts_xyzh,
+                                       int n, int max_wp, dymu_arrive_stat* out);
 /* goalI() / goalJ(): the single goal's cell (goal 0 of a goal set); 1 = written, 0 = no
  * goal set yet */
 int dymu_planner_goal_cell(dymu_planner* p, uint32_t* i, uint32_t* j);

@@ -33,6 +33,8 @@ struct dymu_ctx {
   bool path_timed = false;
   hipEvent_t ev_pstat0 = nullptr, ev_pstat1 = nullptr;  // around the last k_path_stats
   bool pstat_timed = false;
+  hipEvent_t ev_arr0 = nullptr, ev_arr1 = nullptr;  // around the last k_arrive_paths
+  bool arr_timed = false;
   uint32_t* d_pq = nullptr;  // k_path_stats' work queue: the next path index
   hipEvent_t ev_lab0 = nullptr, ev_lab1 = nullptr;  // around the last dymu_goal_labels_device
   bool lab_timed = false;
@@ -1712,6 +1714,8 @@ int dymu_destroy(dymu_ctx* c) {
   if (c->ev_path1) (void)hipEventDestroy(c->ev_path1);
   if (c->ev_pstat0) (void)hipEventDestroy(c->ev_pstat0);
   if (c->ev_pstat1) (void)hipEventDestroy(c->ev_pstat1);
+  if (c->ev_arr0) (void)hipEventDestroy(c->ev_arr0);
+  if (c->ev_arr1) (void)hipEventDestroy(c->ev_arr1);
   if (c->d_pq) (void)hipFree(c->d_pq);
   if (c->ev_lab0) (void)hipEventDestroy(c->ev_lab0);
   if (c->ev_lab1) (void)hipEventDestroy(c->ev_lab1);
@@ -2052,6 +2056,68 @@ int dymu_path_stats_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t 
 
 int dymu_last_path_stats_ms(dymu_ctx* c, double* ms) {
   return elapsed_ms(c, &dymu_ctx::pstat_timed, &dymu_ctx::ev_pstat0, &dymu_ctx::ev_pstat1, ms);
+}
+
+// ---- the arriving descent (arrive_kernels.hip) ----
+static_assert(sizeof(dymu_arrive_stat) == 32 && sizeof(dymu_arrive_stat) == sizeof(ArriveRec) &&
+                  offsetof(dymu_arrive_stat, start_cost) == offsetof(ArriveRec, start_cost),
+              "ArriveRec is dymu_arrive_stat's layout");
+
+int dymu_arrive_paths_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
+                             double res, uint32_t gi, uint32_t gj, const uint32_t* d_label,
+                             const double* d_goal_xy, uint32_t n_goals, double tau,
+                             const double* d_start_xy, uint32_t n_paths, uint32_t max_wp,
+                             uint32_t stride, double* d_out, int32_t* d_count,
+                             dymu_arrive_stat* d_stats, void* stream) {
+  if (!c || !dT || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
+  if (!(res > 0) || !(res < HUGE_VAL) || !(tau > 0) || !(tau < HUGE_VAL)) return DYMU_ERR_ARG;
+  if (max_wp == 0 || max_wp > 0x7fffffffu || stride == 0) return DYMU_ERR_ARG;
+  if (d_label) {
+    if (!d_goal_xy || n_goals == 0 || n_goals >= (1u << 31)) return DYMU_ERR_ARG;
+    if ((uint64_t)nx * ny >= (1ull << 31)) return DYMU_ERR_ARG;
+    gi = gj = 0;
+  } else if (gi >= nx || gj >= ny) {
+    return DYMU_ERR_ARG;
+  }
+  if (n_paths && (!d_start_xy || !d_stats || (d_out && !d_count))) return DYMU_ERR_ARG;
+  if (n_paths == 0) return DYMU_OK;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  if (!c->ev_arr0) HIPC(c, hipEventCreate(&c->ev_arr0));
+  if (!c->ev_arr1) HIPC(c, hipEventCreate(&c->ev_arr1));
+  ArriveArgs a{};
+  a.T = dT;
+  a.ld = (int64_t)ld;
+  a.nx = nx;
+  a.ny = ny;
+  a.res = res;
+  // the host's expressions, as dymu_extract_paths_device forms them
+  a.res_tau = res * tau;
+  a.stall = 0.01 * tau * res;
+  a.sink_x = res * (double)gi;
+  a.sink_y = res * (double)gj;
+  a.goal_i = gi;
+  a.goal_j = gj;
+  a.start_xy = d_start_xy;
+  a.n_paths = n_paths;
+  a.max_wp = max_wp;
+  a.stride = stride;
+  a.out = d_out;
+  a.count = d_count;
+  a.stats = reinterpret_cast<ArriveRec*>(d_stats);
+  a.label = d_label;
+  a.goal_xy = d_goal_xy;
+  a.n_goals = n_goals;
+  c->arr_timed = false;
+  HIPC(c, hipEventRecord(c->ev_arr0, st));
+  HIPC(c, launch_arrive_paths(a, st));
+  HIPC(c, hipEventRecord(c->ev_arr1, st));
+  c->arr_timed = true;
+  return DYMU_OK;
+}
+
+int dymu_last_arrive_ms(dymu_ctx* c, double* ms) {
+  return elapsed_ms(c, &dymu_ctx::arr_timed, &dymu_ctx::ev_arr0, &dymu_ctx::ev_arr1, ms);
 }
 
 int dymu_solve_seeds_device(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t ny,

@@ -430,6 +430,32 @@ struct PathStatArgs {
 hipError_t launch_path_stats(const PathStatArgs& a, uint32_t n_fields, uint32_t lanes,
                              hipStream_t st);
 
+// the arriving descent (arrive_kernels.hip): the continuous step where
+// it is valid, a node-to-node step on T where it is not.  ArriveRec is dymu_arrive_stat's
+// layout.
+struct ArriveRec {
+  int32_t status, sink;
+  uint32_t count, hops;
+  double length, start_cost;
+};
+struct ArriveArgs {
+  const double* T;  // total cost, pitch ld
+  int64_t ld;
+  uint32_t nx, ny;
+  double res, res_tau, stall;  // as PathArgs
+  double sink_x, sink_y;       // res * goal_i, res * goal_j
+  uint32_t goal_i, goal_j;     // the single sink's node
+  const double* start_xy;      // n_paths x 2
+  uint32_t n_paths, max_wp, stride;
+  double* out;       // null: no waypoint is stored; else PathArgs' slots
+  int32_t* count;    // slots kept per path (may be null with out)
+  ArriveRec* stats;  // n_paths records
+  const uint32_t* label;  // null: the single sink; else as PathArgs, looked up at the node
+  const double* goal_xy;
+  uint32_t n_goals;
+};
+hipError_t launch_arrive_paths(const ArriveArgs& a, hipStream_t st);
+
 // goal sets (goal_kernels.hip)
 struct GoalSeed {  // dymu_seed's layout
   uint32_t i, j;

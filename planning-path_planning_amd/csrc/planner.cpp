@@ -2184,6 +2184,37 @@ struct DeviceScratch {
 };
 }  // namespace
 
+// getPaths' host post-pass: z from the elevation with the host's interpolate call and its
+// argument order (nextWaypoint), heading = atan2(-dcy, -dcx) with the host libm
+void DyMuPathPlanner::slotsToPath(const double* r, uint64_t c, int status,
+                                  const base::Waypoint& start, const base::Waypoint& sink,
+                                  std::vector<base::Waypoint>& path) const {
+  path.assign(c, base::Waypoint());
+  for (uint64_t k = 0; k < c; ++k, r += 4) {
+    base::Waypoint& w = path[k];
+    if (status == 1 && k + 1 == c) {
+      w = sink;
+      continue;
+    }
+    if (k == 0) w = start;
+    else w.heading = std::atan2(-r[3], -r[2]);
+    w.position[0] = r[0];
+    w.position[1] = r[1];
+    const double gx = r[0] / global_res_, gy = r[1] / global_res_;
+    unsigned cx = 0, cy = 0;
+    if (path_cell(gx, nx_, cx) && path_cell(gy, ny_, cy)) {
+      const double ax = gx - (double)cx, ay = gy - (double)cy;
+      const uint64_t e = idx(cx, cy);
+      w.position[2] = bilinear(ax, ay, elevation_[e], elevation_[e + 1], elevation_[e + nx_],
+                               elevation_[e + nx_ + 1]);
+    } else if (k > 0) {
+      w.position[2] = 0.0;  // nextWaypoint left the default waypoint's z
+    }
+    w.position[0] += global_offset_[0];
+    w.position[1] += global_offset_[1];
+  }
+}
+
 // The device route: upload the starts, k_extract_paths, download the counts and
 // statuses, then the waypoints written (runs of paths by pitched copies); z and the
 // heading on the host threads.  The kernel's output has one fixed number of slots per path, and a caller's
@@ -2194,7 +2225,8 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
                                     std::vector<std::vector<base::Waypoint>>& out,
                                     std::vector<int>& st, std::vector<int>& sinks,
                                     unsigned max_wp, unsigned stride,
-                                    const PathTarget* target) {
+                                    const PathTarget* target,
+                                    std::vector<ArriveStats>* arrive) {
   constexpr uint64_t kOutBytes = 4ull << 30;  // device output of one batch, at most
   const size_t n = starts.size();
   const double tau = std::min(0.4, risk_distance_);
@@ -2222,6 +2254,7 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
   for (size_t q = 0; q < n; ++q) pending[q] = (uint32_t)q;
   std::vector<double> xy, raw;
   std::vector<int32_t> cnt, sts;
+  std::vector<ArriveStats> recs;  // arrive: the batch's records (status and sink are theirs)
   std::vector<uint64_t> off, len;  // per path: its row in `raw` (waypoints), its count
   struct Run {
     uint32_t q0, n;
@@ -2259,8 +2292,15 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
       int32_t* d_st = dev.alloc<int32_t>(m);
       double* d_out = dev.alloc<double>(4 * cap * m);
       check(dymu_memcpy_h2d(ctx_, d_xy, xy.data(), sizeof(double) * xy.size()), "upload");
-      int32_t* d_snk = gs ? dev.alloc<int32_t>(m) : nullptr;
-      if (gs)
+      int32_t* d_snk = gs && !arrive ? dev.alloc<int32_t>(m) : nullptr;
+      ArriveStats* d_rec = arrive ? dev.alloc<ArriveStats>(m) : nullptr;
+      if (arrive)
+        check(dymu_arrive_paths_device(ctx_, map, nx_, ny_, nx_, global_res_, gi, gj,
+                                       gs ? d_label_ : nullptr, d_gxy,
+                                       gs ? (uint32_t)goals_.size() : 0u, tau, d_xy, m,
+                                       (uint32_t)cap, stride, d_out, d_cnt, d_rec, nullptr),
+              "kernel");
+      else if (gs)
         check(dymu_extract_paths_goals_device(ctx_, dT_, nx_, ny_, nx_, global_res_, d_label_,
                                               d_gxy, (uint32_t)goals_.size(), tau, d_xy, m,
                                               (uint32_t)cap, stride, d_out, d_cnt, d_st, nullptr,
@@ -2273,11 +2313,21 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
       cnt.resize(m);
       sts.resize(m);
       snk.assign(m, 0);
-      if (gs) check(dymu_memcpy_d2h(ctx_, snk.data(), d_snk, sizeof(int32_t) * m), "download");
+      if (d_snk) check(dymu_memcpy_d2h(ctx_, snk.data(), d_snk, sizeof(int32_t) * m), "download");
       check(dymu_memcpy_d2h(ctx_, cnt.data(), d_cnt, sizeof(int32_t) * m), "download");
-      check(dymu_memcpy_d2h(ctx_, sts.data(), d_st, sizeof(int32_t) * m), "download");
+      if (arrive) {
+        recs.resize(m);
+        check(dymu_memcpy_d2h(ctx_, recs.data(), d_rec, sizeof(ArriveStats) * m), "download");
+        for (uint32_t q = 0; q < m; ++q) {
+          sts[q] = recs[q].status;
+          snk[q] = recs[q].sink;
+        }
+      } else {
+        check(dymu_memcpy_d2h(ctx_, sts.data(), d_st, sizeof(int32_t) * m), "download");
+      }
       double ms = 0.0;
-      if (dymu_last_paths_ms(ctx_, &ms) == DYMU_OK) last_paths_kernel_ms_ += ms;
+      if ((arrive ? dymu_last_arrive_ms(ctx_, &ms) : dymu_last_paths_ms(ctx_, &ms)) == DYMU_OK)
+        last_paths_kernel_ms_ += ms;
       // the waypoints: runs of consecutive paths, each downloaded by one pitched copy
       // as wide as its longest path -- a run grows while that moves at most twice its
       // waypoints (plus 1024), so few commands move little more than the counts
@@ -2312,8 +2362,8 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
                 "download");
       for (void* p : {(void*)d_xy, (void*)d_cnt, (void*)d_st, (void*)d_out}) dev.release(p);
       if (d_snk) dev.release(d_snk);
-      // host post-pass: z from the elevation with the host's interpolate call and its
-      // argument order (nextWaypoint), heading = atan2(-dcy, -dcx) with the host libm
+      if (d_rec) dev.release(d_rec);
+      // host post-pass (slotsToPath) on the host threads
       const unsigned nt = std::min<unsigned>(host_threads(), m);
       std::atomic<uint32_t> next{0};
       parallel_tasks(nt, [&](unsigned) {
@@ -2322,39 +2372,314 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
           st[id] = sts[q];
           if (sts[q] == -3 && cap < max_wp) continue;
           sinks[id] = sts[q] == 1 ? snk[q] : -1;
-          const uint64_t c = len[q];
-          const double* r = raw.data() + 4 * off[q];
-          std::vector<base::Waypoint>& path = out[id];
-          path.assign(c, base::Waypoint());
-          for (uint64_t k = 0; k < c; ++k, r += 4) {
-            base::Waypoint& w = path[k];
-            if (sts[q] == 1 && k + 1 == c) {
-              w = gs ? gsinks[(size_t)snk[q]] : sink;
-              continue;
-            }
-            if (k == 0) w = starts[id];
-            else w.heading = std::atan2(-r[3], -r[2]);
-            w.position[0] = r[0];
-            w.position[1] = r[1];
-            const double gx = r[0] / global_res_, gy = r[1] / global_res_;
-            unsigned cx = 0, cy = 0;
-            if (path_cell(gx, nx_, cx) && path_cell(gy, ny_, cy)) {
-              const double ax = gx - (double)cx, ay = gy - (double)cy;
-              const uint64_t e = idx(cx, cy);
-              w.position[2] = bilinear(ax, ay, elevation_[e], elevation_[e + 1],
-                                       elevation_[e + nx_], elevation_[e + nx_ + 1]);
-            } else if (k > 0) {
-              w.position[2] = 0.0;  // nextWaypoint left the default waypoint's z
-            }
-            w.position[0] += global_offset_[0];
-            w.position[1] += global_offset_[1];
-          }
+          if (arrive) (*arrive)[id] = recs[q];
+          slotsToPath(raw.data() + 4 * off[q], len[q], sts[q], starts[id],
+                      gs ? gsinks[(size_t)std::max(snk[q], 0)] : sink, out[id]);
         }
       });
     }
     pending.swap(again);
     cap = std::min<uint64_t>(cap * 4, max_wp);
   }
+}
+
+// ---- the arriving descent (extension) ----
+// null with an engine that predates the entry (tests/hostengine): the host route runs
+#pragma weak dymu_arrive_paths_device
+#pragma weak dymu_last_arrive_ms
+
+namespace {
+// The node of coordinate v (nearestIndex's rounding) on an axis of n nodes; false off the
+// grid -- a negative or NaN coordinate included.  k_arrive_paths makes the same test.
+bool arrive_node(double v, double res, unsigned n, unsigned& i) {
+  if (!(v >= 0.0)) return false;
+  const double h = v / res + 0.5;
+  if (!(h < 4294967296.0)) return false;
+  i = (unsigned)h;
+  return i < n;
+}
+constexpr DyMuPathPlanner::ArriveStats kNoArrival{-1, -1, 0u, 0u, 0.0, 0.0};
+}  // namespace
+
+// The rule of include/dymu_fim.h (dymu_arrive_stat), which k_arrive_paths
+// (arrive_kernels.hip) follows statement for statement: every expression here is formed
+// there in the same order.
+int DyMuPathPlanner::descendArriving(double x, double y, uint64_t max_wp, unsigned stride,
+                                     std::vector<double>* slots, ArriveStats& rec) const {
+  rec = kNoArrival;
+  if (slots) slots->clear();
+  if (!has_goal_) return -1;
+  const double res = global_res_, tau = std::min(0.4, risk_distance_);
+  const double res_tau = res * tau, stall = 0.01 * tau * res;
+  const uint64_t limit = max_wp > std::numeric_limits<uint64_t>::max() / stride
+                             ? std::numeric_limits<uint64_t>::max()
+                             : max_wp * stride;
+  unsigned ni = 0, nj = 0;
+  if (!arrive_node(x, res, nx_, ni) || !arrive_node(y, res, ny_, nj)) return -1;
+  const bool gs = !goals_.empty();
+  // T at the node (dj, di) away from (ni, nj); +inf off the grid, which no test accepts
+  auto at = [&](int di, int dj) {
+    const int64_t i = (int64_t)ni + di, j = (int64_t)nj + dj;
+    return i < 0 || j < 0 || i >= (int64_t)nx_ || j >= (int64_t)ny_ ? kInf
+                                                                    : T(idx((unsigned)i, (unsigned)j));
+  };
+  auto dist = [](double ax, double ay, double bx, double by) {
+    const double dx = ax - bx, dy = ay - by;
+    return std::sqrt(dx * dx + dy * dy);
+  };
+  // the sink of the node the path is on: the goal, or the goal labelled there (-1: none)
+  double sink_x = res * (double)goal_i_, sink_y = res * (double)goal_j_;
+  unsigned sni = goal_i_, snj = goal_j_;
+  int sink_k = gs ? -1 : 0;
+  auto track = [&] {
+    if (!gs) return;
+    const uint32_t lab = labels_[idx(ni, nj)];
+    sink_k = lab < goals_.size() ? (int)lab : -1;
+    if (sink_k < 0) return;
+    const base::Waypoint s = sinkWaypoint(lab);
+    sink_x = s.position[0];
+    sink_y = s.position[1];
+    if (!arrive_node(sink_x, res, nx_, sni) || !arrive_node(sink_y, res, ny_, snj))
+      sni = snj = 0xffffffffu;  // a goal off the grid is no node's sink
+  };
+  track();
+  if (!(at(0, 0) < kInf) || sink_k < 0) return -1;
+  rec.start_cost = at(0, 0);
+  int status = 0;
+  uint64_t kept = 0;
+  unsigned phase = 0, same = 0;
+  double px = 0, py = 0, pdx = 0, pdy = 0;
+  for (uint64_t w = 0;; ++w) {
+    // waypoint w joins the record and, under the stride rule, the slots
+    if (w > 0) rec.length = rec.length + dist(px, py, x, y);
+    ++rec.count;
+    if (phase == 0) {
+      if (slots) slots->insert(slots->end(), {x, y, pdx, pdy});
+      ++kept;
+    }
+    if (++phase == stride) phase = 0;
+    px = x;
+    py = y;
+    // 1. arrived
+    if (ni == sni && nj == snj && sink_k >= 0) {
+      status = 1;
+      break;
+    }
+    if (w + 1 == limit) {
+      status = -3;
+      break;
+    }
+    const double tn = at(0, 0);
+    // 2. the continuous candidate (nextWaypoint's expressions) and its node m
+    const double gx = x / res, gy = y / res;
+    double cx_ = std::numeric_limits<double>::quiet_NaN(), cy_ = cx_, dcx = 0, dcy = 0;
+    unsigned cx = 0, cy = 0;
+    if (path_cell(gx, nx_, cx) && path_cell(gy, ny_, cy)) {
+      const double ax = gx - (double)cx, ay = gy - (double)cy;
+      double gx00, gx10, gx01, gx11, gy00, gy10, gy01, gy11;
+      gradientNode(cx, cy, gx00, gy00);
+      gradientNode(cx + 1, cy, gx10, gy10);
+      gradientNode(cx, cy + 1, gx01, gy01);
+      gradientNode(cx + 1, cy + 1, gx11, gy11);
+      dcx = bilinear(ax, ay, gx00, gx01, gx10, gx11);
+      dcy = bilinear(ax, ay, gy00, gy01, gy10, gy11);
+      cx_ = x - res_tau * dcx;
+      cy_ = y - res_tau * dcy;
+    }
+    unsigned mi = 0, mj = 0;
+    bool take = dist(x, y, cx_, cy_) >= stall;  // false for a NaN candidate
+    take = take && arrive_node(cx_, res, nx_, mi) && arrive_node(cy_, res, ny_, mj);
+    int di = 0, dj = 0;
+    if (take) {
+      const int64_t ddi = (int64_t)mi - (int64_t)ni, ddj = (int64_t)mj - (int64_t)nj;
+      take = ddi >= -1 && ddi <= 1 && ddj >= -1 && ddj <= 1;
+      di = (int)ddi;
+      dj = (int)ddj;
+    }
+    if (take) {
+      const double tm = at(di, dj);
+      take = tm < kInf;
+      if (di == 0 && dj == 0) take = take && same < 8u;
+      else take = take && tm < tn;
+      if (di != 0 && dj != 0)  // no corner is cut: both side nodes are finite
+        take = take && at(di, 0) < kInf && at(0, dj) < kInf;
+    }
+    if (take) {
+      x = cx_;
+      y = cy_;
+      pdx = dcx;
+      pdy = dcy;
+      if (di == 0 && dj == 0) {
+        ++same;
+      } else {
+        same = 0;
+        ni = mi;
+        nj = mj;
+        track();
+      }
+      continue;
+    }
+    // 3. a hop to the neighbour of the steepest fall of T; the first of equal scores
+    static const int kHop[8][2] = {{0, -1}, {-1, 0}, {1, 0}, {0, 1},
+                                   {-1, -1}, {1, -1}, {-1, 1}, {1, 1}};
+    double best = -1.0;
+    int bi = 0, bj = 0;
+    for (const auto& h : kHop) {
+      const bool diag = h[0] != 0 && h[1] != 0;
+      if (diag && !(at(h[0], 0) < kInf && at(0, h[1]) < kInf)) continue;
+      const double tm = at(h[0], h[1]);
+      if (!(tm < tn)) continue;
+      const double s = diag ? (tn - tm) * 0.7071067811865476 : tn - tm;
+      if (s > best) {
+        best = s;
+        bi = h[0];
+        bj = h[1];
+      }
+    }
+    if (bi == 0 && bj == 0) break;  // stalled: status 0
+    ni = (unsigned)((int64_t)ni + bi);
+    nj = (unsigned)((int64_t)nj + bj);
+    x = res * (double)ni;
+    y = res * (double)nj;
+    pdx = (double)-bi;
+    pdy = (double)-bj;
+    same = 0;
+    ++rec.hops;
+    track();
+  }
+  if (status == 1) {
+    if (kept < max_wp) {
+      rec.length = rec.length + dist(px, py, sink_x, sink_y);
+      ++rec.count;
+      if (slots) slots->insert(slots->end(), {sink_x, sink_y, 0.0, 0.0});
+    } else {
+      status = -3;
+    }
+  }
+  rec.status = status;
+  rec.sink = status == 1 ? sink_k : -1;
+  return status;
+}
+
+std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getArrivingPaths(
+    const std::vector<base::Waypoint>& starts, std::vector<int>* status, unsigned max_wp,
+    unsigned stride, std::vector<int>* sinks, std::vector<ArriveStats>* stats) {
+  if (max_wp == 0 || stride == 0)
+    throw std::invalid_argument("getArrivingPaths: max_wp, stride >= 1");
+  const size_t n = starts.size();
+  std::vector<std::vector<base::Waypoint>> out(n);
+  std::vector<int> st(n, -1), sk(n, -1);
+  std::vector<ArriveStats> rec(n, kNoArrival);
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  if (n && has_goal_) {
+    if (ctx_ && dT_ && dev_map_current_ && n <= 0xffffffffull && &dymu_arrive_paths_device &&
+        &dymu_last_arrive_ms && (goals_.empty() || goalsOnDevice())) {
+      pathsOnDevice(starts, out, st, sk, max_wp, stride, nullptr, &rec);
+      last_paths_device_ = true;
+    } else {
+      if (!goals_.empty()) ensureHostLabels();
+      base::Waypoint sink;
+      sink.position[0] = global_res_ * (double)goal_i_ + global_offset_[0];
+      sink.position[1] = global_res_ * (double)goal_j_ + global_offset_[1];
+      sink.position[2] = elevation_[idx(goal_i_, goal_j_)];
+      sink.heading = goal_heading_;
+      const unsigned nt = (unsigned)std::min<size_t>(host_threads(), n);
+      std::atomic<size_t> next{0};
+      parallel_tasks(nt, [&](unsigned) {
+        std::vector<double> slots;
+        for (size_t q = next++; q < n; q = next++) {
+          st[q] = descendArriving(starts[q].position[0] - global_offset_[0],
+                                  starts[q].position[1] - global_offset_[1], max_wp, stride,
+                                  &slots, rec[q]);
+          sk[q] = rec[q].sink;
+          base::Waypoint end = sink;
+          if (!goals_.empty() && sk[q] >= 0) {
+            end = sinkWaypoint((size_t)sk[q]);
+            end.position[0] += global_offset_[0];
+            end.position[1] += global_offset_[1];
+          }
+          slotsToPath(slots.data(), slots.size() / 4, st[q], starts[q], end, out[q]);
+        }
+      });
+    }
+  }
+  if (status) status->swap(st);
+  if (sinks) sinks->swap(sk);
+  if (stats) stats->swap(rec);
+  return out;
+}
+
+std::vector<DyMuPathPlanner::ArriveStats> DyMuPathPlanner::getArrivingStats(
+    const std::vector<base::Waypoint>& starts, unsigned max_wp, bool host) {
+  if (max_wp == 0) throw std::invalid_argument("getArrivingStats: max_wp >= 1");
+  const size_t n = starts.size();
+  std::vector<ArriveStats> out(n, kNoArrival);
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  if (!n || !has_goal_) return out;
+  if (!host && ctx_ && dT_ && dev_map_current_ && n <= 0xffffffffull &&
+      max_wp <= 0x7fffffffu && &dymu_arrive_paths_device && &dymu_last_arrive_ms &&
+      (goals_.empty() || goalsOnDevice())) {
+    arriveStatsOnDevice(starts, out, max_wp, nullptr);
+    last_paths_device_ = true;
+    return out;
+  }
+  if (!goals_.empty()) ensureHostLabels();
+  const unsigned nt = (unsigned)std::min<size_t>(host_threads(), n);
+  std::atomic<size_t> next{0};
+  parallel_tasks(nt, [&](unsigned) {
+    for (size_t q = next++; q < n; q = next++)
+      (void)descendArriving(starts[q].position[0] - global_offset_[0],
+                            starts[q].position[1] - global_offset_[1], max_wp, 1, nullptr, out[q]);
+  });
+  return out;
+}
+
+// The device route of the records: the starts up, one k_arrive_paths launch that stores
+// no waypoint, the records down.
+void DyMuPathPlanner::arriveStatsOnDevice(const std::vector<base::Waypoint>& starts,
+                                          std::vector<ArriveStats>& out, unsigned max_wp,
+                                          const PathTarget* target) {
+  const size_t n = starts.size();
+  const double tau = std::min(0.4, risk_distance_);
+  auto check = [&](int rc, const char* what) {
+    if (rc != DYMU_OK)
+      throw std::runtime_error(std::string("dymu: getArrivingStats ") + what + " failed: " +
+                               dymu_strerror(rc) + " " + dymu_last_error(ctx_));
+  };
+  const double* map = target ? target->map : dT_;
+  const unsigned gi = target ? target->gi : goal_i_, gj = target ? target->gj : goal_j_;
+  const bool gs = !target && !goals_.empty();
+  DeviceScratch dev(ctx_);
+  double* d_gxy = nullptr;
+  if (gs) {
+    ensureDeviceLabels();
+    std::vector<double> gxy(2 * goals_.size());
+    for (size_t k = 0; k < goals_.size(); ++k) {
+      const base::Waypoint w = sinkWaypoint(k);
+      gxy[2 * k] = w.position[0];
+      gxy[2 * k + 1] = w.position[1];
+    }
+    d_gxy = dev.alloc<double>(gxy.size());
+    check(dymu_memcpy_h2d(ctx_, d_gxy, gxy.data(), sizeof(double) * gxy.size()), "upload");
+  }
+  std::vector<double> xy(2 * n);
+  for (size_t q = 0; q < n; ++q) {
+    xy[2 * q] = starts[q].position[0] - global_offset_[0];
+    xy[2 * q + 1] = starts[q].position[1] - global_offset_[1];
+  }
+  double* d_xy = dev.alloc<double>(2 * (uint64_t)n);
+  ArriveStats* d_rec = dev.alloc<ArriveStats>(n);
+  check(dymu_memcpy_h2d(ctx_, d_xy, xy.data(), sizeof(double) * xy.size()), "upload");
+  check(dymu_arrive_paths_device(ctx_, map, nx_, ny_, nx_, global_res_, gi, gj,
+                                 gs ? d_label_ : nullptr, d_gxy,
+                                 gs ? (uint32_t)goals_.size() : 0u, tau, d_xy, (uint32_t)n, max_wp,
+                                 1, nullptr, nullptr, d_rec, nullptr),
+        "kernel");
+  check(dymu_memcpy_d2h(ctx_, out.data(), d_rec, sizeof(ArriveStats) * n), "download");
+  double ms = 0.0;
+  if (dymu_last_arrive_ms(ctx_, &ms) == DYMU_OK) last_paths_kernel_ms_ = ms;
 }
 
 // ---- getPathStats: per-path summaries (extension) ----
@@ -3551,6 +3876,52 @@ std::vector<DyMuPathPlanner::PathStats> DyMuPathPlanner::getPathStatsTo(
     const PathTarget tgt{dT_batch_ + (uint64_t)b * dymu_batch_plane_rows(ny_) * nx_, g.i, g.j,
                          g.heading};
     pathStatsOnDevice(starts, out, max_wp, field, &tgt);
+    last_paths_device_ = true;
+  }
+  return out;
+}
+
+std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getArrivingPathsTo(
+    unsigned b, const std::vector<base::Waypoint>& starts, std::vector<int>* status,
+    unsigned max_wp, unsigned stride, std::vector<ArriveStats>* stats) {
+  if (max_wp == 0 || stride == 0)
+    throw std::invalid_argument("getArrivingPathsTo: max_wp, stride >= 1");
+  if (b >= batch_goals_.size() || !ctx_ || !dT_batch_ || starts.size() > 0xffffffffull ||
+      !&dymu_arrive_paths_device || !&dymu_last_arrive_ms || !refreshBatch())
+    throw std::invalid_argument("getArrivingPathsTo: no such map in the batch");
+  const size_t n = starts.size();
+  std::vector<std::vector<base::Waypoint>> out(n);
+  std::vector<int> st(n, -1), sk(n, -1);
+  std::vector<ArriveStats> rec(n, kNoArrival);
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  if (n) {
+    const BatchGoal& g = batch_goals_[b];
+    const PathTarget tgt{dT_batch_ + (uint64_t)b * dymu_batch_plane_rows(ny_) * nx_, g.i, g.j,
+                         g.heading};
+    pathsOnDevice(starts, out, st, sk, max_wp, stride, &tgt, &rec);
+    last_paths_device_ = true;
+  }
+  if (status) status->swap(st);
+  if (stats) stats->swap(rec);
+  return out;
+}
+
+std::vector<DyMuPathPlanner::ArriveStats> DyMuPathPlanner::getArrivingStatsTo(
+    unsigned b, const std::vector<base::Waypoint>& starts, unsigned max_wp) {
+  if (max_wp == 0) throw std::invalid_argument("getArrivingStatsTo: max_wp >= 1");
+  if (b >= batch_goals_.size() || !ctx_ || !dT_batch_ || starts.size() > 0xffffffffull ||
+      max_wp > 0x7fffffffu || !&dymu_arrive_paths_device || !&dymu_last_arrive_ms ||
+      !refreshBatch())
+    throw std::invalid_argument("getArrivingStatsTo: no such map in the batch");
+  std::vector<ArriveStats> out(starts.size(), kNoArrival);
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  if (!starts.empty()) {
+    const BatchGoal& g = batch_goals_[b];
+    const PathTarget tgt{dT_batch_ + (uint64_t)b * dymu_batch_plane_rows(ny_) * nx_, g.i, g.j,
+                         g.heading};
+    arriveStatsOnDevice(starts, out, max_wp, &tgt);
     last_paths_device_ = true;
   }
   return out;

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -567,6 +568,75 @@ int dymu_planner_get_path_stats_to(dymu_planner* p, uint32_t b, const double* st
     return DYMU_ERR_ARG;
   return guarded([&] {
     const auto v = p->pl.getPathStatsTo(b, wps(starts, n, 4), (unsigned)max_wp, field);
+    std::copy(v.begin(), v.end(), out);
+    return n;
+  });
+}
+
+namespace {
+// the first half of the two-call protocol for a result `run` leaves in the handle
+// (p->paths, p->paths_status, p->paths_sinks); the second half is dymu_planner_get_paths'
+int arriving_paths(dymu_planner* p, int n, double* out, int* counts, int* status,
+                   const std::function<void()>& run) {
+  const int rc = guarded([&] {
+    run();
+    return DYMU_OK;
+  });
+  if (rc != DYMU_OK) return rc;
+  for (int q = 0; q < n; ++q) {
+    if (counts) counts[q] = (int)p->paths[q].size();
+    if (status) status[q] = p->paths_status[q];
+  }
+  if (out) return dymu_planner_get_paths(p, nullptr, n, 0, 0, out, nullptr, nullptr);
+  return n;
+}
+}  // namespace
+
+int dymu_planner_get_arriving_paths(dymu_planner* p, const double* starts, int n, int max_wp,
+                                    int stride, double* out, int* counts, int* status,
+                                    dymu_arrive_stat* stats) {
+  if (!starts) return dymu_planner_get_paths(p, nullptr, n, max_wp, stride, out, counts, status);
+  if (!p || n < 0 || max_wp <= 0 || stride <= 0) return DYMU_ERR_ARG;
+  return arriving_paths(p, n, out, counts, status, [&] {
+    std::vector<DyMuPathPlanner::ArriveStats> rec;
+    p->paths = p->pl.getArrivingPaths(wps(starts, n, 4), &p->paths_status, (unsigned)max_wp,
+                                      (unsigned)stride, &p->paths_sinks, &rec);
+    if (stats) std::copy(rec.begin(), rec.end(), stats);
+  });
+}
+
+int dymu_planner_get_arriving_paths_to(dymu_planner* p, uint32_t b, const double* starts, int n,
+                                       int max_wp, int stride, double* out, int* counts,
+                                       int* status, dymu_arrive_stat* stats) {
+  if (!starts) return dymu_planner_get_paths(p, nullptr, n, max_wp, stride, out, counts, status);
+  if (!p || n < 0 || max_wp <= 0 || stride <= 0 || b >= p->pl.batchCount()) return DYMU_ERR_ARG;
+  return arriving_paths(p, n, out, counts, status, [&] {
+    std::vector<DyMuPathPlanner::ArriveStats> rec;
+    p->paths = p->pl.getArrivingPathsTo(b, wps(starts, n, 4), &p->paths_status, (unsigned)max_wp,
+                                        (unsigned)stride, &rec);
+    p->paths_sinks.assign((size_t)n, 0);
+    for (int q = 0; q < n; ++q)
+      if (p->paths_status[q] != 1) p->paths_sinks[q] = -1;
+    if (stats) std::copy(rec.begin(), rec.end(), stats);
+  });
+}
+
+int dymu_planner_get_arriving_stats(dymu_planner* p, const double* starts, int n, int max_wp,
+                                    int host, dymu_arrive_stat* out) {
+  if (!p || n < 0 || max_wp <= 0 || (n > 0 && (!starts || !out))) return DYMU_ERR_ARG;
+  return guarded([&] {
+    const auto v = p->pl.getArrivingStats(wps(starts, n, 4), (unsigned)max_wp, host != 0);
+    std::copy(v.begin(), v.end(), out);
+    return n;
+  });
+}
+
+int dymu_planner_get_arriving_stats_to(dymu_planner* p, uint32_t b, const double* starts, int n,
+                                       int max_wp, dymu_arrive_stat* out) {
+  if (!p || n < 0 || max_wp <= 0 || (n > 0 && (!starts || !out)) || b >= p->pl.batchCount())
+    return DYMU_ERR_ARG;
+  return guarded([&] {
+    const auto v = p->pl.getArrivingStatsTo(b, wps(starts, n, 4), (unsigned)max_wp);
     std::copy(v.begin(), v.end(), out);
     return n;
   });

@@ -181,6 +181,10 @@ PATH_STAT_DTYPE = np.dtype([("status", np.int32), ("sink", np.int32), ("count", 
                             ("vmin", np.float64, (PATH_FIELDS,)),
                             ("vmax", np.float64, (PATH_FIELDS,)),
                             ("skipped", np.uint32, (PATH_FIELDS,))], align=True)
+# dymu_arrive_stat: the record of one arriving path (include/dymu_fim.h)
+ARRIVE_STAT_DTYPE = np.dtype([("status", np.int32), ("sink", np.int32), ("count", np.uint32),
+                              ("hops", np.uint32), ("length", np.float64),
+                              ("start_cost", np.float64)], align=True)
 
 FIM_SYMBOLS = {
     "dymu_create": (_i32, [ctypes.POINTER(_vp), ctypes.POINTER(DymuOpts)]),
@@ -263,6 +267,10 @@ FIM_SYMBOLS = {
                                       _vp, _vp, _u32, ctypes.c_double, _vp, _u32, _u32, _vp, _vp,
                                       _u32, _u32, _vp, _vp]),
     "dymu_last_path_stats_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_arrive_paths_device": (_i32, [_vp, _vp, _u32, _u32, _u64, ctypes.c_double, _u32, _u32,
+                                        _vp, _vp, _u32, ctypes.c_double, _vp, _u32, _u32, _u32,
+                                        _vp, _vp, _vp, _vp]),
+    "dymu_last_arrive_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "dymu_batch_plane_rows": (_u32, [_u32]),
     "dymu_stack_speed_device": (_i32, [_vp, _vp, _u64, _u64, _u32, _u32, _u32, _vp, _u64, _vp]),
     "dymu_solve_batch_device": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _u32, _vp,
@@ -656,6 +664,57 @@ class Engine:
         """Device time of the last path_stats kernel (waits for it)."""
         ms = ctypes.c_double()
         _check(self._lib.dymu_last_path_stats_ms(self.ctx, ctypes.byref(ms)), self.ctx)
+        return ms.value
+
+    # -- the arriving descent (DESIGN.md s5.15) --
+    def arrive_paths(self, dT: int, nx: int, ny: int, ld: int, res: float, goal_i: int,
+                     goal_j: int, tau: float, starts_xy, max_wp: int, stride: int = 1,
+                     store: bool = True, d_label: int = 0, goals_ij=None, stream: int = 0):
+        """dymu_arrive_paths_device on the device map dT for host starts (n, 2) in grid-local
+        metres: (out [n, max_wp, 4] of x, y, dcx, dcy; counts [n]; records, an
+        ARRIVE_STAT_DTYPE array).  store=False passes d_out = NULL: (None, None, records).
+        d_label with goals_ij (n_goals, 2): the sink follows the label map."""
+        xy = np.ascontiguousarray(starts_xy, dtype=np.float64).reshape(-1, 2)
+        n = len(xy)
+        rec = np.zeros(n, dtype=ARRIVE_STAT_DTYPE)
+        out = np.zeros((n, max_wp, 4)) if store else None
+        cnt = np.zeros(n, dtype=np.int32) if store else None
+        gxy = None
+        if d_label:
+            gxy = res * np.ascontiguousarray(goals_ij, dtype=np.float64).reshape(-1, 2)
+        ptrs = [self.alloc(max(xy.nbytes, 8)), self.alloc(max(rec.nbytes, 8)),
+                self.alloc(max(out.nbytes, 8)) if store else 0,
+                self.alloc(4 * max(n, 1)) if store else 0,
+                self.alloc(max(gxy.nbytes, 8)) if gxy is not None else 0]
+        try:
+            if n:
+                self.h2d(ptrs[0], xy)
+            if gxy is not None and len(gxy):
+                self.h2d(ptrs[4], gxy)
+            _check(self._lib.dymu_arrive_paths_device(
+                self.ctx, dT, nx, ny, ld, res, goal_i, goal_j, d_label or None, ptrs[4] or None,
+                len(gxy) if gxy is not None else 0, tau, ptrs[0], n, max_wp, stride,
+                ptrs[2] or None, ptrs[3] if store else None, ptrs[1], stream or None), self.ctx)
+            if n:
+                if stream:  # d2h is ordered on the context stream only
+                    self.last_arrive_ms()
+                self.d2h(rec, ptrs[1])
+                if store:
+                    self.d2h(cnt, ptrs[3])
+                    self.d2h(out, ptrs[2])
+        finally:
+            for p in ptrs:
+                if p:
+                    self.free(p)
+        if store:
+            for q in range(n):  # slots past the count were never written
+                out[q, max(cnt[q], 0):] = 0.0
+        return out, cnt, rec
+
+    def last_arrive_ms(self) -> float:
+        """Device time of the last arrive_paths kernel (waits for it)."""
+        ms = ctypes.c_double()
+        _check(self._lib.dymu_last_arrive_ms(self.ctx, ctypes.byref(ms)), self.ctx)
         return ms.value
 
     # -- batched solves (DESIGN.md s5.7) --
@@ -1135,6 +1194,11 @@ PLANNER_SYMBOLS = {
     "dymu_planner_last_combine_kernel_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "dymu_planner_get_path_stats": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp]),
     "dymu_planner_get_path_stats_to": (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp]),
+    "dymu_planner_get_arriving_paths": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "dymu_planner_get_arriving_paths_to": (_i32, [_vp, _u32, _vp, _i32, _i32, _i32, _vp, _vp, _vp,
+                                                  _vp]),
+    "dymu_planner_get_arriving_stats": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "dymu_planner_get_arriving_stats_to": (_i32, [_vp, _u32, _vp, _i32, _i32, _vp]),
     "dymu_planner_goal_cell": (_i32, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "dymu_planner_get_locomotion_mode": (_i32, [_vp, _d, _d, _d, _d, ctypes.c_char_p, _i32]),
     "dymu_planner_set_global_risk": (_i32, [_vp, _d, _d]),
@@ -1595,6 +1659,56 @@ class Planner:
         _b_int(self._lib.dymu_planner_get_path_stats_to(
             self.h, b, s.ctypes.data, len(s), max_wp, None if f is None else f.ctypes.data,
             out.ctypes.data))
+        return out
+
+    # -- the arriving descent (DyMuPathPlanner::getArrivingPaths) --
+    def _arriving(self, fn, pre, starts, max_wp, stride):
+        s = np.ascontiguousarray([self._wp(w) for w in starts], dtype=np.float64).reshape(-1, 4)
+        n = len(s)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        rec = np.zeros(max(n, 1), dtype=ARRIVE_STAT_DTYPE)
+        _b_int(fn(self.h, *pre, s.ctypes.data, n, max_wp, stride, None, cnt.ctypes.data,
+                  st.ctypes.data, rec.ctypes.data))
+        self._sinks = np.full(n, -1, dtype=np.int32)
+        if n:
+            _b_int(self._lib.dymu_planner_last_path_sinks(self.h, self._sinks.ctypes.data, n))
+        buf = np.empty((max(int(cnt[:n].sum()), 1), 4))
+        _b_int(fn(self.h, *pre, None, n, 0, 0, buf.ctypes.data, None, None, None))
+        ends = np.cumsum(cnt[:n])
+        return ([buf[e - c:e].copy() for e, c in zip(ends, cnt[:n])], st[:n].copy(),
+                rec[:n].copy())
+
+    def getArrivingPaths(self, starts, max_wp: int = 1 << 20, stride: int = 1):
+        """getPaths with the arriving descent: paths that pass obstacles and end on the
+        goal's node -- the continuous descent wherever it is valid, a node-to-node step on
+        the total cost wherever it is not, never inside an obstacle node's square.  Returns
+        (paths, status, records): getPaths' two, and an ARRIVE_STAT_DTYPE array (status,
+        sink, waypoints and hops at stride 1, length, total cost at the start's node).
+        Status -1: the start's node is off the grid, an obstacle or without a label.
+        lastPathSinks / lastPathsOnDevice / lastPathsKernelMs report the call."""
+        return self._arriving(self._lib.dymu_planner_get_arriving_paths, (), starts, max_wp,
+                              stride)
+
+    def getArrivingPathsTo(self, b: int, starts, max_wp: int = 1 << 20, stride: int = 1):
+        """getArrivingPaths on map b of the batch, with goal b as the sink."""
+        return self._arriving(self._lib.dymu_planner_get_arriving_paths_to, (b,), starts, max_wp,
+                              stride)
+
+    def getArrivingStats(self, starts, max_wp: int = 1 << 20, host: bool = False):
+        """The records of getArrivingPaths alone: no waypoint is stored or moved."""
+        s = np.ascontiguousarray([self._wp(w) for w in starts], dtype=np.float64).reshape(-1, 4)
+        out = np.zeros(len(s), dtype=ARRIVE_STAT_DTYPE)
+        _b_int(self._lib.dymu_planner_get_arriving_stats(self.h, s.ctypes.data, len(s), max_wp,
+                                                         int(bool(host)), out.ctypes.data))
+        return out
+
+    def getArrivingStatsTo(self, b: int, starts, max_wp: int = 1 << 20):
+        """getArrivingStats on map b of the batch, with goal b as the sink."""
+        s = np.ascontiguousarray([self._wp(w) for w in starts], dtype=np.float64).reshape(-1, 4)
+        out = np.zeros(len(s), dtype=ARRIVE_STAT_DTYPE)
+        _b_int(self._lib.dymu_planner_get_arriving_stats_to(self.h, b, s.ctypes.data, len(s),
+                                                            max_wp, out.ctypes.data))
         return out
 
     def goalCell(self):
