@@ -509,7 +509,42 @@ class DyMuPathPlanner {
   std::vector<ArriveStats> getArrivingStatsTo(unsigned b,
                                               const std::vector<base::Waypoint>& starts,
                                               unsigned max_wp = 1u << 20);
-  // whether the last getPaths / getPathStats / getArriving* ran on the device, and its kernel time (HIP
+  // Every cell's node route to the goal at once (include/dymu_fim.h states
+  // the definition with dymu_route_out): per cell the goal its route ends on, the hops
+  // between axis and diagonal neighbours, the length, and per sampled field the integral
+  // along the route, the minimum and the maximum.  The route is the hop of the arriving
+  // descent applied at every node -- a chain of grid nodes along which the total cost falls
+  // strictly and that cuts no obstacle corner, not the mostly continuous path
+  // getArrivingPaths returns; its length is octile (up to 8.2 % above a straight run), and
+  // under a goal set its sink can differ from the 4-neighbour label of goalLabel().
+  // request.fields: up to DYMU_PATH_FIELDS entries, each the speed map the solve used
+  // (nullptr, getPathStats' slot 0) or a caller's row-major nx*ny array.  request.outputs:
+  // the maps wanted (kRoute* bits); only they are computed.  The device route is getPaths'
+  // (dymu_route_fields_device while the device map is current), else -- or with host = true
+  // -- the same definition on the host mirror, the cells in ascending total cost, each from
+  // its parent.  Integer outputs, length, vmin and vmax are bit-identical between the two;
+  // the integrals add the same terms in another order.  current_path is not touched.
+  // Without a goal every cell is without a route.
+  enum : uint32_t {
+    kRouteSink = 1u, kRouteAxis = 2u, kRouteDiag = 4u, kRouteLength = 8u,
+    kRouteIntegral = 16u, kRouteMin = 32u, kRouteMax = 64u, kRouteAll = 127u
+  };
+  struct RouteRequest {
+    uint32_t outputs = kRouteAll;
+    std::vector<const double*> fields;
+    bool host = false;
+  };
+  struct RouteFields {  // row-major nx*ny maps; empty where not requested
+    std::vector<uint32_t> sink, axis, diag;
+    std::vector<double> length;
+    std::vector<std::vector<double>> integral, vmin, vmax;  // one per requested field
+    uint32_t rounds = 0;  // doubling rounds of the device route (0 on the host)
+  };
+  RouteFields getRouteFields(const RouteRequest& request);
+  // ... on map b of the batch with goal b as the root (always on the device; the speed is
+  // the one the batch was solved with).  Throws std::invalid_argument for b >= batchCount().
+  RouteFields getRouteFieldsTo(unsigned b, const RouteRequest& request);
+  // whether the last getPaths / getPathStats / getArriving* / getRouteFields ran on the device, and its kernel time (HIP
   // events, ms)
   bool lastPathsOnDevice() const { return last_paths_device_; }
   double lastPathsKernelMs() const { return last_paths_kernel_ms_; }
@@ -701,6 +736,21 @@ class DyMuPathPlanner {
   // getPathStats' copy of the caller's field on the device: dcells_ doubles, allocated on
   // first use and kept until the map buffers go (dropLabels), never re-allocated per call
   double* d_pfield_ = nullptr;
+  // getRouteFields on the device: the caller's fields (dcells_ doubles each), the output
+  // maps (dcells_ elements each: sink, axis, diag; length; per field integral, vmin, vmax)
+  // and the engine's workspace, plain cached device memory.  Each is allocated on first
+  // use and kept until the map buffers go (dropLabels); the workspace alone is replaced,
+  // when a request needs more than it holds.
+  double* d_rfield_[DYMU_PATH_FIELDS] = {};
+  uint32_t* d_rout_u_[3] = {};
+  double* d_rout_len_ = nullptr;
+  double* d_rout_f_[3][DYMU_PATH_FIELDS] = {};
+  void* d_route_ws_ = nullptr;
+  size_t route_ws_bytes_ = 0;
+  void routeFieldsOnDevice(const RouteRequest& rq, const double* map,
+                           const std::vector<dymu_seed>& seeds, RouteFields& out);
+  void routeFieldsOnHost(const RouteRequest& rq, RouteFields& out);
+  void dropRouteBuffers();
   // the batch (computeTotalCostMaps): its goals and the solved stack, plane b at
   // dT_batch_ + b * dymu_batch_plane_rows(ny_) * nx_ (pitch nx_)
   struct BatchGoal {

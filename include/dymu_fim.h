@@ -332,6 +332,81 @@ int dymu_last_arrive_ms(dymu_ctx* ctx, double* ms);
 /* Device time (ms, HIP events) of the last dymu_goal_labels_device, first kernel to last.
  * DYMU_ERR_STATE before the first one. */
 int dymu_last_labels_ms(dymu_ctx* ctx, double* ms);
+/* ---- every cell's node route to the goal (DyMuPathPlanner::getRouteFields) ----
+ * The per-path record of every cell at once, along a route that provably arrives.  The
+ * definition is a function of T alone (nx x ny, pitch ld, nx*ny < 2^31) and of a seed list
+ * (a single goal is one seed with t0 = 0), the same on host and device:
+ *   root      dymu_goal_labels_device's rule: seed k's cell is a root iff its T is bitwise
+ *             t0_k (duplicate cells: the smallest t0, the lowest k among equal ones; a
+ *             dominated seed is no root).  A root is terminal even with a lower neighbour.
+ *   rp(c)     the route parent of a non-root node c with T[c] < +inf: the hop target of
+ *             dymu_arrive_paths_device's step 3 evaluated at n = c -- among the in-grid
+ *             8-neighbours m in the order (i,j-1), (i-1,j), (i+1,j), (i,j+1), (i-1,j-1),
+ *             (i+1,j-1), (i-1,j+1), (i+1,j+1) with T[m] < T[c] strictly, a diagonal only with
+ *             both side nodes finite, the first one of the largest score T[c] - T[m] (a
+ *             diagonal: (T[c] - T[m]) * 0.7071067811865476).  None: c is a dead end.
+ *   route(c)  c, rp(c), rp(rp(c)), ... up to a root or a dead end; T falls strictly along
+ *             it, so it has no cycle.
+ *   no route  T[c] is +inf or NaN, or the route ends in a dead end.
+ * Per cell with a route n_0 = c -> n_1 -> ... -> n_h that ends on root k:
+ *   sink         k
+ *   axis, diag   hops between axis and between diagonal neighbours; h = axis + diag
+ *   length       res * axis + (res * 1.4142135623730951) * diag, in exactly that form
+ *   integral[f]  the sum over k < h of v_f(n_k) * seg_k, seg_k = res or
+ *                res * 1.4142135623730951, counting finite samples only (a sample that does
+ *                not count adds 0.0): dymu_path_stat's left sum on the node route.  The
+ *                order of the additions is the implementation's; a host that sums each cell
+ *                from its parent and the device differ by rounding (at most
+ *                h * 2^-52 * sum |v_f(n_k)| seg_k), and two device calls not at all.
+ *   vmin[f], vmax[f]  over the finite samples at n_0 .. n_h (-0.0 below +0.0); +inf / -inf
+ *                if there are none
+ * A cell without a route gets sink = DYMU_LABEL_NONE, axis = diag = 0, length and integral
+ * NaN, vmin = +inf and vmax = -inf.
+ * What this route is: the hop-only walk, a chain of grid nodes.  It is not the mostly
+ * continuous path dymu_arrive_paths_device returns; length follows the octile metric and
+ * overstates a straight run by up to 8.2 %; and with a goal set, sink can differ from the
+ * 4-neighbour label of dymu_goal_labels_device. */
+typedef struct dymu_route_out {
+  /* maps of nx x ny elements, pitch ld elements (>= nx); any may be NULL: not computed */
+  uint32_t *sink, *axis, *diag;
+  double* length;
+  double* integral[DYMU_PATH_FIELDS];
+  double* vmin[DYMU_PATH_FIELDS];
+  double* vmax[DYMU_PATH_FIELDS];
+  uint64_t ld;
+} dymu_route_out;
+/* The bytes of workspace dymu_route_fields_device needs for these outputs (the pointers of
+ * `out` are only tested against NULL; out NULL: every output of n_fields fields).  0 for
+ * nx*ny = 0 or >= 2^31 and for n_fields > DYMU_PATH_FIELDS.  The doubling keeps two copies
+ * of a 4-byte entry per cell, of the two hop counts if axis, diag or length is asked for,
+ * and per field of the 8-byte aggregates asked for: at most 2 * (12 + 24 n_fields) bytes a
+ * cell.  An integral, vmin or vmax beyond n_fields must be NULL. */
+size_t dymu_route_fields_workspace(uint32_t nx, uint32_t ny, uint32_t n_fields,
+                                   const dymu_route_out* out);
+/* The routes of all cells of dT for the seeds (HOST array) over the fields d_fields[f]
+ * (HOST array of n_fields <= DYMU_PATH_FIELDS device maps, pitch field_ld[f] >= nx, HOST
+ * array; as dymu_path_stats_device takes them) into the device maps of *out.  A NULL output
+ * is not carried through the rounds and costs nothing.  d_workspace: device memory of at
+ * least dymu_route_fields_workspace(...) bytes, 256-byte aligned, the caller's (plain
+ * cached device memory, dymu_device_alloc_cached, serves the random gathers best); the call
+ * allocates and frees nothing map-sized.  *rounds (may be NULL) = doubling rounds run,
+ * about log2 of the longest route (DYMU_ERR_NOT_CONVERGED beyond 32; 31 always suffice).
+ * A batch plane is an ordinary map pointer.  Asynchronous on `stream` but for the reads of
+ * the round counters (one every four rounds): the outputs are complete once the stream
+ * has drained.  One call at a time per context.  DYMU_ERR_ARG: what dymu_goal_labels_device
+ * rejects, dymu_path_stats_device's field-list errors, a NULL out or workspace, out->ld <
+ * nx, a per-field output beyond n_fields, workspace_bytes too small. */
+int dymu_route_fields_device(dymu_ctx* ctx, const double* dT, uint32_t nx, uint32_t ny,
+                             uint64_t ld, double res, const dymu_seed* seeds, uint32_t n_seeds,
+                             const double* const* d_fields, const uint64_t* field_ld,
+                             uint32_t n_fields, const dymu_route_out* out, void* d_workspace,
+                             size_t workspace_bytes, void* stream, uint32_t* rounds);
+/* Device time (ms, HIP events) of the last dymu_route_fields_device, first kernel to last;
+ * waits for it.  DYMU_ERR_STATE before the first one. */
+int dymu_last_route_fields_ms(dymu_ctx* ctx, double* ms);
+/* ... and its parts: stage_ms[0] the init and root kernels, [1] the rounds (the counter
+ * reads between them included), [2] the finalize kernel. */
+int dymu_last_route_fields_stages(dymu_ctx* ctx, double stage_ms[3]);
 
 /* ---- batched solves: many maps in one pass sequence ----
  * A batch is B planes of nx x ny cells stacked into ONE domain of nx x (B * P) cells with

@@ -159,6 +159,20 @@ int dymu_planner_get_arriving_stats(dymu_planner* p, const double* starts_xyzh, 
                                     int host, dymu_arrive_stat* out);
 int dymu_planner_get_arriving_stats_to(dymu_planner* p, uint32_t b, const double* starts_xyzh,
                                        int n, int max_wp, dymu_arrive_stat* out);
+/* getRouteFields (extension, DyMu.hpp): every cell's node route to the
+ * goal at once, as include/dymu_fim.h defines it with dymu_route_out.  fields: n_fields <=
+ * DYMU_PATH_FIELDS row-major ny x nx arrays, a NULL entry being the speed map the solve
+ * used.  out: HOST maps of nx * ny elements (out->ld is ignored: the pitch is nx); a NULL
+ * map is not computed, an integral / vmin / vmax beyond n_fields must be NULL.  The route
+ * is get_paths' unless host is non-zero; dymu_planner_last_paths_on_device / _kernel_ms
+ * report the call.  *rounds (may be NULL) = doubling rounds on the device, 0 on the host.
+ * Returns DYMU_OK or a negative status. */
+int dymu_planner_get_route_fields(dymu_planner* p, const double* const* fields, int n_fields,
+                                  int host, const dymu_route_out* out, uint32_t* rounds);
+/* ... on map b of the batch with goal b as the root (always on the device).  DYMU_ERR_ARG
+ * for b >= batch_count. */
+int dymu_planner_get_route_fields_to(dymu_planner* p, uint32_t b, const double* const* fields,
+                                     int n_fields, const dymu_route_out* out, uint32_t* rounds);
 /* goalI() / goalJ(): the single goal's cell (goal 0 of a goal set); 1 = written, 0 = no
  * goal set yet */
 int dymu_planner_goal_cell(dymu_planner* p, uint32_t* i, uint32_t* j);

@@ -39,6 +39,9 @@ struct dymu_ctx {
   hipEvent_t ev_lab0 = nullptr, ev_lab1 = nullptr;  // around the last dymu_goal_labels_device
   bool lab_timed = false;
   uint32_t* d_lab_cnt = nullptr;  // kLabelRounds + 1 counters of unresolved label entries
+  // the last dymu_route_fields_device: before init, after it, after the rounds, after finalize
+  hipEvent_t ev_route[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool route_timed = false;
   dymu_opts opts{};
   int cu_count = 256;
   uint32_t* d_xchg = nullptr;  // k_exchange's block ticket (zero between launches)
@@ -1720,6 +1723,8 @@ int dymu_destroy(dymu_ctx* c) {
   if (c->ev_lab0) (void)hipEventDestroy(c->ev_lab0);
   if (c->ev_lab1) (void)hipEventDestroy(c->ev_lab1);
   if (c->d_lab_cnt) (void)hipFree(c->d_lab_cnt);
+  for (hipEvent_t e : c->ev_route)
+    if (e) (void)hipEventDestroy(e);
   if (c->d_lists) (void)hipFree(c->d_lists);
   if (c->d_tile_epoch) (void)hipFree(c->d_tile_epoch);
   if (c->d_counts) (void)hipFree(c->d_counts);
@@ -2118,6 +2123,179 @@ int dymu_arrive_paths_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_
 
 int dymu_last_arrive_ms(dymu_ctx* c, double* ms) {
   return elapsed_ms(c, &dymu_ctx::arr_timed, &dymu_ctx::ev_arr0, &dymu_ctx::ev_arr1, ms);
+}
+
+// ---- every cell's node route (route_kernels.hip) ----
+namespace {
+constexpr size_t kRouteAlign = 256;
+constexpr size_t kRouteCntBytes = 256;  // kRouteRounds counters at the workspace's start
+static_assert(sizeof(uint32_t) * kRouteRounds <= kRouteCntBytes, "the counters fit");
+
+// which arrays the doubling carries for these outputs (null `out`: all of n_fields fields)
+struct RouteCarry {
+  bool cnt;
+  bool integ[kPathFields], vmin[kPathFields], vmax[kPathFields];
+};
+RouteCarry route_carry(uint32_t n_fields, const dymu_route_out* out) {
+  RouteCarry k{};
+  k.cnt = !out || out->axis || out->diag || out->length;
+  for (uint32_t f = 0; f < n_fields; ++f) {
+    k.integ[f] = !out || out->integral[f];
+    k.vmin[f] = !out || out->vmin[f];
+    k.vmax[f] = !out || out->vmax[f];
+  }
+  return k;
+}
+// the workspace's layout: the counters, then per carried array its two buffers; returns
+// the bytes used, and with ws the two states
+size_t route_layout(uint64_t n, const RouteCarry& k, char* ws, RouteState st[2]) {
+  size_t off = kRouteCntBytes;
+  auto take = [&](size_t elem, void** a, void** b) {
+    const size_t bytes = (elem * n + kRouteAlign - 1) / kRouteAlign * kRouteAlign;
+    if (ws) {
+      *a = ws + off;
+      *b = ws + off + bytes;
+    }
+    off += 2 * bytes;
+  };
+  RouteState dummy[2]{};
+  RouteState* s = st ? st : dummy;
+  take(4, (void**)&s[0].next, (void**)&s[1].next);
+  if (k.cnt) {
+    take(4, (void**)&s[0].axis, (void**)&s[1].axis);
+    take(4, (void**)&s[0].diag, (void**)&s[1].diag);
+  }
+  for (int f = 0; f < kPathFields; ++f) {
+    if (k.integ[f]) take(8, (void**)&s[0].integ[f], (void**)&s[1].integ[f]);
+    if (k.vmin[f]) take(8, (void**)&s[0].vmin[f], (void**)&s[1].vmin[f]);
+    if (k.vmax[f]) take(8, (void**)&s[0].vmax[f], (void**)&s[1].vmax[f]);
+  }
+  return off;
+}
+bool route_out_ok(uint32_t n_fields, const dymu_route_out* out) {
+  if (!out) return true;
+  for (uint32_t f = n_fields; f < DYMU_PATH_FIELDS; ++f)
+    if (out->integral[f] || out->vmin[f] || out->vmax[f]) return false;
+  return true;
+}
+}  // namespace
+
+size_t dymu_route_fields_workspace(uint32_t nx, uint32_t ny, uint32_t n_fields,
+                                   const dymu_route_out* out) {
+  const uint64_t n = (uint64_t)nx * ny;
+  if (n == 0 || n >= (1ull << 31) || n_fields > DYMU_PATH_FIELDS || !route_out_ok(n_fields, out))
+    return 0;
+  return route_layout(n, route_carry(n_fields, out), nullptr, nullptr);
+}
+
+int dymu_route_fields_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
+                             double res, const dymu_seed* seeds, uint32_t n_seeds,
+                             const double* const* d_fields, const uint64_t* field_ld,
+                             uint32_t n_fields, const dymu_route_out* out, void* d_workspace,
+                             size_t workspace_bytes, void* stream, uint32_t* rounds) {
+  if (!c || !dT || !out || !d_workspace || nx == 0 || ny == 0 || ld < nx || out->ld < nx)
+    return DYMU_ERR_ARG;
+  if ((uint64_t)nx * ny >= (1ull << 31)) return DYMU_ERR_ARG;  // entries hold a cell index + tag
+  if (!(res > 0) || !(res < HUGE_VAL)) return DYMU_ERR_ARG;
+  if (n_fields > DYMU_PATH_FIELDS || (n_fields && (!d_fields || !field_ld))) return DYMU_ERR_ARG;
+  for (uint32_t f = 0; f < n_fields; ++f)
+    if (!d_fields[f] || field_ld[f] < nx) return DYMU_ERR_ARG;
+  if (!route_out_ok(n_fields, out)) return DYMU_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(d_workspace) % kRouteAlign) return DYMU_ERR_ARG;
+  const uint32_t n = nx * ny;
+  const RouteCarry carry = route_carry(n_fields, out);
+  RouteState s[2]{};
+  if (route_layout(n, carry, static_cast<char*>(d_workspace), s) > workspace_bytes)
+    return DYMU_ERR_ARG;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  const GoalSeed* d_seeds = nullptr;
+  int rc = stage_seeds(c, nx, ny, seeds, n_seeds, st, &d_seeds, nullptr);
+  if (rc) return rc;
+  for (hipEvent_t& e : c->ev_route)
+    if (!e) HIPC(c, hipEventCreate(&e));
+  uint32_t* d_cnt = static_cast<uint32_t*>(d_workspace);
+  RouteInitArgs ia{};
+  ia.T = dT;
+  ia.ld = (int64_t)ld;
+  ia.nx = nx;
+  ia.ny = ny;
+  ia.res = res;
+  for (uint32_t f = 0; f < n_fields; ++f) {
+    // a field none of whose aggregates is asked for is not sampled
+    if (!carry.integ[f] && !carry.vmin[f] && !carry.vmax[f]) continue;
+    ia.field[f] = d_fields[f];
+    ia.field_ld[f] = (int64_t)field_ld[f];
+  }
+  ia.s0 = s[0];
+  ia.s1 = s[1];
+  c->route_timed = false;
+  HIPC(c, hipEventRecord(c->ev_route[0], st));
+  HIPC(c, hipMemsetAsync(d_cnt, 0, kRouteCntBytes, st));
+  HIPC(c, launch_route_init(ia, d_seeds, n_seeds, st));
+  HIPC(c, hipEventRecord(c->ev_route[1], st));
+  // rounds in batches of 4 between read-backs of the counters; a round launched behind
+  // the one that closed the last entry returns at once.  Round r reads buffer r & 1.
+  uint32_t launched = 0, done = 0;
+  uint32_t h_cnt[kRouteRounds];
+  while (done == 0 && launched < kRouteRounds) {
+    const uint32_t r0 = launched;
+    for (uint32_t k = 0; k < 4 && launched < kRouteRounds; ++k, ++launched)
+      HIPC(c, launch_route_round(s[launched & 1u], s[(launched + 1u) & 1u], n, d_cnt, launched, st));
+    HIPC(c, hipStreamSynchronize(st));
+    HIPC(c, hipMemcpy(h_cnt + r0, d_cnt + r0, sizeof(uint32_t) * (launched - r0),
+                      hipMemcpyDeviceToHost));
+    for (uint32_t r = r0; r < launched && done == 0; ++r)
+      if (h_cnt[r] == 0) done = r + 1;
+  }
+  HIPC(c, hipEventRecord(c->ev_route[2], st));
+  const uint32_t ran = done ? done : launched;
+  RouteFinalArgs fa{};
+  fa.nx = nx;
+  fa.ny = ny;
+  fa.res = res;
+  for (int f = 0; f < kPathFields; ++f) {
+    fa.field[f] = ia.field[f];
+    fa.field_ld[f] = ia.field_ld[f];
+    fa.o_integ[f] = out->integral[f];
+    fa.o_vmin[f] = out->vmin[f];
+    fa.o_vmax[f] = out->vmax[f];
+  }
+  fa.s = s[ran & 1u];  // the state after `ran` rounds
+  fa.seeds = d_seeds;
+  fa.n_seeds = n_seeds;
+  fa.o_sink = out->sink;
+  fa.o_axis = out->axis;
+  fa.o_diag = out->diag;
+  fa.o_length = out->length;
+  fa.o_ld = (int64_t)out->ld;
+  HIPC(c, launch_route_final(fa, st));
+  HIPC(c, hipEventRecord(c->ev_route[3], st));
+  c->route_timed = true;
+  if (rounds) *rounds = ran;
+  if (done == 0) {
+    c->last_error = "route fields: round cap reached";
+    return DYMU_ERR_NOT_CONVERGED;
+  }
+  return DYMU_OK;
+}
+
+int dymu_last_route_fields_ms(dymu_ctx* c, double* ms) {
+  if (!c || !ms) return DYMU_ERR_ARG;
+  if (!c->route_timed) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  return event_ms(c, c->ev_route[0], c->ev_route[3], ms);
+}
+
+int dymu_last_route_fields_stages(dymu_ctx* c, double stage_ms[3]) {
+  if (!c || !stage_ms) return DYMU_ERR_ARG;
+  if (!c->route_timed) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  for (int k = 0; k < 3; ++k) {
+    const int rc = event_ms(c, c->ev_route[k], c->ev_route[k + 1], &stage_ms[k]);
+    if (rc) return rc;
+  }
+  return DYMU_OK;
 }
 
 int dymu_solve_seeds_device(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_t ny,

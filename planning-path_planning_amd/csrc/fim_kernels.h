@@ -493,6 +493,52 @@ hipError_t launch_label_jump(uint32_t* L, uint32_t n, uint32_t* cnt, uint32_t ro
                              hipStream_t st);
 hipError_t launch_label_strip(uint32_t* L, uint32_t n, hipStream_t st);
 
+// every cell's node route to the goal (route_kernels.hip): the hop of the
+// arriving descent at every node, its aggregates by synchronous pointer doubling.
+// RouteState is one of the two buffers of the doubling, SoA over the nx * ny cells (pitch
+// nx); an array that is not carried is null.
+constexpr uint32_t kRouteRounds = 32;  // 31 suffice for nx * ny < 2^31
+struct RouteState {
+  uint32_t* next;  // a cell index, or a terminal entry (top bit set: seed index / NONE)
+  uint32_t *axis, *diag;
+  double* integ[kPathFields];
+  double* vmin[kPathFields];
+  double* vmax[kPathFields];
+};
+struct RouteInitArgs {
+  const double* T;  // total cost, pitch ld
+  int64_t ld;
+  uint32_t nx, ny;
+  double res;
+  const double* field[kPathFields];  // null: not sampled
+  int64_t field_ld[kPathFields];
+  RouteState s0, s1;
+};
+struct RouteFinalArgs {
+  uint32_t nx, ny;
+  double res;
+  const double* field[kPathFields];
+  int64_t field_ld[kPathFields];
+  RouteState s;  // the final state
+  const GoalSeed* seeds;
+  uint32_t n_seeds;
+  // the outputs, pitch o_ld elements; null: not written
+  uint32_t *o_sink, *o_axis, *o_diag;
+  double* o_length;
+  double* o_integ[kPathFields];
+  double* o_vmin[kPathFields];
+  double* o_vmax[kPathFields];
+  int64_t o_ld;
+};
+// state 0 into s0, what a round needs of it into s1, the roots marked in both
+hipError_t launch_route_init(const RouteInitArgs& a, const GoalSeed* seeds, uint32_t n_seeds,
+                             hipStream_t st);
+// dst = one doubling of src; cnt[round] = entries still open after it; a round after a 0
+// does nothing
+hipError_t launch_route_round(const RouteState& src, const RouteState& dst, uint32_t n,
+                              uint32_t* cnt, uint32_t round, hipStream_t st);
+hipError_t launch_route_final(const RouteFinalArgs& a, hipStream_t st);
+
 // batched solves (batch_kernels.hip): `planes` maps of nx x ny stacked at
 // a plane pitch of P rows (dymu_batch_plane_rows), rows ny .. P-1 of each being +inf walls
 // dst (pitch ld, planes * P rows) <- plane b from src + b * src_plane_stride (pitch src_ld;

@@ -2784,6 +2784,266 @@ void DyMuPathPlanner::pathStatsOnDevice(const std::vector<base::Waypoint>& start
   if (dymu_last_path_stats_ms(ctx_, &ms) == DYMU_OK) last_paths_kernel_ms_ = ms;
 }
 
+// ---- getRouteFields: every cell's node route at once (extension) ----
+#pragma weak dymu_route_fields_device
+#pragma weak dymu_route_fields_workspace
+#pragma weak dymu_last_route_fields_ms
+#pragma weak dymu_device_alloc_cached
+
+namespace {
+// include/dymu_fim.h's minimum and maximum: -0.0 below +0.0, so the order of folds does not show
+inline double route_min(double a, double b) { return (b < a || (b == a && std::signbit(b))) ? b : a; }
+inline double route_max(double a, double b) { return (b > a || (b == a && !std::signbit(b))) ? b : a; }
+inline bool route_finite(double v) { return v > -kInf && v < kInf; }
+void route_check_request(const DyMuPathPlanner::RouteRequest& rq) {
+  if (rq.fields.size() > DYMU_PATH_FIELDS)
+    throw std::invalid_argument("getRouteFields: at most DYMU_PATH_FIELDS fields");
+}
+// the output maps of a request, every cell without a route
+void route_empty(const DyMuPathPlanner::RouteRequest& rq, uint64_t n,
+                 DyMuPathPlanner::RouteFields& out) {
+  typedef DyMuPathPlanner P;
+  const size_t nf = rq.fields.size();
+  if (rq.outputs & P::kRouteSink) out.sink.assign(n, DYMU_LABEL_NONE);
+  if (rq.outputs & P::kRouteAxis) out.axis.assign(n, 0u);
+  if (rq.outputs & P::kRouteDiag) out.diag.assign(n, 0u);
+  if (rq.outputs & P::kRouteLength) out.length.assign(n, std::nan(""));
+  if (rq.outputs & P::kRouteIntegral)
+    out.integral.assign(nf, std::vector<double>(n, std::nan("")));
+  if (rq.outputs & P::kRouteMin) out.vmin.assign(nf, std::vector<double>(n, kInf));
+  if (rq.outputs & P::kRouteMax) out.vmax.assign(nf, std::vector<double>(n, -kInf));
+}
+}  // namespace
+
+DyMuPathPlanner::RouteFields DyMuPathPlanner::getRouteFields(const RouteRequest& rq) {
+  route_check_request(rq);
+  RouteFields out;
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  const uint64_t n = (uint64_t)nx_ * ny_;
+  if (!n || !has_goal_) {
+    route_empty(rq, n, out);
+    return out;
+  }
+  bool speed = false;
+  for (const double* f : rq.fields) speed = speed || !f;
+  if (!rq.host && ctx_ && dT_ && dev_map_current_ && n < (1ull << 31) &&
+      (!speed || (dF_ && speed_valid_)) && &dymu_route_fields_device &&
+      &dymu_route_fields_workspace && &dymu_last_route_fields_ms && &dymu_device_alloc_cached) {
+    routeFieldsOnDevice(rq, dT_, seedList(), out);
+    last_paths_device_ = true;
+    return out;
+  }
+  routeFieldsOnHost(rq, out);
+  return out;
+}
+
+// The definition of include/dymu_fim.h on the host mirror: roots first, then the finite
+// cells in ascending total cost, each from its parent (a parent is strictly lower, so it
+// is done by then) -- the integral as w(c) + integral[rp(c)].
+void DyMuPathPlanner::routeFieldsOnHost(const RouteRequest& rq, RouteFields& out) {
+  const uint64_t n = (uint64_t)nx_ * ny_;
+  const size_t nf = rq.fields.size();
+  fetchAll();
+  const double* t = total_cost_.data();
+  // a null field is the speed map the solve used (getPathStats' slot 0): the packed copy,
+  // or without one the node's own speed, as the host descent's record takes it
+  bool speed = false;
+  for (const double* f : rq.fields) speed = speed || !f;
+  if (speed && !speed_valid_) syncGlobalRisk();
+  const double* f0 = speed_valid_ ? speed_.data() : nullptr;
+  std::vector<const double*> fld(rq.fields);
+  for (const double*& f : fld)
+    if (!f) f = f0;
+  // the whole record is kept while the pass runs; what was not asked for is dropped after
+  std::vector<uint32_t> sink(n, DYMU_LABEL_NONE), axis(n, 0u), diag(n, 0u);
+  std::vector<std::vector<double>> integ(nf, std::vector<double>(n, 0.0)),
+      vmin(nf, std::vector<double>(n, kInf)), vmax(nf, std::vector<double>(n, -kInf));
+  auto sample = [&](size_t f, uint64_t c, double& v) {
+    v = fld[f] ? fld[f][c] : is_obstacle_[c] ? kInf : nodeSpeed(c);
+    return route_finite(v);
+  };
+  const std::vector<dymu_seed> seeds = seedList();
+  std::vector<uint8_t> root(n, 0);
+  for (size_t k = seeds.size(); k-- > 0;) {  // descending: the lowest k is written last
+    const uint64_t c = idx(seeds[k].i, seeds[k].j);
+    if (std::memcmp(&t[c], &seeds[k].t0, sizeof(double)) != 0) continue;  // dominated
+    sink[c] = (uint32_t)k;
+    root[c] = 1;
+  }
+  for (uint64_t c = 0; c < n; ++c)
+    if (root[c])
+      for (size_t f = 0; f < nf; ++f) {
+        double v;
+        if (sample(f, c, v)) vmin[f][c] = vmax[f][c] = v;
+      }
+  std::vector<std::pair<double, uint64_t>> order;
+  for (uint64_t c = 0; c < n; ++c)
+    if (t[c] < kInf && !root[c]) order.emplace_back(t[c], c);
+  parallel_sort(order);
+  const double seg_d = global_res_ * 1.4142135623730951;
+  const int64_t nx = nx_, ny = ny_;
+  for (const auto& e : order) {
+    const uint64_t c = e.second;
+    const int64_t i = (int64_t)(c % nx_), j = (int64_t)(c / nx_);
+    const double tn = e.first;
+    // a neighbour off the grid is +inf: no test accepts it
+    auto at = [&](int di, int dj) {
+      const int64_t a = i + di, b = j + dj;
+      return a >= 0 && a < nx && b >= 0 && b < ny ? t[b * nx + a] : kInf;
+    };
+    double best = -1.0;
+    int bi = 0, bj = 0;
+    auto hop_try = [&](bool ok, int di, int dj) {
+      const double tm = at(di, dj);
+      if (ok && tm < tn) {
+        const double s = (di && dj) ? (tn - tm) * 0.7071067811865476 : tn - tm;
+        if (s > best) best = s, bi = di, bj = dj;
+      }
+    };
+    const bool w = at(-1, 0) < kInf, ea = at(1, 0) < kInf, s = at(0, -1) < kInf,
+               no = at(0, 1) < kInf;
+    hop_try(true, 0, -1);
+    hop_try(true, -1, 0);
+    hop_try(true, 1, 0);
+    hop_try(true, 0, 1);
+    hop_try(w && s, -1, -1);
+    hop_try(ea && s, 1, -1);
+    hop_try(w && no, -1, 1);
+    hop_try(ea && no, 1, 1);
+    if (bi == 0 && bj == 0) continue;  // a dead end
+    const uint64_t p = (uint64_t)((j + bj) * nx + (i + bi));
+    if (sink[p] == DYMU_LABEL_NONE) continue;  // drains to a dead end
+    const bool dg = bi != 0 && bj != 0;
+    sink[c] = sink[p];
+    axis[c] = axis[p] + (dg ? 0u : 1u);
+    diag[c] = diag[p] + (dg ? 1u : 0u);
+    const double seg = dg ? seg_d : global_res_;
+    for (size_t f = 0; f < nf; ++f) {
+      double v = 0.0;
+      const bool cnt = sample(f, c, v);
+      integ[f][c] = (cnt ? v * seg : 0.0) + integ[f][p];
+      vmin[f][c] = route_min(cnt ? v : kInf, vmin[f][p]);
+      vmax[f][c] = route_max(cnt ? v : -kInf, vmax[f][p]);
+    }
+  }
+  if (rq.outputs & kRouteLength) {
+    out.length.resize(n);
+    for (uint64_t c = 0; c < n; ++c)
+      out.length[c] = sink[c] == DYMU_LABEL_NONE
+                          ? std::nan("")
+                          : global_res_ * (double)axis[c] + seg_d * (double)diag[c];
+  }
+  for (uint64_t c = 0; c < n; ++c)
+    if (sink[c] == DYMU_LABEL_NONE)
+      for (size_t f = 0; f < nf; ++f) {
+        integ[f][c] = std::nan("");
+        vmin[f][c] = kInf;
+        vmax[f][c] = -kInf;
+      }
+  if (rq.outputs & kRouteSink) out.sink.swap(sink);
+  if (rq.outputs & kRouteAxis) out.axis.swap(axis);
+  if (rq.outputs & kRouteDiag) out.diag.swap(diag);
+  if (rq.outputs & kRouteIntegral) out.integral.swap(integ);
+  if (rq.outputs & kRouteMin) out.vmin.swap(vmin);
+  if (rq.outputs & kRouteMax) out.vmax.swap(vmax);
+}
+
+// The device route: the caller's fields up, dymu_route_fields_device into the planner's
+// output maps, the requested maps down.
+void DyMuPathPlanner::routeFieldsOnDevice(const RouteRequest& rq, const double* map,
+                                          const std::vector<dymu_seed>& seeds, RouteFields& out) {
+  const uint64_t n = (uint64_t)nx_ * ny_;
+  const uint32_t nf = (uint32_t)rq.fields.size();
+  auto check = [&](int rc, const char* what) {
+    if (rc != DYMU_OK)
+      throw std::runtime_error(std::string("dymu: getRouteFields ") + what + " failed: " +
+                               dymu_strerror(rc) + " " + dymu_last_error(ctx_));
+  };
+  auto ensure = [&](auto*& p, size_t elem) {
+    if (p) return;
+    void* q = nullptr;
+    check(dymu_device_alloc_cached(ctx_, elem * dcells_, &q), "allocation");
+    p = static_cast<std::remove_reference_t<decltype(p)>>(q);
+  };
+  const double* fields[DYMU_PATH_FIELDS] = {};
+  uint64_t pitch[DYMU_PATH_FIELDS] = {};
+  for (uint32_t f = 0; f < nf; ++f) {
+    pitch[f] = nx_;
+    if (!rq.fields[f]) {
+      fields[f] = dF_;
+      continue;
+    }
+    ensure(d_rfield_[f], sizeof(double));
+    check(dymu_memcpy_h2d(ctx_, d_rfield_[f], rq.fields[f], sizeof(double) * n), "field upload");
+    fields[f] = d_rfield_[f];
+  }
+  dymu_route_out o{};
+  o.ld = nx_;
+  const uint32_t ubit[3] = {kRouteSink, kRouteAxis, kRouteDiag};
+  uint32_t** const uout[3] = {&o.sink, &o.axis, &o.diag};
+  for (int k = 0; k < 3; ++k)
+    if (rq.outputs & ubit[k]) {
+      ensure(d_rout_u_[k], sizeof(uint32_t));
+      *uout[k] = d_rout_u_[k];
+    }
+  if (rq.outputs & kRouteLength) {
+    ensure(d_rout_len_, sizeof(double));
+    o.length = d_rout_len_;
+  }
+  const uint32_t fbit[3] = {kRouteIntegral, kRouteMin, kRouteMax};
+  double** const fout[3] = {o.integral, o.vmin, o.vmax};
+  for (int k = 0; k < 3; ++k)
+    for (uint32_t f = 0; f < nf; ++f)
+      if (rq.outputs & fbit[k]) {
+        ensure(d_rout_f_[k][f], sizeof(double));
+        fout[k][f] = d_rout_f_[k][f];
+      }
+  const size_t need = dymu_route_fields_workspace(nx_, ny_, nf, &o);
+  if (!need) check(DYMU_ERR_ARG, "workspace query");
+  if (need > route_ws_bytes_) {
+    if (d_route_ws_) (void)dymu_device_free(ctx_, d_route_ws_);
+    d_route_ws_ = nullptr;
+    route_ws_bytes_ = 0;
+    check(dymu_device_alloc_cached(ctx_, need, &d_route_ws_), "workspace allocation");
+    route_ws_bytes_ = need;
+  }
+  check(dymu_route_fields_device(ctx_, map, nx_, ny_, nx_, global_res_, seeds.data(),
+                                 (uint32_t)seeds.size(), fields, pitch, nf, &o, d_route_ws_,
+                                 route_ws_bytes_, nullptr, &out.rounds),
+        "kernels");
+  auto down = [&](auto& v, const void* d) {
+    v.resize(n);
+    check(dymu_memcpy_d2h(ctx_, v.data(), d, sizeof(v[0]) * n), "download");
+  };
+  if (o.sink) down(out.sink, o.sink);
+  if (o.axis) down(out.axis, o.axis);
+  if (o.diag) down(out.diag, o.diag);
+  if (o.length) down(out.length, o.length);
+  std::vector<std::vector<double>>* const hv[3] = {&out.integral, &out.vmin, &out.vmax};
+  for (int k = 0; k < 3; ++k)
+    if (rq.outputs & fbit[k]) {
+      hv[k]->resize(nf);
+      for (uint32_t f = 0; f < nf; ++f) down((*hv[k])[f], fout[k][f]);
+    }
+  double ms = 0.0;
+  if (dymu_last_route_fields_ms(ctx_, &ms) == DYMU_OK) last_paths_kernel_ms_ = ms;
+}
+
+void DyMuPathPlanner::dropRouteBuffers() {
+  auto drop = [&](auto*& p) {
+    if (p && ctx_) (void)dymu_device_free(ctx_, p);
+    p = nullptr;
+  };
+  for (auto& p : d_rfield_) drop(p);
+  for (auto& p : d_rout_u_) drop(p);
+  drop(d_rout_len_);
+  for (auto& row : d_rout_f_)
+    for (auto& p : row) drop(p);
+  drop(d_route_ws_);
+  route_ws_bytes_ = 0;
+}
+
 // ---- goal sets (extension) ----
 
 // The goal-set entries of the engine C-ABI: null with an engine that predates them
@@ -2945,6 +3205,7 @@ void DyMuPathPlanner::dropLabels() {
   // getPathStats' field buffer goes where the label map goes: with the map buffers
   if (d_pfield_ && ctx_) (void)dymu_device_free(ctx_, d_pfield_);
   d_pfield_ = nullptr;
+  dropRouteBuffers();  // ... and getRouteFields' buffers
 }
 
 void DyMuPathPlanner::ensureDeviceLabels() {
@@ -3924,6 +4185,24 @@ std::vector<DyMuPathPlanner::ArriveStats> DyMuPathPlanner::getArrivingStatsTo(
     arriveStatsOnDevice(starts, out, max_wp, &tgt);
     last_paths_device_ = true;
   }
+  return out;
+}
+
+DyMuPathPlanner::RouteFields DyMuPathPlanner::getRouteFieldsTo(unsigned b,
+                                                              const RouteRequest& rq) {
+  route_check_request(rq);
+  if (b >= batch_goals_.size() || !ctx_ || !dT_batch_ || !dF_ ||
+      (uint64_t)nx_ * ny_ >= (1ull << 31) || !&dymu_route_fields_device ||
+      !&dymu_route_fields_workspace || !&dymu_last_route_fields_ms ||
+      !&dymu_device_alloc_cached || !refreshBatch())
+    throw std::invalid_argument("getRouteFieldsTo: no such map in the batch");
+  RouteFields out;
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  const BatchGoal& g = batch_goals_[b];
+  routeFieldsOnDevice(rq, dT_batch_ + (uint64_t)b * dymu_batch_plane_rows(ny_) * nx_,
+                      {dymu_seed{g.i, g.j, 0.0}}, out);
+  last_paths_device_ = true;
   return out;
 }
 

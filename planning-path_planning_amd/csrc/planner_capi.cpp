@@ -642,6 +642,64 @@ int dymu_planner_get_arriving_stats_to(dymu_planner* p, uint32_t b, const double
   });
 }
 
+namespace {
+// a flat route request: the outputs are the non-NULL maps of `out`; false: rejected
+bool route_request(const double* const* fields, int n_fields, const dymu_route_out* out,
+                   DyMuPathPlanner::RouteRequest& rq) {
+  typedef DyMuPathPlanner P;
+  if (!out || n_fields < 0 || n_fields > DYMU_PATH_FIELDS || (n_fields && !fields)) return false;
+  rq.outputs = (out->sink ? P::kRouteSink : 0u) | (out->axis ? P::kRouteAxis : 0u) |
+               (out->diag ? P::kRouteDiag : 0u) | (out->length ? P::kRouteLength : 0u);
+  for (int f = 0; f < DYMU_PATH_FIELDS; ++f) {
+    if (f >= n_fields && (out->integral[f] || out->vmin[f] || out->vmax[f])) return false;
+    if (f >= n_fields) continue;
+    // a per-field output is computed for every field or for none
+    if (out->integral[f]) rq.outputs |= P::kRouteIntegral;
+    if (out->vmin[f]) rq.outputs |= P::kRouteMin;
+    if (out->vmax[f]) rq.outputs |= P::kRouteMax;
+  }
+  rq.fields.assign(fields, fields + n_fields);
+  return true;
+}
+void route_copy(const DyMuPathPlanner::RouteFields& r, int n_fields, const dymu_route_out* out) {
+  if (out->sink) std::copy(r.sink.begin(), r.sink.end(), out->sink);
+  if (out->axis) std::copy(r.axis.begin(), r.axis.end(), out->axis);
+  if (out->diag) std::copy(r.diag.begin(), r.diag.end(), out->diag);
+  if (out->length) std::copy(r.length.begin(), r.length.end(), out->length);
+  for (int f = 0; f < n_fields; ++f) {
+    if (out->integral[f]) std::copy(r.integral[f].begin(), r.integral[f].end(), out->integral[f]);
+    if (out->vmin[f]) std::copy(r.vmin[f].begin(), r.vmin[f].end(), out->vmin[f]);
+    if (out->vmax[f]) std::copy(r.vmax[f].begin(), r.vmax[f].end(), out->vmax[f]);
+  }
+}
+}  // namespace
+
+int dymu_planner_get_route_fields(dymu_planner* p, const double* const* fields, int n_fields,
+                                  int host, const dymu_route_out* out, uint32_t* rounds) {
+  DyMuPathPlanner::RouteRequest rq;
+  if (!p || !route_request(fields, n_fields, out, rq)) return DYMU_ERR_ARG;
+  rq.host = host != 0;
+  return guarded([&] {
+    const auto r = p->pl.getRouteFields(rq);
+    route_copy(r, n_fields, out);
+    if (rounds) *rounds = r.rounds;
+    return DYMU_OK;
+  });
+}
+
+int dymu_planner_get_route_fields_to(dymu_planner* p, uint32_t b, const double* const* fields,
+                                     int n_fields, const dymu_route_out* out, uint32_t* rounds) {
+  DyMuPathPlanner::RouteRequest rq;
+  if (!p || !route_request(fields, n_fields, out, rq) || b >= p->pl.batchCount())
+    return DYMU_ERR_ARG;
+  return guarded([&] {
+    const auto r = p->pl.getRouteFieldsTo(b, rq);
+    route_copy(r, n_fields, out);
+    if (rounds) *rounds = r.rounds;
+    return DYMU_OK;
+  });
+}
+
 int dymu_planner_goal_cell(dymu_planner* p, uint32_t* i, uint32_t* j) {
   if (!p || !i || !j) return DYMU_ERR_ARG;
   if (!p->pl.hasGoal()) return 0;

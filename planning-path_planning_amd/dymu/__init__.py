@@ -107,6 +107,17 @@ class DymuReduceSummary(ctypes.Structure):
                 "min_plane": self.min_plane, "n_finite": self.n_finite}
 
 
+class DymuRouteOut(ctypes.Structure):
+    """dymu_route_out (include/dymu_fim.h): output maps, NULL = not computed."""
+    _fields_ = [("sink", ctypes.c_void_p), ("axis", ctypes.c_void_p), ("diag", ctypes.c_void_p),
+                ("length", ctypes.c_void_p), ("integral", ctypes.c_void_p * 4),
+                ("vmin", ctypes.c_void_p * 4), ("vmax", ctypes.c_void_p * 4),
+                ("ld", ctypes.c_uint64)]
+
+
+ROUTE_OUTPUTS = ("sink", "axis", "diag", "length", "integral", "vmin", "vmax")
+
+
 class DymuCorridorInfo(ctypes.Structure):
     """dymu_corridor_info (include/dymu_planner.h)."""
     _fields_ = [("d_min", ctypes.c_double), ("min_i", ctypes.c_uint32), ("min_j", ctypes.c_uint32),
@@ -271,6 +282,13 @@ FIM_SYMBOLS = {
                                         _vp, _vp, _u32, ctypes.c_double, _vp, _u32, _u32, _u32,
                                         _vp, _vp, _vp, _vp]),
     "dymu_last_arrive_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_route_fields_workspace": (ctypes.c_size_t, [_u32, _u32, _u32,
+                                                      ctypes.POINTER(DymuRouteOut)]),
+    "dymu_route_fields_device": (_i32, [_vp, _vp, _u32, _u32, _u64, ctypes.c_double, _vp, _u32,
+                                        _vp, _vp, _u32, ctypes.POINTER(DymuRouteOut), _vp,
+                                        ctypes.c_size_t, _vp, ctypes.POINTER(_u32)]),
+    "dymu_last_route_fields_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_last_route_fields_stages": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "dymu_batch_plane_rows": (_u32, [_u32]),
     "dymu_stack_speed_device": (_i32, [_vp, _vp, _u64, _u64, _u32, _u32, _u32, _vp, _u64, _vp]),
     "dymu_solve_batch_device": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _u32, _vp,
@@ -909,6 +927,53 @@ class Engine:
             return None
         return {"box": (r.i0, r.j0, r.i1, r.j1), "n_range": r.n_range, "r_const": r.r_const}
 
+    # -- every cell's node route to the goal --
+    @staticmethod
+    def route_out(ld: int, sink: int = 0, axis: int = 0, diag: int = 0, length: int = 0,
+                  integral=(), vmin=(), vmax=()) -> DymuRouteOut:
+        """A dymu_route_out of device (or host) pointers; 0 / missing: not computed."""
+        o = DymuRouteOut(sink or None, axis or None, diag or None, length or None)
+        for name, ptrs in (("integral", integral), ("vmin", vmin), ("vmax", vmax)):
+            arr = getattr(o, name)
+            for f, q in enumerate(ptrs):
+                arr[f] = q or None
+        o.ld = ld
+        return o
+
+    def route_fields_workspace(self, nx: int, ny: int, n_fields: int, out=None) -> int:
+        """dymu_route_fields_workspace: the bytes route_fields needs for the outputs of
+        `out` (a DymuRouteOut; None: every output of n_fields fields); 0: rejected."""
+        return int(self._lib.dymu_route_fields_workspace(
+            nx, ny, n_fields, ctypes.byref(out) if out is not None else None))
+
+    def route_fields(self, dT: int, nx: int, ny: int, ld: int, res: float, seeds, fields, out,
+                     workspace: int, workspace_bytes: int, stream: int = 0) -> int:
+        """dymu_route_fields_device on raw pointers: the routes of all cells of the device
+        map dT for the seeds (i, j[, t0]) over fields, pairs (device pointer, pitch), into
+        the device maps of `out` (route_out); returns the doubling rounds run.  Asynchronous
+        on the stream: d2h (context stream) or last_route_fields_ms() waits for it."""
+        a = self._seeds(seeds)
+        fp = (_vp * max(len(fields), 1))(*[int(f[0]) for f in fields])
+        fl = (_u64 * max(len(fields), 1))(*[int(f[1]) for f in fields])
+        rounds = _u32()
+        _check(self._lib.dymu_route_fields_device(
+            self.ctx, dT, nx, ny, ld, res, a.ctypes.data, len(a), ctypes.cast(fp, _vp),
+            ctypes.cast(fl, _vp), len(fields), ctypes.byref(out), workspace or None,
+            workspace_bytes, stream or None, ctypes.byref(rounds)), self.ctx)
+        return rounds.value
+
+    def last_route_fields_ms(self) -> float:
+        """Device time of the last route_fields, first kernel to last (waits for it)."""
+        ms = ctypes.c_double()
+        _check(self._lib.dymu_last_route_fields_ms(self.ctx, ctypes.byref(ms)), self.ctx)
+        return ms.value
+
+    def last_route_fields_stages(self):
+        """(init, rounds, finalize) device times of the last route_fields, ms."""
+        ms = (ctypes.c_double * 3)()
+        _check(self._lib.dymu_last_route_fields_stages(self.ctx, ms), self.ctx)
+        return tuple(ms)
+
     def alloc(self, nbytes: int) -> int:
         p = _vp()
         _check(self._lib.dymu_device_alloc(self.ctx, nbytes, ctypes.byref(p)), self.ctx)
@@ -1199,6 +1264,11 @@ PLANNER_SYMBOLS = {
                                                   _vp]),
     "dymu_planner_get_arriving_stats": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "dymu_planner_get_arriving_stats_to": (_i32, [_vp, _u32, _vp, _i32, _i32, _vp]),
+    "dymu_planner_get_route_fields": (_i32, [_vp, _vp, _i32, _i32, ctypes.POINTER(DymuRouteOut),
+                                             ctypes.POINTER(_u32)]),
+    "dymu_planner_get_route_fields_to": (_i32, [_vp, _u32, _vp, _i32,
+                                                ctypes.POINTER(DymuRouteOut),
+                                                ctypes.POINTER(_u32)]),
     "dymu_planner_goal_cell": (_i32, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "dymu_planner_get_locomotion_mode": (_i32, [_vp, _d, _d, _d, _d, ctypes.c_char_p, _i32]),
     "dymu_planner_set_global_risk": (_i32, [_vp, _d, _d]),
@@ -1710,6 +1780,65 @@ class Planner:
         _b_int(self._lib.dymu_planner_get_arriving_stats_to(self.h, b, s.ctypes.data, len(s),
                                                             max_wp, out.ctypes.data))
         return out
+
+    # -- every cell's node route to the goal (DyMuPathPlanner::getRouteFields) --
+    def _route_fields(self, call, fields, outputs):
+        fields = [] if fields is None else list(fields)
+        if len(fields) > PATH_FIELDS:
+            raise ValueError(f"at most {PATH_FIELDS} fields")
+        bad = set(outputs) - set(ROUTE_OUTPUTS)
+        if bad:
+            raise ValueError(f"unknown outputs {sorted(bad)}; the outputs are {ROUTE_OUTPUTS}")
+        keep = []  # the caller's arrays, alive across the call
+        fp = (_vp * max(len(fields), 1))()
+        for f, a in enumerate(fields):
+            if isinstance(a, str):
+                if a != "speed":
+                    raise ValueError(f"unknown field {a!r}; by name there is 'speed'")
+                fp[f] = None
+            else:
+                keep.append(self._grid(a))
+                fp[f] = keep[-1].ctypes.data
+        res = {}
+        o = DymuRouteOut()
+        o.ld = self.nx
+        for name, dt in (("sink", np.uint32), ("axis", np.uint32), ("diag", np.uint32),
+                         ("length", np.float64)):
+            if name in outputs:
+                res[name] = np.empty((self.ny, self.nx), dtype=dt)
+                setattr(o, name, res[name].ctypes.data)
+        for name in ("integral", "vmin", "vmax"):
+            if name in outputs:
+                res[name] = np.empty((len(fields), self.ny, self.nx))
+                arr = getattr(o, name)
+                for f in range(len(fields)):
+                    arr[f] = res[name][f].ctypes.data
+        rounds = _u32()
+        _b_int(call(ctypes.cast(fp, _vp), len(fields), o, rounds))
+        res["rounds"] = rounds.value
+        return res
+
+    def getRouteFields(self, fields=None, outputs=ROUTE_OUTPUTS, host: bool = False) -> dict:
+        """Every cell's node route to the goal at once (DyMuPathPlanner::getRouteFields,
+        DESIGN.md s5.16): a dict of [ny, nx] maps -- 'sink' (uint32, LABEL_NONE: no route),
+        'axis' and 'diag' (hops between axis / diagonal neighbours), 'length' (octile, NaN
+        without a route) -- and, stacked [len(fields), ny, nx], 'integral', 'vmin', 'vmax'
+        along the route; plus 'rounds'.  fields: up to PATH_FIELDS entries, each 'speed'
+        (the speed map the solve used) or a [ny, nx] array.  outputs: the names wanted;
+        only they are computed.  The route is the hop-only walk of getArrivingPaths, a chain
+        of grid nodes, not its mostly continuous path.  On the GPU while the device map is
+        current, else -- or with host=True -- on the host."""
+        return self._route_fields(
+            lambda fp, n, o, r: self._lib.dymu_planner_get_route_fields(
+                self.h, fp, n, int(bool(host)), ctypes.byref(o), ctypes.byref(r)),
+            fields, outputs)
+
+    def getRouteFieldsTo(self, b: int, fields=None, outputs=ROUTE_OUTPUTS) -> dict:
+        """getRouteFields on map b of the batch, with goal b as the root."""
+        return self._route_fields(
+            lambda fp, n, o, r: self._lib.dymu_planner_get_route_fields_to(
+                self.h, b, fp, n, ctypes.byref(o), ctypes.byref(r)),
+            fields, outputs)
 
     def goalCell(self):
         """(goalI(), goalJ()): the single goal's cell (goal 0 of a goal set), or None."""
