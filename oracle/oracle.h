@@ -12,12 +12,11 @@
  * [j][i], j = y row, i = x column, index = j*nx + i.  nb4 order
  * {(i,j-1),(i-1,j),(i+1,j),(i,j+1)} (reference :76-80).
  *
- * Pinning: the reference has no tests and cannot be rebuilt here (it needs
- * Rock base-types/base-logging headers absent from the image).  The
- * restatement is pinned against the reference-run known-answer checksums
- * recorded in SURVEY.md s8(c) (sum of getTotalCostMatrix and T[1][1] at
- * N = 256..4096, mt19937_64(1) inputs) and against closed forms; see
- * tests/test_oracle.py and DESIGN.md s3.
+ * Pinning: the reference's own sources, compiled unmodified against the
+ * stand-in headers of ref_harness/ (Makefile target `ref`), recorded
+ * tests/golden/ref_*.npz; tests/test_reference_pins.py holds every function
+ * here to them bit for bit, next to the reference-run checksums of SURVEY.md
+ * s8(c) and the closed forms of tests/test_oracle.py.  See DESIGN.md s3.
  */
 #ifndef DYMU_ORACLE_H
 #define DYMU_ORACLE_H
@@ -156,6 +155,8 @@ void oracle_local_deviation_matrix(oracle_local* L, double x, double y, double* 
 uint64_t oracle_local_map_mask(const oracle_local* L, uint8_t* mask);
 int oracle_local_block(const oracle_local* L, uint32_t gi, uint32_t gj, double* dev, double* tc,
                        double* risk, uint8_t* state, uint8_t* obst);
+/* getTotalCost(Waypoint) (reference :860-890) at world coordinates */
+double oracle_local_total_cost(const oracle_local* L, double x, double y);
 
 #ifdef __cplusplus
 }

@@ -1026,3 +1026,7 @@ int oracle_local_min_cost(oracle_local* L, double reach_x, double reach_y, doubl
 
 /* expandRisk (L:493-523) as a whole */
 void oracle_local_expand_risk(oracle_local* L) { expand_risk(L); }
+/* G:860-890 getTotalCost(Waypoint) at world coordinates, for the reference pins */
+double oracle_local_total_cost(const oracle_local* L, double x, double y) {
+  return total_cost_w(L, x, y);
+}

@@ -1,9 +1,11 @@
 """Generates the committed golden fixtures under tests/golden/.
 
-Inputs are synthetic (the reference ships no fixtures and no tests); expected
-outputs come from the CPU restatement in oracle/ (exact reference pop order),
-which is itself pinned by the reference-run KAT checksums of SURVEY.md s8(c)
-(tests/test_oracle.py::test_kat_reference_checksums).  Run from the repo root:
+Writes setcost64_*, terrain128_*, early64_* and early256_*.  Inputs are synthetic
+(the reference ships no fixtures and no tests); expected outputs come from the CPU
+restatement in oracle/ (exact reference pop order).  The oracle is pinned to the
+reference's own code by the ref_*.npz files that gen_golden_ref.py records, and
+tests/test_reference_pins.py::test_live_older_* holds each file written here to the
+reference's output for the same inputs.  Run from the repo root:
     python tests/golden/gen_golden.py
 """
 import os

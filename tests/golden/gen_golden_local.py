@@ -5,9 +5,11 @@ exercised) through computeCostMap, goal (36, 32), the oracle's heap FMM for
 the total cost, getPath from (7.3, 9.1), then computeLocalPlanning with a
 0.8 m obstacle disc on the path 10 waypoints ahead (0.25 m local cells,
 36x36 image), for CONSERVATIVE and SWEEPING.  Expected outputs come from the
-local-layer restatement oracle/oracle_local.c (the reference has no tests and
-ships no fixtures; parity of the local layer is unpinned beyond this
-restatement).  Run from the repo root:
+local-layer restatement oracle/oracle_local.c.  The same two scenes are recorded
+from the reference's own code as ref_local_cons.npz / ref_local_sweep.npz
+(gen_golden_ref.py), and tests/test_reference_pins.py::test_live_older_local holds
+the files written here to the reference's output.  Run from the
+repo root:
     python tests/golden/gen_golden_local.py
 """
 import os

@@ -65,6 +65,7 @@ _SIGS = {
     "oracle_local_set_state_at": (ctypes.c_int, [_vp, _d, _d, ctypes.c_int]),
     "oracle_local_min_cost": (ctypes.c_int, [_vp, _d, _d, _vp]),
     "oracle_local_expand_risk": (None, [_vp]),
+    "oracle_local_total_cost": (_d, [_vp, _d, _d]),
 }
 
 
@@ -156,6 +157,10 @@ class OracleLocal:
 
     def deviation_matrix(self, x, y):
         return self._window(self.lib.oracle_local_deviation_matrix, x, y)
+
+    def total_cost(self, x, y):
+        """getTotalCost(Waypoint) at world coordinates"""
+        return self.lib.oracle_local_total_cost(self.h, x, y)
 
     def map_mask(self):
         m = np.zeros((self.ny, self.nx), dtype=np.uint8)
