@@ -712,6 +712,13 @@ class DyMuPathPlanner {
     unsigned gi, gj;
     double heading;
   };
+  // one call of a device descent entry: its map and sinks, uploads and error text
+  struct DeviceQuery;
+  // the device holds the current map, and the goal set's labels if there is one: the
+  // descent entries can run there
+  bool descentOnDevice() const;
+  // the single sink's waypoint, grid-local: node (gi, gj) with this heading
+  base::Waypoint nodeSink(unsigned gi, unsigned gj, double heading) const;
   // arrive: the arriving descent (dymu_arrive_paths_device) in place of the reference's,
   // its records into *arrive
   void pathsOnDevice(const std::vector<base::Waypoint>& starts,

@@ -2,10 +2,9 @@
 // (DyMuPathPlanner::getArrivingPaths / getArrivingStats).
 //
 // k_arrive_paths: one lane per path.  A path takes k_extract_paths' continuous step
-// (path_kernels.hip: the same expressions in the same order, built with
-// -ffp-contract=off like the host code) wherever that step is valid, and a node-to-node
-// step on T wherever it is not; it never enters an obstacle node's square and ends on the
-// sink's node.  The rule is DyMuPathPlanner::descendArriving (planner.cpp), statement for
+// (descent_step.h, which states the bit-identity contract) wherever that step is valid,
+// and a node-to-node step on T wherever it is not; it never enters an obstacle node's
+// square and ends on the sink's node.  The rule is DyMuPathPlanner::descendArriving (planner.cpp), statement for
 // statement, so x, y, the counts, the hops and the length are the host's bits.
 //
 // A lane holds two things between steps, each renewed only when it changes:
@@ -21,20 +20,13 @@
 // that is in no cell (a hop along the last row or column) loads its own nine.  Every
 // index is clamped for its load and a value from outside the grid is replaced by +inf,
 // which no test accepts.
+#include "descent_step.h"
 #include "fim_kernels.h"
 
 namespace dymu {
 namespace {
 
-constexpr double kInfD = __builtin_huge_val();
 constexpr double kDiag = 0.7071067811865476;  // a diagonal hop's score per unit of T
-
-// path_kernels.hip's path_cell
-__device__ __forceinline__ bool path_cell(double g, uint32_t n, int64_t& c) {
-  if (!(g > -9.2e18 && g < 9.2e18)) return false;
-  c = (int64_t)g;
-  return c >= 0 && c + 1 < (int64_t)n;
-}
 
 // planner.cpp's arrive_node: the node of coordinate v with grid coordinate g = v / res
 // (nearestIndex's rounding); false off a grid of n nodes -- negative and NaN included
@@ -44,40 +36,6 @@ __device__ __forceinline__ bool arrive_node(double v, double g, uint32_t n, uint
   if (!(h < 4294967296.0)) return false;
   i = (uint32_t)h;
   return i < n;
-}
-
-// path_kernels.hip's gradient_node (gradientNode, :718-772)
-__device__ __forceinline__ void gradient_node(bool hw, bool he, bool hs, bool hn, double tw,
-                                              double te, double ts, double tn, double t,
-                                              double& dnx, double& dny) {
-  double dx, dy;
-  if ((!hw && !he) || (hw && he && tw == kInfD && te == kInfD)) dx = 0;
-  else if (!hw || tw == kInfD) dx = te - t;
-  else if (!he || te == kInfD) dx = t - tw;
-  else dx = (te - tw) * 0.5;
-  if ((!hs && !hn) || (hs && hn && ts == kInfD && tn == kInfD)) dy = 0;
-  else if (!hs || ts == kInfD) dy = tn - t;
-  else if (!hn || tn == kInfD) dy = t - ts;
-  else dy = (tn - ts) * 0.5;
-  if (dx == 0 && dy == 0) {
-    dnx = 0;
-    dny = 0;
-  } else {
-    const double r = sqrt(dx * dx + dy * dy);
-    dnx = dx / r;
-    dny = dy / r;
-  }
-}
-
-// interpolate (:776-784)
-__device__ __forceinline__ double interpolate(double a, double b, double g00, double g01,
-                                              double g10, double g11) {
-  return g00 + (g10 - g00) * a + (g01 - g00) * b + (g11 + g00 - g10 - g01) * a * b;
-}
-
-__device__ __forceinline__ double dist2d(double ax, double ay, double bx, double by) {
-  const double dx = ax - bx, dy = ay - by;
-  return sqrt(dx * dx + dy * dy);
 }
 
 // one of three named values by d in {-1, 0, +1}: no array is indexed at run time
@@ -126,9 +84,8 @@ __global__ __launch_bounds__(64) void k_arrive_paths(ArriveArgs a) {
   uint32_t lab_held = 0xffffffffu;  // GOALS: the label whose goal (sni, snj) is
   double px = 0, py = 0;            // the previous waypoint
   double pdx = 0, pdy = 0;          // the direction that produced the current waypoint
-  int64_t ccx = -1, ccy = -1;       // the cell whose corner gradients are held
-  double gx00 = 0, gx10 = 0, gx01 = 0, gx11 = 0, gy00 = 0, gy10 = 0, gy01 = 0, gy11 = 0;
-  // the 4x4 block of T around that cell, b<row><column>: rows ccy-1 .. ccy+2, columns
+  HeldCell cell;
+  // the 4x4 block of T around the held cell, b<row><column>: rows ccy-1 .. ccy+2, columns
   // ccx-1 .. ccx+2 (where the grid ends, a copy of the clamped row or column)
   double b00 = 0, b01 = 0, b02 = 0, b03 = 0, b10 = 0, b11 = 0, b12 = 0, b13 = 0, b20 = 0, b21 = 0,
          b22 = 0, b23 = 0, b30 = 0, b31 = 0, b32 = 0, b33 = 0;
@@ -142,33 +99,18 @@ __global__ __launch_bounds__(64) void k_arrive_paths(ArriveArgs a) {
     double nxt_x = __builtin_nan(""), nxt_y = nxt_x, dcx = 0, dcy = 0;
     const bool in_x = path_cell(gx, a.nx, cx), in_y = path_cell(gy, a.ny, cy);
     if (in_x && in_y) {
-      if (cx != ccx || cy != ccy) {
-        // rows cy-1 .. cy+2, columns cx-1 .. cx+2, loaded together; an index off the grid
-        // is clamped for the load and its value never used.  The gradients take the block
-        // without its corners (k_extract_paths' 12 values); the corners serve the nodes.
-        const int64_t i0 = cx > 0 ? cx - 1 : 0, i3 = cx + 2 < nx ? cx + 2 : nx - 1;
-        const int64_t j0 = cy > 0 ? cy - 1 : 0, j3 = cy + 2 < ny ? cy + 2 : ny - 1;
-        const double* r0 = a.T + j0 * ld;
-        const double* r1 = a.T + cy * ld;
-        const double* r2 = r1 + ld;
-        const double* r3 = a.T + j3 * ld;
-        b00 = r0[i0], b01 = r0[cx], b02 = r0[cx + 1], b03 = r0[i3];
-        b10 = r1[i0], b11 = r1[cx], b12 = r1[cx + 1], b13 = r1[i3];
-        b20 = r2[i0], b21 = r2[cx], b22 = r2[cx + 1], b23 = r2[i3];
-        b30 = r3[i0], b31 = r3[cx], b32 = r3[cx + 1], b33 = r3[i3];
-        const bool w_ok = cx > 0, e_ok = cx + 2 < nx, s_ok = cy > 0, n_ok = cy + 2 < ny;
-        gradient_node(w_ok, true, s_ok, true, b10, b12, b01, b21, b11, gx00, gy00);
-        gradient_node(true, e_ok, s_ok, true, b11, b13, b02, b22, b12, gx10, gy10);
-        gradient_node(w_ok, true, true, n_ok, b20, b22, b11, b31, b21, gx01, gy01);
-        gradient_node(true, e_ok, true, n_ok, b21, b23, b12, b32, b22, gx11, gy11);
-        ccx = cx;
-        ccy = cy;
+      if (!cell.holds(cx, cy)) {
+        // the whole 4x4 block, loaded together.  The gradients take it without its
+        // corners (k_extract_paths' 12 values); the corners serve the nodes.
+        const Stencil s = stencil_of(a.T, ld, nx, ny, cx, cy);
+        b00 = s.r0[s.i0], b01 = s.r0[cx], b02 = s.r0[cx + 1], b03 = s.r0[s.i3];
+        b10 = s.r1[s.i0], b11 = s.r1[cx], b12 = s.r1[cx + 1], b13 = s.r1[s.i3];
+        b20 = s.r2[s.i0], b21 = s.r2[cx], b22 = s.r2[cx + 1], b23 = s.r2[s.i3];
+        b30 = s.r3[s.i0], b31 = s.r3[cx], b32 = s.r3[cx + 1], b33 = s.r3[s.i3];
+        cell.set(cx, cy, s.w_ok, s.e_ok, s.s_ok, s.n_ok, b01, b02, b10, b11, b12, b13, b20, b21,
+                 b22, b23, b31, b32);
       }
-      const double ax = gx - (double)cx, ay = gy - (double)cy;
-      dcx = interpolate(ax, ay, gx00, gx01, gx10, gx11);
-      dcy = interpolate(ax, ay, gy00, gy01, gy10, gy11);
-      nxt_x = x - a.res_tau * dcx;
-      nxt_y = y - a.res_tau * dcy;
+      cell.candidate(x, y, gx, gy, cx, cy, a.res_tau, dcx, dcy, nxt_x, nxt_y);
     }
     if (fresh) {
       // the 3x3 block of the new node, before the grid's edge is applied

@@ -12,12 +12,11 @@
 // so the values are bit-identical to the host's on the same T.
 // k_probe_targets is the stop test of the early exit on target cells: the
 // largest value among the targets of finite speed, per plane and over the whole stack.
+#include "descent_step.h"  // kInfD, grid_u32
 #include "fim_kernels.h"
 
 namespace dymu {
 namespace {
-
-constexpr double kInfD = __builtin_huge_val();
 
 // one lane per cell of a row strip, rows and column strips by grid stride: a wave
 // reads / writes 64 consecutive doubles of one row
@@ -36,11 +35,6 @@ __global__ __launch_bounds__(256) void k_stack_speed(const double* __restrict__ 
          i += (uint64_t)gridDim.x * 256u)
       d[i] = wall ? kInfD : s[i];
   }
-}
-
-// local_layer.hpp's grid_u32: the reference's (uint) cast of an in-range value
-__device__ __forceinline__ uint32_t grid_u32(double d) {
-  return (d > -9.2e18 && d < 9.2e18) ? (uint32_t)(int64_t)d : 0u;
 }
 
 __global__ __launch_bounds__(256) void k_gather_costs(const double* __restrict__ T, uint64_t ld,

@@ -887,6 +887,21 @@ int elapsed_ms(dymu_ctx* c, bool dymu_ctx::*timed, hipEvent_t dymu_ctx::*ev_a,
   return event_ms(c, c->*ev_a, c->*ev_b, ms);
 }
 
+// launch() between the event pair of a dymu_last_*_ms getter (elapsed_ms): the events are
+// created on first use, and the flag holds once both are recorded behind the launch
+template <class Launch>
+int timed_launch(dymu_ctx* c, hipStream_t st, bool dymu_ctx::*timed, hipEvent_t dymu_ctx::*ev_a,
+                 hipEvent_t dymu_ctx::*ev_b, Launch launch) {
+  if (!(c->*ev_a)) HIPC(c, hipEventCreate(&(c->*ev_a)));
+  if (!(c->*ev_b)) HIPC(c, hipEventCreate(&(c->*ev_b)));
+  c->*timed = false;
+  HIPC(c, hipEventRecord(c->*ev_a, st));
+  HIPC(c, launch());
+  HIPC(c, hipEventRecord(c->*ev_b, st));
+  c->*timed = true;
+  return DYMU_OK;
+}
+
 // the end of a timed call: ev1 behind the work queued so far, the time since ev0, and the
 // live domain's statistics
 int finish_timed(dymu_ctx* c, hipStream_t st, dymu_stats* stats) {
@@ -1919,24 +1934,26 @@ int dymu_scatter(dymu_ctx* c, double* dT, uint32_t nx, uint64_t ld, const uint64
   return DYMU_OK;
 }
 
+// ---- the descent entries: paths, path summaries, arriving paths (descent_step.h) ----
 namespace {
-// dymu_extract_paths_device (d_label null: one sink, the goal (gi, gj)) and
-// dymu_extract_paths_goals_device (the sink follows the label map)
-int extract_paths(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld, double res,
-                  uint32_t gi, uint32_t gj, const uint32_t* d_label, const double* d_goal_xy,
-                  uint32_t n_goals, double tau, const double* d_start_xy, uint32_t n_paths,
-                  uint32_t max_wp, uint32_t stride, double* d_out, int32_t* d_count,
-                  int32_t* d_status, int32_t* d_sink, void* stream) {
-  if (!c || !dT || nx == 0 || ny == 0 || ld < nx || gi >= nx || gj >= ny) return DYMU_ERR_ARG;
+// What the three entries share: the checks of the shared arguments, the d_label / (gi, gj)
+// branch (under a label map the single sink is unused: gi = gj = 0) and the argument block
+// of the step.  Makes no HIP call.
+int descent_args(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld, double res,
+                 uint32_t& gi, uint32_t& gj, const uint32_t* d_label, const double* d_goal_xy,
+                 uint32_t n_goals, double tau, const double* d_start_xy, uint32_t n_paths,
+                 uint32_t max_wp, DescentArgs& a) {
+  if (!c || !dT || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
   if (!(res > 0) || !(res < HUGE_VAL) || !(tau > 0) || !(tau < HUGE_VAL)) return DYMU_ERR_ARG;
-  if (max_wp == 0 || max_wp > 0x7fffffffu || stride == 0) return DYMU_ERR_ARG;
-  if (n_paths && (!d_start_xy || !d_out || !d_count || !d_status)) return DYMU_ERR_ARG;
-  if (n_paths == 0) return DYMU_OK;
-  HIPC(c, hipSetDevice(c->device));
-  hipStream_t st = pick_stream(c, stream);
-  if (!c->ev_path0) HIPC(c, hipEventCreate(&c->ev_path0));
-  if (!c->ev_path1) HIPC(c, hipEventCreate(&c->ev_path1));
-  PathArgs a{};
+  if (max_wp == 0 || max_wp > 0x7fffffffu) return DYMU_ERR_ARG;
+  if (d_label) {
+    if (!d_goal_xy || n_goals == 0 || n_goals >= (1u << 31)) return DYMU_ERR_ARG;
+    if ((uint64_t)nx * ny >= (1ull << 31)) return DYMU_ERR_ARG;
+    gi = gj = 0;
+  } else if (gi >= nx || gj >= ny) {
+    return DYMU_ERR_ARG;
+  }
+  if (n_paths && !d_start_xy) return DYMU_ERR_ARG;
   a.T = dT;
   a.ld = (int64_t)ld;
   a.nx = nx;
@@ -1951,20 +1968,35 @@ int extract_paths(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint6
   a.start_xy = d_start_xy;
   a.n_paths = n_paths;
   a.max_wp = max_wp;
+  a.label = d_label;
+  a.goal_xy = d_goal_xy;
+  a.n_goals = n_goals;
+  return DYMU_OK;
+}
+
+// dymu_extract_paths_device (d_label null: one sink, the goal (gi, gj)) and
+// dymu_extract_paths_goals_device (the sink follows the label map)
+int extract_paths(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld, double res,
+                  uint32_t gi, uint32_t gj, const uint32_t* d_label, const double* d_goal_xy,
+                  uint32_t n_goals, double tau, const double* d_start_xy, uint32_t n_paths,
+                  uint32_t max_wp, uint32_t stride, double* d_out, int32_t* d_count,
+                  int32_t* d_status, int32_t* d_sink, void* stream) {
+  PathArgs a{};
+  const int rc = descent_args(c, dT, nx, ny, ld, res, gi, gj, d_label, d_goal_xy, n_goals, tau,
+                              d_start_xy, n_paths, max_wp, a);
+  if (rc) return rc;
+  if (stride == 0 || (n_paths && (!d_out || !d_count || !d_status))) return DYMU_ERR_ARG;
+  if (n_paths == 0) return DYMU_OK;
   a.stride = stride;
   a.out = d_out;
   a.count = d_count;
   a.status = d_status;
-  a.label = d_label;
-  a.goal_xy = d_goal_xy;
-  a.n_goals = n_goals;
   a.sink = d_sink;
-  c->path_timed = false;
-  HIPC(c, hipEventRecord(c->ev_path0, st));
-  HIPC(c, d_label ? launch_extract_paths_goals(a, st) : launch_extract_paths(a, st));
-  HIPC(c, hipEventRecord(c->ev_path1, st));
-  c->path_timed = true;
-  return DYMU_OK;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  return timed_launch(c, st, &dymu_ctx::path_timed, &dymu_ctx::ev_path0, &dymu_ctx::ev_path1, [&] {
+    return d_label ? launch_extract_paths_goals(a, st) : launch_extract_paths(a, st);
+  });
 }
 }  // namespace
 
@@ -1983,8 +2015,7 @@ int dymu_extract_paths_goals_device(dymu_ctx* c, const double* dT, uint32_t nx, 
                                     const double* d_start_xy, uint32_t n_paths, uint32_t max_wp,
                                     uint32_t stride, double* d_out, int32_t* d_count,
                                     int32_t* d_status, void* stream, int32_t* d_sink) {
-  if (!d_label || !d_goal_xy || n_goals == 0 || n_goals >= (1u << 31)) return DYMU_ERR_ARG;
-  if ((uint64_t)nx * ny >= (1ull << 31) || (n_paths && !d_sink)) return DYMU_ERR_ARG;
+  if (!d_label || (n_paths && !d_sink)) return DYMU_ERR_ARG;
   return extract_paths(c, dT, nx, ny, ld, res, 0, 0, d_label, d_goal_xy, n_goals, tau, d_start_xy,
                        n_paths, max_wp, stride, d_out, d_count, d_status, d_sink, stream);
 }
@@ -2000,63 +2031,34 @@ int dymu_path_stats_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t 
                            const double* const* d_fields, const uint64_t* field_ld,
                            uint32_t n_fields, uint32_t n_lanes, dymu_path_stat* d_stats,
                            void* stream) {
-  if (!c || !dT || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
-  if (!(res > 0) || !(res < HUGE_VAL) || !(tau > 0) || !(tau < HUGE_VAL)) return DYMU_ERR_ARG;
-  if (max_wp == 0 || max_wp > 0x7fffffffu || n_paths > 0x7fffffffu) return DYMU_ERR_ARG;
-  if (d_label) {
-    if (!d_goal_xy || n_goals == 0 || n_goals >= (1u << 31)) return DYMU_ERR_ARG;
-    if ((uint64_t)nx * ny >= (1ull << 31)) return DYMU_ERR_ARG;
-    gi = gj = 0;
-  } else if (gi >= nx || gj >= ny) {
-    return DYMU_ERR_ARG;
-  }
+  PathStatArgs a{};
+  const int rc = descent_args(c, dT, nx, ny, ld, res, gi, gj, d_label, d_goal_xy, n_goals, tau,
+                              d_start_xy, n_paths, max_wp, a);
+  if (rc) return rc;
+  if (n_paths > 0x7fffffffu || (n_paths && !d_stats)) return DYMU_ERR_ARG;
   if (n_fields > DYMU_PATH_FIELDS || (n_fields && (!d_fields || !field_ld))) return DYMU_ERR_ARG;
   for (uint32_t f = 0; f < n_fields; ++f)
     if (!d_fields[f] || field_ld[f] < nx) return DYMU_ERR_ARG;
-  if (n_paths && (!d_start_xy || !d_stats)) return DYMU_ERR_ARG;
   if (n_paths == 0) return DYMU_OK;
-  HIPC(c, hipSetDevice(c->device));
-  hipStream_t st = pick_stream(c, stream);
-  if (!c->ev_pstat0) HIPC(c, hipEventCreate(&c->ev_pstat0));
-  if (!c->ev_pstat1) HIPC(c, hipEventCreate(&c->ev_pstat1));
-  if (!c->d_pq) HIPC(c, hipMalloc(&c->d_pq, 256));
-  PathStatArgs a{};
-  a.T = dT;
-  a.ld = (int64_t)ld;
-  a.nx = nx;
-  a.ny = ny;
-  a.res = res;
-  // the host's expressions, as dymu_extract_paths_device forms them
-  a.res_tau = res * tau;
-  a.two_res = 2.0 * res;
-  a.stall = 0.01 * tau * res;
-  a.sink_x = res * (double)gi;
-  a.sink_y = res * (double)gj;
-  a.start_xy = d_start_xy;
-  a.n_paths = n_paths;
-  a.max_wp = max_wp;
-  a.label = d_label;
-  a.goal_xy = d_goal_xy;
-  a.n_goals = n_goals;
   for (uint32_t f = 0; f < n_fields; ++f) {
     a.field[f] = d_fields[f];
     a.field_ld[f] = (int64_t)field_ld[f];
   }
-  a.next = c->d_pq;
   a.out = reinterpret_cast<PathStatRec*>(d_stats);
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  if (!c->d_pq) HIPC(c, hipMalloc(&c->d_pq, 256));
+  a.next = c->d_pq;
   // The default is one lane per path: lanes that refill from the queue were slower than
   // that where measured.  More lanes than paths would only fetch and
   // leave; the fetches add at most n_paths + lanes < 2^32 to the counter.
   const uint32_t whole = (n_paths + 63u) / 64u * 64u;
   uint32_t lanes = n_lanes ? (n_lanes + 63u) / 64u * 64u : whole;
   if (n_lanes > 0xffffffc0u || lanes > whole) lanes = whole;
-  c->pstat_timed = false;
+  c->pstat_timed = false;  // the queue's reset is outside the timed bracket
   HIPC(c, hipMemsetAsync(c->d_pq, 0, sizeof(uint32_t), st));
-  HIPC(c, hipEventRecord(c->ev_pstat0, st));
-  HIPC(c, launch_path_stats(a, n_fields, lanes, st));
-  HIPC(c, hipEventRecord(c->ev_pstat1, st));
-  c->pstat_timed = true;
-  return DYMU_OK;
+  return timed_launch(c, st, &dymu_ctx::pstat_timed, &dymu_ctx::ev_pstat0, &dymu_ctx::ev_pstat1,
+                      [&] { return launch_path_stats(a, n_fields, lanes, st); });
 }
 
 int dymu_last_path_stats_ms(dymu_ctx* c, double* ms) {
@@ -2074,51 +2076,22 @@ int dymu_arrive_paths_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_
                              const double* d_start_xy, uint32_t n_paths, uint32_t max_wp,
                              uint32_t stride, double* d_out, int32_t* d_count,
                              dymu_arrive_stat* d_stats, void* stream) {
-  if (!c || !dT || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
-  if (!(res > 0) || !(res < HUGE_VAL) || !(tau > 0) || !(tau < HUGE_VAL)) return DYMU_ERR_ARG;
-  if (max_wp == 0 || max_wp > 0x7fffffffu || stride == 0) return DYMU_ERR_ARG;
-  if (d_label) {
-    if (!d_goal_xy || n_goals == 0 || n_goals >= (1u << 31)) return DYMU_ERR_ARG;
-    if ((uint64_t)nx * ny >= (1ull << 31)) return DYMU_ERR_ARG;
-    gi = gj = 0;
-  } else if (gi >= nx || gj >= ny) {
-    return DYMU_ERR_ARG;
-  }
-  if (n_paths && (!d_start_xy || !d_stats || (d_out && !d_count))) return DYMU_ERR_ARG;
-  if (n_paths == 0) return DYMU_OK;
-  HIPC(c, hipSetDevice(c->device));
-  hipStream_t st = pick_stream(c, stream);
-  if (!c->ev_arr0) HIPC(c, hipEventCreate(&c->ev_arr0));
-  if (!c->ev_arr1) HIPC(c, hipEventCreate(&c->ev_arr1));
   ArriveArgs a{};
-  a.T = dT;
-  a.ld = (int64_t)ld;
-  a.nx = nx;
-  a.ny = ny;
-  a.res = res;
-  // the host's expressions, as dymu_extract_paths_device forms them
-  a.res_tau = res * tau;
-  a.stall = 0.01 * tau * res;
-  a.sink_x = res * (double)gi;
-  a.sink_y = res * (double)gj;
+  const int rc = descent_args(c, dT, nx, ny, ld, res, gi, gj, d_label, d_goal_xy, n_goals, tau,
+                              d_start_xy, n_paths, max_wp, a);
+  if (rc) return rc;
+  if (stride == 0 || (n_paths && (!d_stats || (d_out && !d_count)))) return DYMU_ERR_ARG;
+  if (n_paths == 0) return DYMU_OK;
   a.goal_i = gi;
   a.goal_j = gj;
-  a.start_xy = d_start_xy;
-  a.n_paths = n_paths;
-  a.max_wp = max_wp;
   a.stride = stride;
   a.out = d_out;
   a.count = d_count;
   a.stats = reinterpret_cast<ArriveRec*>(d_stats);
-  a.label = d_label;
-  a.goal_xy = d_goal_xy;
-  a.n_goals = n_goals;
-  c->arr_timed = false;
-  HIPC(c, hipEventRecord(c->ev_arr0, st));
-  HIPC(c, launch_arrive_paths(a, st));
-  HIPC(c, hipEventRecord(c->ev_arr1, st));
-  c->arr_timed = true;
-  return DYMU_OK;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  return timed_launch(c, st, &dymu_ctx::arr_timed, &dymu_ctx::ev_arr0, &dymu_ctx::ev_arr1,
+                      [&] { return launch_arrive_paths(a, st); });
 }
 
 int dymu_last_arrive_ms(dymu_ctx* c, double* ms) {

@@ -374,9 +374,10 @@ hipError_t launch_store_u64(unsigned long long* p, unsigned long long v, hipStre
 hipError_t launch_scatter(double* T, int64_t ld, uint32_t nx, const uint64_t* idx,
                           const double* vals, uint64_t n, hipStream_t st);
 
-// batched path extraction (path_kernels.hip): one lane per path runs the reference's
-// gradient descent on T from start_xy[p] (grid-local metres) towards the sink
-struct PathArgs {
+// The argument block of the continuous descent step (descent_step.h), which the three
+// path kernels' blocks begin with: the reference's gradient descent on T from start_xy[p]
+// (grid-local metres) towards the sink.  dymu_fim.cpp's descent_args fills it.
+struct DescentArgs {
   const double* T;  // total cost, pitch ld
   int64_t ld;
   uint32_t nx, ny;
@@ -386,15 +387,20 @@ struct PathArgs {
   double stall;            // 0.01 * tau * res: a shorter step is "ERROR in trajectory"
   double sink_x, sink_y;   // res * goal_i, res * goal_j
   const double* start_xy;  // n_paths x 2
-  uint32_t n_paths, max_wp, stride;
-  double* out;      // [path][slot][4]: x, y and the (dcx, dcy) that produced the waypoint
-  int32_t* count;   // slots written per path
-  int32_t* status;  // 1 sink appended, 0 stalled, -1 first step NaN / off the grid, -3 max_wp
-  // ---- goal sets (launch_extract_paths_goals; unused by launch_extract_paths) ----
+  uint32_t n_paths, max_wp;
+  // ---- goal sets: label null is the single sink (sink_x, sink_y) ----
   const uint32_t* label;  // nearest-goal label per cell, pitch nx (0xFFFFFFFF: none)
   const double* goal_xy;  // n_goals x 2: the sinks (res * i, res * j)
   uint32_t n_goals;
-  int32_t* sink;          // per path: the goal whose sink was appended, or -1
+};
+
+// batched path extraction (path_kernels.hip): one lane per path runs the descent
+struct PathArgs : DescentArgs {
+  uint32_t stride;
+  double* out;      // [path][slot][4]: x, y and the (dcx, dcy) that produced the waypoint
+  int32_t* count;   // slots written per path
+  int32_t* status;  // 1 sink appended, 0 stalled, -1 first step NaN / off the grid, -3 max_wp
+  int32_t* sink;    // goal sets: per path the goal whose sink was appended, or -1
 };
 hipError_t launch_extract_paths(const PathArgs& a, hipStream_t st);
 // the same descent with a per-path sink: the goal labelled on the cell the path is in
@@ -410,17 +416,7 @@ struct PathStatRec {
   double integral[kPathFields], vmin[kPathFields], vmax[kPathFields];
   uint32_t skipped[kPathFields];
 };
-struct PathStatArgs {
-  const double* T;  // total cost, pitch ld
-  int64_t ld;
-  uint32_t nx, ny;
-  double res, res_tau, two_res, stall;  // as PathArgs
-  double sink_x, sink_y;
-  const double* start_xy;  // n_paths x 2
-  uint32_t n_paths, max_wp;
-  const uint32_t* label;  // null: the single sink (sink_x, sink_y); else as PathArgs
-  const double* goal_xy;
-  uint32_t n_goals;
+struct PathStatArgs : DescentArgs {
   const double* field[kPathFields];  // the sampled fields, pitch field_ld
   int64_t field_ld[kPathFields];
   uint32_t* next;    // the work queue: the next path index to hand out (zero at launch)
@@ -438,21 +434,12 @@ struct ArriveRec {
   uint32_t count, hops;
   double length, start_cost;
 };
-struct ArriveArgs {
-  const double* T;  // total cost, pitch ld
-  int64_t ld;
-  uint32_t nx, ny;
-  double res, res_tau, stall;  // as PathArgs
-  double sink_x, sink_y;       // res * goal_i, res * goal_j
-  uint32_t goal_i, goal_j;     // the single sink's node
-  const double* start_xy;      // n_paths x 2
-  uint32_t n_paths, max_wp, stride;
+struct ArriveArgs : DescentArgs {  // the label is looked up at the node; two_res is unused
+  uint32_t goal_i, goal_j;         // the single sink's node
+  uint32_t stride;
   double* out;       // null: no waypoint is stored; else PathArgs' slots
   int32_t* count;    // slots kept per path (may be null with out)
   ArriveRec* stats;  // n_paths records
-  const uint32_t* label;  // null: the single sink; else as PathArgs, looked up at the node
-  const double* goal_xy;
-  uint32_t n_goals;
 };
 hipError_t launch_arrive_paths(const ArriveArgs& a, hipStream_t st);
 

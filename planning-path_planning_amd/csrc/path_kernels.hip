@@ -1,70 +1,16 @@
 // path_kernels.hip -- batched path extraction on the device-resident total cost.
 //
 // k_extract_paths: one lane per path, each running the reference's gradient
-// descent (computeGlobalPath / computeNextGlobalWaypoint / gradientNode /
-// interpolate, src/DyMu_GlobalPathPlanning.cpp:615-784 as restated in
-// planner.cpp) on the row-major fp64 T.  Every expression is the host's, in the
-// host's order, and this file is built with -ffp-contract=off like the host
-// code: fp64 add / sub / mul / div / sqrt round the same on both sides, so x, y
-// and the waypoint count come out bit-identical to the host loop on the same T
-// (DESIGN.md s5.3).  The heading (atan2) and z are left to the host: a waypoint
-// carries the (dcx, dcy) that produced it in its two spare slots.
-//
-// A step touches the 4x4 block of cells around (cx, cy) without its corners
-// (the stencils of the cell's four corner nodes).  A step is 0.4 cell, so most
-// steps stay in their cell: the 12 values are loaded together when the cell
-// changes (one latency per reload) and the four corner gradients -- functions
-// of those values alone -- are kept in registers until it changes again.
+// descent (computeGlobalPath, src/DyMu_GlobalPathPlanning.cpp:615-660 as restated in
+// planner.cpp) with the step of descent_step.h, which states the bit-identity
+// contract with the host loop and how a lane holds its cell's gradients.  The
+// heading (atan2) and z are left to the host: a waypoint carries the (dcx, dcy)
+// that produced it in its two spare slots.
+#include "descent_step.h"
 #include "fim_kernels.h"
 
 namespace dymu {
 namespace {
-
-constexpr double kInfD = __builtin_huge_val();
-
-// planner.cpp's path_cell: the cell index of grid coordinate g (truncation like
-// the reference's (uint) cast of an in-range value), tested in 64-bit; false
-// when the cell or its +1 neighbour is off a grid of n nodes (negative, huge
-// and NaN coordinates included)
-__device__ __forceinline__ bool path_cell(double g, uint32_t n, int64_t& c) {
-  if (!(g > -9.2e18 && g < 9.2e18)) return false;
-  c = (int64_t)g;
-  return c >= 0 && c + 1 < (int64_t)n;
-}
-
-// gradientNode (:718-772) of a node from its values: h* = the neighbour exists
-__device__ __forceinline__ void gradient_node(bool hw, bool he, bool hs, bool hn, double tw,
-                                              double te, double ts, double tn, double t,
-                                              double& dnx, double& dny) {
-  double dx, dy;
-  if ((!hw && !he) || (hw && he && tw == kInfD && te == kInfD)) dx = 0;
-  else if (!hw || tw == kInfD) dx = te - t;
-  else if (!he || te == kInfD) dx = t - tw;
-  else dx = (te - tw) * 0.5;
-  if ((!hs && !hn) || (hs && hn && ts == kInfD && tn == kInfD)) dy = 0;
-  else if (!hs || ts == kInfD) dy = tn - t;
-  else if (!hn || tn == kInfD) dy = t - ts;
-  else dy = (tn - ts) * 0.5;
-  if (dx == 0 && dy == 0) {
-    dnx = 0;
-    dny = 0;
-  } else {
-    const double r = sqrt(dx * dx + dy * dy);
-    dnx = dx / r;
-    dny = dy / r;
-  }
-}
-
-// interpolate (:776-784)
-__device__ __forceinline__ double interpolate(double a, double b, double g00, double g01,
-                                              double g10, double g11) {
-  return g00 + (g10 - g00) * a + (g01 - g00) * b + (g11 + g00 - g10 - g01) * a * b;
-}
-
-__device__ __forceinline__ double dist2d(double ax, double ay, double bx, double by) {
-  const double dx = ax - bx, dy = ay - by;
-  return sqrt(dx * dx + dy * dy);
-}
 
 // GOALS: the sink is per path and follows the label map (goal sets):
 // whenever the cell the lane holds gradients for changes, the sink becomes the goal
@@ -83,8 +29,7 @@ __global__ __launch_bounds__(64) void k_extract_paths(PathArgs a) {
   uint32_t n = 0, phase = 0;
   int32_t status = 1;
   double pdx = 0, pdy = 0;  // the direction that produced the current waypoint
-  int64_t ccx = -1, ccy = -1;  // the cell whose corner gradients are held
-  double gx00 = 0, gx10 = 0, gx01 = 0, gx11 = 0, gy00 = 0, gy10 = 0, gy01 = 0, gy11 = 0;
+  HeldCell cell;
   double sink_x = a.sink_x, sink_y = a.sink_y;
   int32_t sink_k = -1;  // GOALS: the goal of the current sink
   for (uint64_t w = 0;; ++w) {
@@ -101,40 +46,12 @@ __global__ __launch_bounds__(64) void k_extract_paths(PathArgs a) {
     // no load before both indices are proven inside the grid
     const bool in_x = path_cell(gx, a.nx, cx), in_y = path_cell(gy, a.ny, cy);
     if (in_x && in_y) {
-      if (cx != ccx || cy != ccy) {
-        // rows cy-1 .. cy+2, columns cx-1 .. cx+2 without the corners; an index off
-        // the grid is clamped for the load and its value never used
-        const int64_t i0 = cx > 0 ? cx - 1 : 0, i3 = cx + 2 < nx ? cx + 2 : nx - 1;
-        const int64_t j0 = cy > 0 ? cy - 1 : 0, j3 = cy + 2 < ny ? cy + 2 : ny - 1;
-        const double* r0 = a.T + j0 * ld;
-        const double* r1 = a.T + cy * ld;
-        const double* r2 = r1 + ld;
-        const double* r3 = a.T + j3 * ld;
-        const double t01 = r0[cx], t02 = r0[cx + 1];
-        const double t10 = r1[i0], t11 = r1[cx], t12 = r1[cx + 1], t13 = r1[i3];
-        const double t20 = r2[i0], t21 = r2[cx], t22 = r2[cx + 1], t23 = r2[i3];
-        const double t31 = r3[cx], t32 = r3[cx + 1];
-        const bool w_ok = cx > 0, e_ok = cx + 2 < nx, s_ok = cy > 0, n_ok = cy + 2 < ny;
-        gradient_node(w_ok, true, s_ok, true, t10, t12, t01, t21, t11, gx00, gy00);
-        gradient_node(true, e_ok, s_ok, true, t11, t13, t02, t22, t12, gx10, gy10);
-        gradient_node(w_ok, true, true, n_ok, t20, t22, t11, t31, t21, gx01, gy01);
-        gradient_node(true, e_ok, true, n_ok, t21, t23, t12, t32, t22, gx11, gy11);
-        ccx = cx;
-        ccy = cy;
-        if (GOALS) {  // the cell is inside the grid: cy * nx + cx < nx * ny
-          const uint32_t lab = a.label[cy * nx + cx];
-          if (lab < a.n_goals) {
-            sink_x = a.goal_xy[2 * (uint64_t)lab];
-            sink_y = a.goal_xy[2 * (uint64_t)lab + 1];
-            sink_k = (int32_t)lab;
-          }
-        }
+      if (!cell.holds(cx, cy)) {
+        cell.load(a.T, ld, nx, ny, cx, cy);
+        // the cell is inside the grid: cy * nx + cx < nx * ny
+        if (GOALS) label_sink(a.label, a.goal_xy, a.n_goals, cy * nx + cx, sink_x, sink_y, sink_k);
       }
-      const double ax = gx - (double)cx, ay = gy - (double)cy;
-      dcx = interpolate(ax, ay, gx00, gx01, gx10, gx11);
-      dcy = interpolate(ax, ay, gy00, gy01, gy10, gy11);
-      nxt_x = x - a.res_tau * dcx;
-      nxt_y = y - a.res_tau * dcy;
+      cell.candidate(x, y, gx, gy, cx, cy, a.res_tau, dcx, dcy, nxt_x, nxt_y);
     }
     if (w == 0 && (nxt_x != nxt_x || nxt_y != nxt_y)) {  // :628-633
       status = -1;

@@ -1,9 +1,8 @@
 // path_stats_kernels.hip -- per-path summaries of the reference's descent on the
 // device-resident total cost (DyMuPathPlanner::getPathStats).
 //
-// k_path_stats runs k_extract_paths' descent (path_kernels.hip: the same expressions in
-// the same order, built with -ffp-contract=off like the host code) and stores no
-// waypoint.  It keeps the previous waypoint in registers and accumulates one record per
+// k_path_stats runs k_extract_paths' descent (the step of descent_step.h, which states
+// the bit-identity contract with the host loop) and stores no waypoint.  It keeps the previous waypoint in registers and accumulates one record per
 // path: outcome, waypoint count, length, last hop, and for up to kPathFields sampled
 // fields the integral along the path, the minimum, the maximum and the number of
 // samples skipped.  The record is defined on the host loop (planner.cpp, PathAccum) and
@@ -19,58 +18,11 @@
 // the next path index from a device counter and goes on in the same loop -- the idle
 // lanes of a wave fetch together, one atomic add for all of them.  A record depends on
 // its path alone, never on the lane that ran it.
+#include "descent_step.h"
 #include "fim_kernels.h"
 
 namespace dymu {
 namespace {
-
-constexpr double kInfD = __builtin_huge_val();
-
-// path_kernels.hip's path_cell
-__device__ __forceinline__ bool path_cell(double g, uint32_t n, int64_t& c) {
-  if (!(g > -9.2e18 && g < 9.2e18)) return false;
-  c = (int64_t)g;
-  return c >= 0 && c + 1 < (int64_t)n;
-}
-
-// local_layer.hpp's grid_u32: the reference's (uint) cast of an in-range value
-__device__ __forceinline__ uint32_t grid_u32(double d) {
-  return (d > -9.2e18 && d < 9.2e18) ? (uint32_t)(int64_t)d : 0u;
-}
-
-// path_kernels.hip's gradient_node (gradientNode, :718-772)
-__device__ __forceinline__ void gradient_node(bool hw, bool he, bool hs, bool hn, double tw,
-                                              double te, double ts, double tn, double t,
-                                              double& dnx, double& dny) {
-  double dx, dy;
-  if ((!hw && !he) || (hw && he && tw == kInfD && te == kInfD)) dx = 0;
-  else if (!hw || tw == kInfD) dx = te - t;
-  else if (!he || te == kInfD) dx = t - tw;
-  else dx = (te - tw) * 0.5;
-  if ((!hs && !hn) || (hs && hn && ts == kInfD && tn == kInfD)) dy = 0;
-  else if (!hs || ts == kInfD) dy = tn - t;
-  else if (!hn || tn == kInfD) dy = t - ts;
-  else dy = (tn - ts) * 0.5;
-  if (dx == 0 && dy == 0) {
-    dnx = 0;
-    dny = 0;
-  } else {
-    const double r = sqrt(dx * dx + dy * dy);
-    dnx = dx / r;
-    dny = dy / r;
-  }
-}
-
-// interpolate (:776-784)
-__device__ __forceinline__ double interpolate(double a, double b, double g00, double g01,
-                                              double g10, double g11) {
-  return g00 + (g10 - g00) * a + (g01 - g00) * b + (g11 + g00 - g10 - g01) * a * b;
-}
-
-__device__ __forceinline__ double dist2d(double ax, double ay, double bx, double by) {
-  const double dx = ax - bx, dy = ay - by;
-  return sqrt(dx * dx + dy * dy);
-}
 
 // The record of one path while it is built (planner.cpp's PathAccum): everything stays
 // in registers, NF is a compile-time count so that no array is indexed at run time.
@@ -134,8 +86,7 @@ __global__ __launch_bounds__(64) void k_path_stats(PathStatArgs a) {
   bool idle = true;
   double x = 0, y = 0;
   int32_t status = 1;
-  int64_t ccx = -1, ccy = -1;  // the cell whose corner gradients are held
-  double gx00 = 0, gx10 = 0, gx01 = 0, gx11 = 0, gy00 = 0, gy10 = 0, gy01 = 0, gy11 = 0;
+  HeldCell cell;
   double sink_x = a.sink_x, sink_y = a.sink_y;
   int32_t sink_k = -1;
   uint32_t hni = 0xffffffffu, hnj = 0xffffffffu;  // the node whose field values are held
@@ -154,7 +105,7 @@ __global__ __launch_bounds__(64) void k_path_stats(PathStatArgs a) {
       x = a.start_xy[2 * (uint64_t)p];
       y = a.start_xy[2 * (uint64_t)p + 1];
       status = 1;
-      ccx = ccy = -1;
+      cell.drop();
       hni = hnj = 0xffffffffu;
       sink_x = a.sink_x;
       sink_y = a.sink_y;
@@ -189,40 +140,13 @@ __global__ __launch_bounds__(64) void k_path_stats(PathStatArgs a) {
         hnj = nj;
       }
       if (in_x && in_y) {
-        if (cx != ccx || cy != ccy) {
-          // rows cy-1 .. cy+2, columns cx-1 .. cx+2 without the corners; an index off
-          // the grid is clamped for the load and its value never used
-          const int64_t i0 = cx > 0 ? cx - 1 : 0, i3 = cx + 2 < nx ? cx + 2 : nx - 1;
-          const int64_t j0 = cy > 0 ? cy - 1 : 0, j3 = cy + 2 < ny ? cy + 2 : ny - 1;
-          const double* r0 = a.T + j0 * ld;
-          const double* r1 = a.T + cy * ld;
-          const double* r2 = r1 + ld;
-          const double* r3 = a.T + j3 * ld;
-          const double t01 = r0[cx], t02 = r0[cx + 1];
-          const double t10 = r1[i0], t11 = r1[cx], t12 = r1[cx + 1], t13 = r1[i3];
-          const double t20 = r2[i0], t21 = r2[cx], t22 = r2[cx + 1], t23 = r2[i3];
-          const double t31 = r3[cx], t32 = r3[cx + 1];
-          const bool w_ok = cx > 0, e_ok = cx + 2 < nx, s_ok = cy > 0, n_ok = cy + 2 < ny;
-          gradient_node(w_ok, true, s_ok, true, t10, t12, t01, t21, t11, gx00, gy00);
-          gradient_node(true, e_ok, s_ok, true, t11, t13, t02, t22, t12, gx10, gy10);
-          gradient_node(w_ok, true, true, n_ok, t20, t22, t11, t31, t21, gx01, gy01);
-          gradient_node(true, e_ok, true, n_ok, t21, t23, t12, t32, t22, gx11, gy11);
-          ccx = cx;
-          ccy = cy;
-          if (GOALS) {  // the cell is inside the grid: cy * nx + cx < nx * ny
-            const uint32_t lab = a.label[cy * nx + cx];
-            if (lab < a.n_goals) {
-              sink_x = a.goal_xy[2 * (uint64_t)lab];
-              sink_y = a.goal_xy[2 * (uint64_t)lab + 1];
-              sink_k = (int32_t)lab;
-            }
-          }
+        if (!cell.holds(cx, cy)) {
+          cell.load(a.T, ld, nx, ny, cx, cy);
+          // the cell is inside the grid: cy * nx + cx < nx * ny
+          if (GOALS)
+            label_sink(a.label, a.goal_xy, a.n_goals, cy * nx + cx, sink_x, sink_y, sink_k);
         }
-        const double ax = gx - (double)cx, ay = gy - (double)cy;
-        dcx = interpolate(ax, ay, gx00, gx01, gx10, gx11);
-        dcy = interpolate(ax, ay, gy00, gy01, gy10, gy11);
-        nxt_x = x - a.res_tau * dcx;
-        nxt_y = y - a.res_tau * dcy;
+        cell.candidate(x, y, gx, gy, cx, cy, a.res_tau, dcx, dcy, nxt_x, nxt_y);
       }
       if (acc.n == 0 && ((nxt_x != nxt_x || nxt_y != nxt_y) || (GOALS && sink_k < 0))) {
         status = -1;  // :628-633, or no goal drains the start's cell: an empty record

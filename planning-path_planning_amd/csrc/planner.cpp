@@ -263,6 +263,17 @@ void parallel_tasks(unsigned nt, Body&& body) {
     if (e) std::rethrow_exception(e);
 }
 
+// body(q) for every q in [0, n) on up to host_threads() threads; a thread takes the next
+// index when it is done with one, so starts of unequal cost balance
+template <class Body>
+void for_each_start(size_t n, Body&& body) {
+  const unsigned nt = (unsigned)std::min<size_t>(host_threads(), n);
+  std::atomic<size_t> next{0};
+  parallel_tasks(nt, [&](unsigned) {
+    for (size_t q = next++; q < n; q = next++) body(q);
+  });
+}
+
 // body(j0, j1) over row ranges of [0, ny) on up to host_threads() threads (at
 // least 64 rows each).  Every loop run this way writes only the node it visits
 // and reads fields no iteration of the same loop writes, so the split changes no
@@ -1981,11 +1992,7 @@ int DyMuPathPlanner::descend(base::Waypoint wPos, std::vector<base::Waypoint>& p
   const uint64_t limit = max_wp > std::numeric_limits<uint64_t>::max() / stride
                              ? std::numeric_limits<uint64_t>::max()
                              : max_wp * stride;
-  base::Waypoint sink;
-  sink.position[0] = global_res_ * (double)goal_i_;
-  sink.position[1] = global_res_ * (double)goal_j_;
-  sink.position[2] = elevation_.empty() ? 0.0 : elevation_[idx(goal_i_, goal_j_)];
-  sink.heading = goal_heading_;
+  base::Waypoint sink = nodeSink(goal_i_, goal_j_, goal_heading_);
   const bool gs = !goals_.empty();
   int sink_k = gs ? -1 : 0;
   bool held = false;
@@ -2131,25 +2138,21 @@ std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getPaths(
   last_paths_device_ = false;
   last_paths_kernel_ms_ = 0.0;
   if (n && has_goal_) {
-    if (ctx_ && dT_ && dev_map_current_ && n <= 0xffffffffull && &dymu_extract_paths_device &&
-        &dymu_last_paths_ms && (goals_.empty() || goalsOnDevice())) {
+    if (descentOnDevice() && n <= 0xffffffffull && &dymu_extract_paths_device &&
+        &dymu_last_paths_ms) {
       pathsOnDevice(starts, out, st, sk, max_wp, stride);
       last_paths_device_ = true;
     } else {
       if (!goals_.empty()) ensureHostLabels();
       // the host descent per start (T() is thread-safe; descend writes no member)
-      const unsigned nt = (unsigned)std::min<size_t>(host_threads(), n);
-      std::atomic<size_t> next{0};
-      parallel_tasks(nt, [&](unsigned) {
-        for (size_t q = next++; q < n; q = next++) {
-          base::Waypoint w = starts[q];
-          w.position[0] -= global_offset_[0];
-          w.position[1] -= global_offset_[1];
-          st[q] = descend(w, out[q], max_wp, stride, &sk[q]);
-          for (auto& p : out[q]) {
-            p.position[0] += global_offset_[0];
-            p.position[1] += global_offset_[1];
-          }
+      for_each_start(n, [&](size_t q) {
+        base::Waypoint w = starts[q];
+        w.position[0] -= global_offset_[0];
+        w.position[1] -= global_offset_[1];
+        st[q] = descend(w, out[q], max_wp, stride, &sk[q]);
+        for (auto& p : out[q]) {
+          p.position[0] += global_offset_[0];
+          p.position[1] += global_offset_[1];
         }
       });
     }
@@ -2159,12 +2162,26 @@ std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getPaths(
   return out;
 }
 
+bool DyMuPathPlanner::descentOnDevice() const {
+  return ctx_ && dT_ && dev_map_current_ && (goals_.empty() || goalsOnDevice());
+}
+
+base::Waypoint DyMuPathPlanner::nodeSink(unsigned gi, unsigned gj, double heading) const {
+  base::Waypoint w;
+  w.position[0] = global_res_ * (double)gi;
+  w.position[1] = global_res_ * (double)gj;
+  w.position[2] = elevation_.empty() ? 0.0 : elevation_[idx(gi, gj)];
+  w.heading = heading;
+  return w;
+}
+
 namespace {
-// device buffers of one getPaths call, freed on every path out of it
+// device buffers of one call of `entry`, freed on every path out of it
 struct DeviceScratch {
   dymu_ctx* ctx;
+  const char* entry;
   std::vector<void*> ptrs;
-  explicit DeviceScratch(dymu_ctx* c) : ctx(c) {}
+  DeviceScratch(dymu_ctx* c, const char* name) : ctx(c), entry(name) {}
   ~DeviceScratch() {
     for (void* p : ptrs) (void)dymu_device_free(ctx, p);
   }
@@ -2172,7 +2189,7 @@ struct DeviceScratch {
   P* alloc(uint64_t count) {
     void* p = nullptr;
     if (dymu_device_alloc(ctx, sizeof(P) * std::max<uint64_t>(count, 1), &p) != DYMU_OK)
-      throw std::runtime_error(std::string("dymu: getPaths device allocation failed: ") +
+      throw std::runtime_error(std::string("dymu: ") + entry + " device allocation failed: " +
                                dymu_last_error(ctx));
     ptrs.push_back(p);
     return static_cast<P*>(p);
@@ -2183,6 +2200,62 @@ struct DeviceScratch {
   }
 };
 }  // namespace
+
+// One call of a device descent entry (pathsOnDevice, arriveStatsOnDevice,
+// pathStatsOnDevice): the map and the sink it runs on -- `target`, else dT_ with the goal
+// or, gs, the goal set, whose label map and sinks (grid-local) it puts on the device.
+struct DyMuPathPlanner::DeviceQuery {
+  DyMuPathPlanner& p;
+  const char* entry;
+  const double* map;
+  const unsigned gi, gj;
+  const bool gs;
+  const double tau;
+  DeviceScratch dev;
+  double* d_gxy = nullptr;
+  std::vector<double> xy;
+
+  DeviceQuery(DyMuPathPlanner& planner, const char* name, const PathTarget* target)
+      : p(planner), entry(name), map(target ? target->map : p.dT_),
+        gi(target ? target->gi : p.goal_i_), gj(target ? target->gj : p.goal_j_),
+        gs(!target && !p.goals_.empty()), tau(std::min(0.4, p.risk_distance_)),
+        dev(p.ctx_, name) {
+    if (!gs) return;
+    p.ensureDeviceLabels();
+    std::vector<double> gxy(2 * p.goals_.size());
+    for (size_t k = 0; k < p.goals_.size(); ++k) {
+      const base::Waypoint w = p.sinkWaypoint(k);
+      gxy[2 * k] = w.position[0];
+      gxy[2 * k + 1] = w.position[1];
+    }
+    d_gxy = dev.alloc<double>(gxy.size());
+    check(dymu_memcpy_h2d(p.ctx_, d_gxy, gxy.data(), sizeof(double) * gxy.size()), "upload");
+  }
+  void check(int rc, const char* what) const {
+    if (rc != DYMU_OK)
+      throw std::runtime_error(std::string("dymu: ") + entry + " " + what + " failed: " +
+                               dymu_strerror(rc) + " " + dymu_last_error(p.ctx_));
+  }
+  const uint32_t* labels() const { return gs ? p.d_label_ : nullptr; }
+  uint32_t goals() const { return gs ? (uint32_t)p.goals_.size() : 0u; }
+  // the m starts ids[0 .. m) (ids null: the first m), grid-local, on the device
+  double* uploadStarts(const std::vector<base::Waypoint>& starts, const uint32_t* ids, size_t m) {
+    xy.resize(2 * m);
+    for (size_t q = 0; q < m; ++q) {
+      const base::Waypoint& s = starts[ids ? ids[q] : q];
+      xy[2 * q] = s.position[0] - p.global_offset_[0];
+      xy[2 * q + 1] = s.position[1] - p.global_offset_[1];
+    }
+    double* d_xy = dev.alloc<double>(2 * (uint64_t)m);
+    check(dymu_memcpy_h2d(p.ctx_, d_xy, xy.data(), sizeof(double) * xy.size()), "upload");
+    return d_xy;
+  }
+  // the last launch's time joins the call's kernel time
+  void addKernelMs(int (*last_ms)(dymu_ctx*, double*)) {
+    double ms = 0.0;
+    if (last_ms(p.ctx_, &ms) == DYMU_OK) p.last_paths_kernel_ms_ += ms;
+  }
+};
 
 // getPaths' host post-pass: z from the elevation with the host's interpolate call and its
 // argument order (nextWaypoint), heading = atan2(-dcy, -dcx) with the host libm
@@ -2229,30 +2302,30 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
                                     std::vector<ArriveStats>* arrive) {
   constexpr uint64_t kOutBytes = 4ull << 30;  // device output of one batch, at most
   const size_t n = starts.size();
-  const double tau = std::min(0.4, risk_distance_);
-  auto check = [&](int rc, const char* what) {
-    if (rc != DYMU_OK)
-      throw std::runtime_error(std::string("dymu: getPaths ") + what + " failed: " +
-                               dymu_strerror(rc) + " " + dymu_last_error(ctx_));
+  DeviceQuery dq(*this, "getPaths", target);
+  DeviceScratch& dev = dq.dev;
+  auto check = [&](int rc, const char* what) { dq.check(rc, what); };
+  const double* map = dq.map;
+  const unsigned gi = dq.gi, gj = dq.gj;
+  const bool gs = dq.gs;
+  // the waypoints a path can end on, offsets added: the sink, or with a goal set (one sink
+  // per path back) every goal's
+  auto shifted = [&](base::Waypoint w) {
+    w.position[0] += global_offset_[0];
+    w.position[1] += global_offset_[1];
+    return w;
   };
-  const double* map = target ? target->map : dT_;
-  const unsigned gi = target ? target->gi : goal_i_, gj = target ? target->gj : goal_j_;
-  base::Waypoint sink;
-  sink.position[0] = global_res_ * (double)gi + global_offset_[0];
-  sink.position[1] = global_res_ * (double)gj + global_offset_[1];
-  sink.position[2] = elevation_[idx(gi, gj)];
-  sink.heading = target ? target->heading : goal_heading_;
-  // a goal set: the label map and the goals' sinks on the device, one sink per path back
-  const bool gs = !target && !goals_.empty();
+  const base::Waypoint sink = shifted(nodeSink(gi, gj, target ? target->heading : goal_heading_));
   std::vector<base::Waypoint> gsinks;
+  if (gs)
+    for (size_t k = 0; k < goals_.size(); ++k) gsinks.push_back(shifted(sinkWaypoint(k)));
   std::vector<int32_t> snk;
-  double* d_gxy = nullptr;
   // a straight descent across the grid is (nx + ny) / tau waypoints at most
   uint64_t cap = std::max<uint64_t>(1024, 4 * ((uint64_t)nx_ + ny_) / stride);
   cap = std::min<uint64_t>(cap, max_wp);
   std::vector<uint32_t> pending(n), again;
   for (size_t q = 0; q < n; ++q) pending[q] = (uint32_t)q;
-  std::vector<double> xy, raw;
+  std::vector<double> raw;
   std::vector<int32_t> cnt, sts;
   std::vector<ArriveStats> recs;  // arrive: the batch's records (status and sink are theirs)
   std::vector<uint64_t> off, len;  // per path: its row in `raw` (waypoints), its count
@@ -2261,54 +2334,33 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
     uint64_t width, base;
   };
   std::vector<Run> runs;
-  DeviceScratch dev(ctx_);
-  if (gs) {
-    ensureDeviceLabels();
-    std::vector<double> gxy(2 * goals_.size());
-    for (size_t k = 0; k < goals_.size(); ++k) {
-      base::Waypoint w = sinkWaypoint(k);
-      gxy[2 * k] = w.position[0];
-      gxy[2 * k + 1] = w.position[1];
-      w.position[0] += global_offset_[0];
-      w.position[1] += global_offset_[1];
-      gsinks.push_back(w);
-    }
-    d_gxy = dev.alloc<double>(gxy.size());
-    check(dymu_memcpy_h2d(ctx_, d_gxy, gxy.data(), sizeof(double) * gxy.size()), "upload");
-  }
   while (!pending.empty()) {
     const uint64_t per_batch = std::max<uint64_t>(1, kOutBytes / (32 * cap));
     again.clear();
     for (size_t b0 = 0; b0 < pending.size(); b0 += per_batch) {
       const uint32_t m = (uint32_t)std::min<uint64_t>(per_batch, pending.size() - b0);
       const uint32_t* ids = &pending[b0];
-      xy.resize(2 * (size_t)m);
-      for (uint32_t q = 0; q < m; ++q) {
-        xy[2 * q] = starts[ids[q]].position[0] - global_offset_[0];
-        xy[2 * q + 1] = starts[ids[q]].position[1] - global_offset_[1];
-      }
-      double* d_xy = dev.alloc<double>(2 * (uint64_t)m);
+      double* d_xy = dq.uploadStarts(starts, ids, m);
       int32_t* d_cnt = dev.alloc<int32_t>(m);
       int32_t* d_st = dev.alloc<int32_t>(m);
       double* d_out = dev.alloc<double>(4 * cap * m);
-      check(dymu_memcpy_h2d(ctx_, d_xy, xy.data(), sizeof(double) * xy.size()), "upload");
       int32_t* d_snk = gs && !arrive ? dev.alloc<int32_t>(m) : nullptr;
       ArriveStats* d_rec = arrive ? dev.alloc<ArriveStats>(m) : nullptr;
       if (arrive)
-        check(dymu_arrive_paths_device(ctx_, map, nx_, ny_, nx_, global_res_, gi, gj,
-                                       gs ? d_label_ : nullptr, d_gxy,
-                                       gs ? (uint32_t)goals_.size() : 0u, tau, d_xy, m,
-                                       (uint32_t)cap, stride, d_out, d_cnt, d_rec, nullptr),
+        check(dymu_arrive_paths_device(ctx_, map, nx_, ny_, nx_, global_res_, gi, gj, dq.labels(),
+                                       dq.d_gxy, dq.goals(), dq.tau, d_xy, m, (uint32_t)cap,
+                                       stride, d_out, d_cnt, d_rec, nullptr),
               "kernel");
       else if (gs)
-        check(dymu_extract_paths_goals_device(ctx_, dT_, nx_, ny_, nx_, global_res_, d_label_,
-                                              d_gxy, (uint32_t)goals_.size(), tau, d_xy, m,
+        check(dymu_extract_paths_goals_device(ctx_, map, nx_, ny_, nx_, global_res_, dq.labels(),
+                                              dq.d_gxy, dq.goals(), dq.tau, d_xy, m,
                                               (uint32_t)cap, stride, d_out, d_cnt, d_st, nullptr,
                                               d_snk),
               "kernel");
       else
-        check(dymu_extract_paths_device(ctx_, map, nx_, ny_, nx_, global_res_, gi, gj, tau, d_xy,
-                                        m, (uint32_t)cap, stride, d_out, d_cnt, d_st, nullptr),
+        check(dymu_extract_paths_device(ctx_, map, nx_, ny_, nx_, global_res_, gi, gj, dq.tau,
+                                        d_xy, m, (uint32_t)cap, stride, d_out, d_cnt, d_st,
+                                        nullptr),
               "kernel");
       cnt.resize(m);
       sts.resize(m);
@@ -2325,9 +2377,7 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
       } else {
         check(dymu_memcpy_d2h(ctx_, sts.data(), d_st, sizeof(int32_t) * m), "download");
       }
-      double ms = 0.0;
-      if ((arrive ? dymu_last_arrive_ms(ctx_, &ms) : dymu_last_paths_ms(ctx_, &ms)) == DYMU_OK)
-        last_paths_kernel_ms_ += ms;
+      dq.addKernelMs(arrive ? &dymu_last_arrive_ms : &dymu_last_paths_ms);
       // the waypoints: runs of consecutive paths, each downloaded by one pitched copy
       // as wide as its longest path -- a run grows while that moves at most twice its
       // waypoints (plus 1024), so few commands move little more than the counts
@@ -2364,18 +2414,14 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
       if (d_snk) dev.release(d_snk);
       if (d_rec) dev.release(d_rec);
       // host post-pass (slotsToPath) on the host threads
-      const unsigned nt = std::min<unsigned>(host_threads(), m);
-      std::atomic<uint32_t> next{0};
-      parallel_tasks(nt, [&](unsigned) {
-        for (uint32_t q = next++; q < m; q = next++) {
-          const uint32_t id = ids[q];
-          st[id] = sts[q];
-          if (sts[q] == -3 && cap < max_wp) continue;
-          sinks[id] = sts[q] == 1 ? snk[q] : -1;
-          if (arrive) (*arrive)[id] = recs[q];
-          slotsToPath(raw.data() + 4 * off[q], len[q], sts[q], starts[id],
-                      gs ? gsinks[(size_t)std::max(snk[q], 0)] : sink, out[id]);
-        }
+      for_each_start(m, [&](size_t q) {
+        const uint32_t id = ids[q];
+        st[id] = sts[q];
+        if (sts[q] == -3 && cap < max_wp) return;
+        sinks[id] = sts[q] == 1 ? snk[q] : -1;
+        if (arrive) (*arrive)[id] = recs[q];
+        slotsToPath(raw.data() + 4 * off[q], len[q], sts[q], starts[id],
+                    gs ? gsinks[(size_t)std::max(snk[q], 0)] : sink, out[id]);
       });
     }
     pending.swap(again);
@@ -2573,34 +2619,24 @@ std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getArrivingPaths(
   last_paths_device_ = false;
   last_paths_kernel_ms_ = 0.0;
   if (n && has_goal_) {
-    if (ctx_ && dT_ && dev_map_current_ && n <= 0xffffffffull && &dymu_arrive_paths_device &&
-        &dymu_last_arrive_ms && (goals_.empty() || goalsOnDevice())) {
+    if (descentOnDevice() && n <= 0xffffffffull && &dymu_arrive_paths_device &&
+        &dymu_last_arrive_ms) {
       pathsOnDevice(starts, out, st, sk, max_wp, stride, nullptr, &rec);
       last_paths_device_ = true;
     } else {
       if (!goals_.empty()) ensureHostLabels();
-      base::Waypoint sink;
-      sink.position[0] = global_res_ * (double)goal_i_ + global_offset_[0];
-      sink.position[1] = global_res_ * (double)goal_j_ + global_offset_[1];
-      sink.position[2] = elevation_[idx(goal_i_, goal_j_)];
-      sink.heading = goal_heading_;
-      const unsigned nt = (unsigned)std::min<size_t>(host_threads(), n);
-      std::atomic<size_t> next{0};
-      parallel_tasks(nt, [&](unsigned) {
+      for_each_start(n, [&](size_t q) {
         std::vector<double> slots;
-        for (size_t q = next++; q < n; q = next++) {
-          st[q] = descendArriving(starts[q].position[0] - global_offset_[0],
-                                  starts[q].position[1] - global_offset_[1], max_wp, stride,
-                                  &slots, rec[q]);
-          sk[q] = rec[q].sink;
-          base::Waypoint end = sink;
-          if (!goals_.empty() && sk[q] >= 0) {
-            end = sinkWaypoint((size_t)sk[q]);
-            end.position[0] += global_offset_[0];
-            end.position[1] += global_offset_[1];
-          }
-          slotsToPath(slots.data(), slots.size() / 4, st[q], starts[q], end, out[q]);
-        }
+        st[q] = descendArriving(starts[q].position[0] - global_offset_[0],
+                                starts[q].position[1] - global_offset_[1], max_wp, stride, &slots,
+                                rec[q]);
+        sk[q] = rec[q].sink;
+        base::Waypoint end = !goals_.empty() && sk[q] >= 0
+                                 ? sinkWaypoint((size_t)sk[q])
+                                 : nodeSink(goal_i_, goal_j_, goal_heading_);
+        end.position[0] += global_offset_[0];
+        end.position[1] += global_offset_[1];
+        slotsToPath(slots.data(), slots.size() / 4, st[q], starts[q], end, out[q]);
       });
     }
   }
@@ -2618,20 +2654,16 @@ std::vector<DyMuPathPlanner::ArriveStats> DyMuPathPlanner::getArrivingStats(
   last_paths_device_ = false;
   last_paths_kernel_ms_ = 0.0;
   if (!n || !has_goal_) return out;
-  if (!host && ctx_ && dT_ && dev_map_current_ && n <= 0xffffffffull &&
-      max_wp <= 0x7fffffffu && &dymu_arrive_paths_device && &dymu_last_arrive_ms &&
-      (goals_.empty() || goalsOnDevice())) {
+  if (!host && descentOnDevice() && n <= 0xffffffffull && max_wp <= 0x7fffffffu &&
+      &dymu_arrive_paths_device && &dymu_last_arrive_ms) {
     arriveStatsOnDevice(starts, out, max_wp, nullptr);
     last_paths_device_ = true;
     return out;
   }
   if (!goals_.empty()) ensureHostLabels();
-  const unsigned nt = (unsigned)std::min<size_t>(host_threads(), n);
-  std::atomic<size_t> next{0};
-  parallel_tasks(nt, [&](unsigned) {
-    for (size_t q = next++; q < n; q = next++)
-      (void)descendArriving(starts[q].position[0] - global_offset_[0],
-                            starts[q].position[1] - global_offset_[1], max_wp, 1, nullptr, out[q]);
+  for_each_start(n, [&](size_t q) {
+    (void)descendArriving(starts[q].position[0] - global_offset_[0],
+                          starts[q].position[1] - global_offset_[1], max_wp, 1, nullptr, out[q]);
   });
   return out;
 }
@@ -2642,44 +2674,15 @@ void DyMuPathPlanner::arriveStatsOnDevice(const std::vector<base::Waypoint>& sta
                                           std::vector<ArriveStats>& out, unsigned max_wp,
                                           const PathTarget* target) {
   const size_t n = starts.size();
-  const double tau = std::min(0.4, risk_distance_);
-  auto check = [&](int rc, const char* what) {
-    if (rc != DYMU_OK)
-      throw std::runtime_error(std::string("dymu: getArrivingStats ") + what + " failed: " +
-                               dymu_strerror(rc) + " " + dymu_last_error(ctx_));
-  };
-  const double* map = target ? target->map : dT_;
-  const unsigned gi = target ? target->gi : goal_i_, gj = target ? target->gj : goal_j_;
-  const bool gs = !target && !goals_.empty();
-  DeviceScratch dev(ctx_);
-  double* d_gxy = nullptr;
-  if (gs) {
-    ensureDeviceLabels();
-    std::vector<double> gxy(2 * goals_.size());
-    for (size_t k = 0; k < goals_.size(); ++k) {
-      const base::Waypoint w = sinkWaypoint(k);
-      gxy[2 * k] = w.position[0];
-      gxy[2 * k + 1] = w.position[1];
-    }
-    d_gxy = dev.alloc<double>(gxy.size());
-    check(dymu_memcpy_h2d(ctx_, d_gxy, gxy.data(), sizeof(double) * gxy.size()), "upload");
-  }
-  std::vector<double> xy(2 * n);
-  for (size_t q = 0; q < n; ++q) {
-    xy[2 * q] = starts[q].position[0] - global_offset_[0];
-    xy[2 * q + 1] = starts[q].position[1] - global_offset_[1];
-  }
-  double* d_xy = dev.alloc<double>(2 * (uint64_t)n);
-  ArriveStats* d_rec = dev.alloc<ArriveStats>(n);
-  check(dymu_memcpy_h2d(ctx_, d_xy, xy.data(), sizeof(double) * xy.size()), "upload");
-  check(dymu_arrive_paths_device(ctx_, map, nx_, ny_, nx_, global_res_, gi, gj,
-                                 gs ? d_label_ : nullptr, d_gxy,
-                                 gs ? (uint32_t)goals_.size() : 0u, tau, d_xy, (uint32_t)n, max_wp,
-                                 1, nullptr, nullptr, d_rec, nullptr),
-        "kernel");
-  check(dymu_memcpy_d2h(ctx_, out.data(), d_rec, sizeof(ArriveStats) * n), "download");
-  double ms = 0.0;
-  if (dymu_last_arrive_ms(ctx_, &ms) == DYMU_OK) last_paths_kernel_ms_ = ms;
+  DeviceQuery dq(*this, "getArrivingStats", target);
+  double* d_xy = dq.uploadStarts(starts, nullptr, n);
+  ArriveStats* d_rec = dq.dev.alloc<ArriveStats>(n);
+  dq.check(dymu_arrive_paths_device(ctx_, dq.map, nx_, ny_, nx_, global_res_, dq.gi, dq.gj,
+                                    dq.labels(), dq.d_gxy, dq.goals(), dq.tau, d_xy, (uint32_t)n,
+                                    max_wp, 1, nullptr, nullptr, d_rec, nullptr),
+           "kernel");
+  dq.check(dymu_memcpy_d2h(ctx_, out.data(), d_rec, sizeof(ArriveStats) * n), "download");
+  dq.addKernelMs(&dymu_last_arrive_ms);
 }
 
 // ---- getPathStats: per-path summaries (extension) ----
@@ -2694,9 +2697,8 @@ std::vector<DyMuPathPlanner::PathStats> DyMuPathPlanner::getPathStats(
   last_paths_device_ = false;
   last_paths_kernel_ms_ = 0.0;
   if (!n || !has_goal_) return out;
-  if (!host && ctx_ && dT_ && dF_ && dev_map_current_ && speed_valid_ && n <= 0x7fffffffull &&
-      max_wp <= 0x7fffffffu && &dymu_path_stats_device && &dymu_last_path_stats_ms &&
-      (goals_.empty() || goalsOnDevice())) {
+  if (!host && descentOnDevice() && dF_ && speed_valid_ && n <= 0x7fffffffull &&
+      max_wp <= 0x7fffffffu && &dymu_path_stats_device && &dymu_last_path_stats_ms) {
     pathStatsOnDevice(starts, out, max_wp, field, nullptr);
     last_paths_device_ = true;
     return out;
@@ -2704,25 +2706,21 @@ std::vector<DyMuPathPlanner::PathStats> DyMuPathPlanner::getPathStats(
   if (!goals_.empty()) ensureHostLabels();
   if (!speed_valid_) syncGlobalRisk();
   const double* f0 = speed_valid_ ? speed_.data() : nullptr;
-  const unsigned nt = (unsigned)std::min<size_t>(host_threads(), n);
-  std::atomic<size_t> next{0};
-  parallel_tasks(nt, [&](unsigned) {
-    std::vector<base::Waypoint> none;
-    for (size_t q = next++; q < n; q = next++) {
-      base::Waypoint w = starts[q];
-      w.position[0] -= global_offset_[0];
-      w.position[1] -= global_offset_[1];
-      PathAccum acc;
-      acc.nf = field ? 2u : 1u;
-      acc.f[0] = f0;
-      acc.f[1] = field;
-      int sink = -1;
-      const int st = descend(w, none, max_wp, 1, &sink, &acc);
-      if (st == -1) continue;  // the empty record
-      acc.r.status = st;
-      acc.r.sink = st == 1 ? sink : -1;
-      out[q] = acc.r;
-    }
+  for_each_start(n, [&](size_t q) {
+    std::vector<base::Waypoint> none;  // stays empty: the waypoints join acc
+    base::Waypoint w = starts[q];
+    w.position[0] -= global_offset_[0];
+    w.position[1] -= global_offset_[1];
+    PathAccum acc;
+    acc.nf = field ? 2u : 1u;
+    acc.f[0] = f0;
+    acc.f[1] = field;
+    int sink = -1;
+    const int st = descend(w, none, max_wp, 1, &sink, &acc);
+    if (st == -1) return;  // the empty record
+    acc.r.status = st;
+    acc.r.sink = st == 1 ? sink : -1;
+    out[q] = acc.r;
   });
   return out;
 }
@@ -2734,54 +2732,25 @@ void DyMuPathPlanner::pathStatsOnDevice(const std::vector<base::Waypoint>& start
                                         std::vector<PathStats>& out, unsigned max_wp,
                                         const double* field, const PathTarget* target) {
   const size_t n = starts.size();
-  const double tau = std::min(0.4, risk_distance_);
-  auto check = [&](int rc, const char* what) {
-    if (rc != DYMU_OK)
-      throw std::runtime_error(std::string("dymu: getPathStats ") + what + " failed: " +
-                               dymu_strerror(rc) + " " + dymu_last_error(ctx_));
-  };
-  const double* map = target ? target->map : dT_;
-  const unsigned gi = target ? target->gi : goal_i_, gj = target ? target->gj : goal_j_;
-  const bool gs = !target && !goals_.empty();
-  DeviceScratch dev(ctx_);
-  double* d_gxy = nullptr;
-  if (gs) {
-    ensureDeviceLabels();
-    std::vector<double> gxy(2 * goals_.size());
-    for (size_t k = 0; k < goals_.size(); ++k) {
-      const base::Waypoint w = sinkWaypoint(k);
-      gxy[2 * k] = w.position[0];
-      gxy[2 * k + 1] = w.position[1];
-    }
-    d_gxy = dev.alloc<double>(gxy.size());
-    check(dymu_memcpy_h2d(ctx_, d_gxy, gxy.data(), sizeof(double) * gxy.size()), "upload");
-  }
+  DeviceQuery dq(*this, "getPathStats", target);
   if (field) {
     if (!d_pfield_) {
       void* p = nullptr;
-      check(dymu_device_alloc(ctx_, sizeof(double) * dcells_, &p), "field allocation");
+      dq.check(dymu_device_alloc(ctx_, sizeof(double) * dcells_, &p), "field allocation");
       d_pfield_ = static_cast<double*>(p);
     }
-    check(dymu_memcpy_h2d(ctx_, d_pfield_, field, sizeof(double) * dcells_), "field upload");
+    dq.check(dymu_memcpy_h2d(ctx_, d_pfield_, field, sizeof(double) * dcells_), "field upload");
   }
-  std::vector<double> xy(2 * n);
-  for (size_t q = 0; q < n; ++q) {
-    xy[2 * q] = starts[q].position[0] - global_offset_[0];
-    xy[2 * q + 1] = starts[q].position[1] - global_offset_[1];
-  }
-  double* d_xy = dev.alloc<double>(2 * (uint64_t)n);
-  PathStats* d_rec = dev.alloc<PathStats>(n);
-  check(dymu_memcpy_h2d(ctx_, d_xy, xy.data(), sizeof(double) * xy.size()), "upload");
+  double* d_xy = dq.uploadStarts(starts, nullptr, n);
+  PathStats* d_rec = dq.dev.alloc<PathStats>(n);
   const double* fields[2] = {dF_, d_pfield_};
   const uint64_t pitch[2] = {nx_, nx_};
-  check(dymu_path_stats_device(ctx_, map, nx_, ny_, nx_, global_res_, gi, gj,
-                               gs ? d_label_ : nullptr, d_gxy, gs ? (uint32_t)goals_.size() : 0u,
-                               tau, d_xy, (uint32_t)n, max_wp, fields, pitch, field ? 2u : 1u, 0u,
-                               d_rec, nullptr),
-        "kernel");
-  check(dymu_memcpy_d2h(ctx_, out.data(), d_rec, sizeof(PathStats) * n), "download");
-  double ms = 0.0;
-  if (dymu_last_path_stats_ms(ctx_, &ms) == DYMU_OK) last_paths_kernel_ms_ = ms;
+  dq.check(dymu_path_stats_device(ctx_, dq.map, nx_, ny_, nx_, global_res_, dq.gi, dq.gj,
+                                  dq.labels(), dq.d_gxy, dq.goals(), dq.tau, d_xy, (uint32_t)n,
+                                  max_wp, fields, pitch, field ? 2u : 1u, 0u, d_rec, nullptr),
+           "kernel");
+  dq.check(dymu_memcpy_d2h(ctx_, out.data(), d_rec, sizeof(PathStats) * n), "download");
+  dq.addKernelMs(&dymu_last_path_stats_ms);
 }
 
 // ---- getRouteFields: every cell's node route at once (extension) ----
@@ -3105,12 +3074,7 @@ std::vector<dymu_seed> DyMuPathPlanner::seedList() const {
 
 base::Waypoint DyMuPathPlanner::sinkWaypoint(size_t k) const {
   const Goal& g = goals_[k];
-  base::Waypoint w;
-  w.position[0] = global_res_ * (double)g.i;
-  w.position[1] = global_res_ * (double)g.j;
-  w.position[2] = elevation_.empty() ? 0.0 : elevation_[idx(g.i, g.j)];
-  w.heading = g.heading;
-  return w;
+  return nodeSink(g.i, g.j, g.heading);
 }
 
 // computeEntireTotalCostMap for a goal set: the cold multi-source solve -- always,
@@ -4019,7 +3983,7 @@ void DyMuPathPlanner::gatherBatch(const std::vector<base::Waypoint>& points,
         throw std::runtime_error(std::string("dymu: getTotalCosts ") + what + " failed: " +
                                  dymu_strerror(rc) + " " + dymu_last_error(ctx_));
     };
-    DeviceScratch dev(ctx_);
+    DeviceScratch dev(ctx_, "getTotalCosts");
     double* d_xy = dev.alloc<double>(xy.size());
     double* d_out = dev.alloc<double>(res.size());
     check(dymu_memcpy_h2d(ctx_, d_xy, xy.data(), sizeof(double) * xy.size()), "upload");
