@@ -544,7 +544,37 @@ class DyMuPathPlanner {
   // ... on map b of the batch with goal b as the root (always on the device; the speed is
   // the one the batch was solved with).  Throws std::invalid_argument for b >= batchCount().
   RouteFields getRouteFieldsTo(unsigned b, const RouteRequest& request);
-  // whether the last getPaths / getPathStats / getArriving* / getRouteFields ran on the device, and its kernel time (HIP
+  // How much of the map drains through every cell (include/dymu_fim.h
+  // states the definition with dymu_usage_out): the upstream side of getRouteFields' forest.
+  // Per cell usage, the weight of all cells whose route passes through it (itself included;
+  // request.weights, a row-major nx*ny array, or 1 a cell), far, the largest total cost among
+  // them, and sink, the goal the route ends on; per goal its catchment, the usage at its
+  // root (0 for a dominated goal).  A cell without a route gets 0 / NaN / DYMU_LABEL_NONE.
+  // request.outputs: what is wanted (kUsage* bits); only that is computed.  The device route
+  // is getRouteFields' (dymu_route_usage_device while the device map is current), else -- or
+  // with host = true -- the same definition on the host mirror, the cells in descending
+  // total cost, each added into its parent.  The two are equal bit for bit.  current_path is
+  // not touched.  Without a goal every cell is without a route and catchment is empty.
+  enum : uint32_t {
+    kUsageUsage = 1u, kUsageFar = 2u, kUsageSink = 4u, kUsageCatchment = 8u, kUsageAll = 15u
+  };
+  struct RouteUsageRequest {
+    uint32_t outputs = kUsageAll;
+    const uint32_t* weights = nullptr;
+    bool host = false;
+  };
+  struct RouteUsage {  // row-major nx*ny maps and one entry per goal; empty where not requested
+    std::vector<uint64_t> usage;
+    std::vector<double> far;
+    std::vector<uint32_t> sink;
+    std::vector<uint64_t> catchment;
+    uint32_t rounds = 0;  // doubling rounds of the device route (0 on the host)
+  };
+  RouteUsage getRouteUsage(const RouteUsageRequest& request);
+  // ... on map b of the batch with goal b as the root (always on the device).  Throws
+  // std::invalid_argument for b >= batchCount().
+  RouteUsage getRouteUsageTo(unsigned b, const RouteUsageRequest& request);
+  // whether the last getPaths / getPathStats / getArriving* / getRouteFields / getRouteUsage ran on the device, and its kernel time (HIP
   // events, ms)
   bool lastPathsOnDevice() const { return last_paths_device_; }
   double lastPathsKernelMs() const { return last_paths_kernel_ms_; }
@@ -757,6 +787,17 @@ class DyMuPathPlanner {
   void routeFieldsOnDevice(const RouteRequest& rq, const double* map,
                            const std::vector<dymu_seed>& seeds, RouteFields& out);
   void routeFieldsOnHost(const RouteRequest& rq, RouteFields& out);
+  // getRouteUsage on the device: the caller's weights (dcells_ uint32), the output maps
+  // (usage, far, sink) and the engine's workspace, parked and dropped as the buffers above
+  uint32_t* d_uweight_ = nullptr;
+  uint64_t* d_uout_usage_ = nullptr;
+  double* d_uout_far_ = nullptr;
+  uint32_t* d_uout_sink_ = nullptr;
+  void* d_usage_ws_ = nullptr;
+  size_t usage_ws_bytes_ = 0;
+  void routeUsageOnDevice(const RouteUsageRequest& rq, const double* map,
+                          const std::vector<dymu_seed>& seeds, RouteUsage& out);
+  void routeUsageOnHost(const RouteUsageRequest& rq, RouteUsage& out);
   void dropRouteBuffers();
   // the batch (computeTotalCostMaps): its goals and the solved stack, plane b at
   // dT_batch_ + b * dymu_batch_plane_rows(ny_) * nx_ (pitch nx_)

@@ -407,6 +407,71 @@ int dymu_last_route_fields_ms(dymu_ctx* ctx, double* ms);
 /* ... and its parts: stage_ms[0] the init and root kernels, [1] the rounds (the counter
  * reads between them included), [2] the finalize kernel. */
 int dymu_last_route_fields_stages(dymu_ctx* ctx, double stage_ms[3]);
+/* ---- how much of the map drains through every cell (DyMuPathPlanner::getRouteUsage) ----
+ * The upstream question on the forest of dymu_route_fields_device.  A function of T (nx x
+ * ny, pitch ld, nx*ny < 2^31), of the seed list and of an optional weight map alone, the
+ * same on host and device.  root, rp(c), route(c) and "no route" are
+ * dymu_route_fields_device's, word for word.  w(c) = d_weight[j*weight_ld + i] (uint32);
+ * with a NULL weight map w(c) = 1 for every cell.  sub(c) = the cells d that have a route
+ * and whose route contains c (c itself if it has a route).
+ * Per cell with a route:
+ *   usage   the sum over d in sub(c) of w(d), uint64: integers, below 2^31 * 2^32, no
+ *           overflow; a leaf holds w(c)
+ *   far     the maximum over d in sub(c) of T[d]: the cost-to-go of the costliest start
+ *           that passes through c, so far[c] >= T[c]
+ *   sink    the root k the route ends on, as dymu_route_out.sink
+ * A cell without a route (a dead-end tree is entirely without one) gets usage 0, far NaN,
+ * sink DYMU_LABEL_NONE.  catchment[k] (HOST, n_seeds entries) = usage at root k's cell, 0
+ * for a seed that is no root (dominated, or a duplicate that lost its cell).
+ * Two calls give identical bytes, and device and host are equal bit for bit.  far is
+ * specified for maps whose routed cells have T >= +0.0 and finite, which every solve
+ * leaves; the contract ends there (a -0.0 or a negative T in a routed cell leaves far
+ * unspecified; usage and sink hold for every map). */
+typedef struct dymu_usage_out {
+  /* maps of nx x ny elements, pitch ld elements (>= nx); any may be NULL: not computed,
+   * and what only it needs is not carried */
+  uint64_t* usage;
+  double* far;
+  uint32_t* sink;
+  uint64_t ld;
+} dymu_usage_out;
+/* The bytes of workspace dymu_route_usage_device needs for these outputs (the pointers of
+ * `out` are only tested against NULL; out NULL: every output).  0 for nx*ny = 0 or >= 2^31.
+ * 512 bytes of counters, two 4-byte entries a cell, two 8-byte sums a cell if usage is
+ * asked for, one 8-byte maximum a cell if far is: at most 32 bytes a cell.  The catchment
+ * needs the sums: size a call that wants it with a non-NULL usage. */
+size_t dymu_route_usage_workspace(uint32_t nx, uint32_t ny, const dymu_usage_out* out);
+/* usage, far and sink of all cells of dT for the seeds (HOST array) and the weights
+ * (device, pitch weight_ld >= nx; NULL: unit weights) into the device maps of *out, and
+ * the catchments into the HOST array catchment (may be NULL).  d_workspace: device memory
+ * of at least dymu_route_usage_workspace(...) bytes (with the sums if catchment is given),
+ * 256-byte aligned, the caller's (dymu_device_alloc_cached); the call allocates and frees
+ * nothing map-sized.  Its first 64 uint32 hold, after the call, per round r the entries
+ * still open after it ([r]) and the entries that sent -- one 8-byte atomic per carried
+ * array each -- in it ([32 + r]).  *rounds (may be NULL) = doubling rounds run
+ * (DYMU_ERR_NOT_CONVERGED beyond 32; 31 always suffice).  A batch plane is an ordinary map
+ * pointer.  Asynchronous on `stream` but for the reads of the round counters (one every
+ * four rounds) and, with a catchment, a final wait: the outputs are complete once the
+ * stream has drained.  One call at a time per context.  DYMU_ERR_ARG, before any device
+ * work: what dymu_route_fields_device rejects that applies here (a NULL ctx, map, out or
+ * workspace, nx or ny 0, ld or out->ld < nx, nx*ny >= 2^31, a bad seed list, a misaligned
+ * workspace), weight_ld < nx with a weight map, all of usage, far, sink and catchment
+ * NULL, workspace_bytes too small. */
+int dymu_route_usage_device(dymu_ctx* ctx, const double* dT, uint32_t nx, uint32_t ny,
+                            uint64_t ld, const dymu_seed* seeds, uint32_t n_seeds,
+                            const uint32_t* d_weight, uint64_t weight_ld,
+                            const dymu_usage_out* out, uint64_t* catchment, void* d_workspace,
+                            size_t workspace_bytes, void* stream, uint32_t* rounds);
+/* Device time (ms, HIP events) of the last dymu_route_usage_device, first kernel to last;
+ * waits for it.  DYMU_ERR_STATE before the first one. */
+int dymu_last_route_usage_ms(dymu_ctx* ctx, double* ms);
+/* ... and its parts: stage_ms[0] the init and root kernels, [1] the rounds (the counter
+ * reads between them included), [2] the final kernels. */
+int dymu_last_route_usage_stages(dymu_ctx* ctx, double stage_ms[3]);
+/* ... and round by round: round_ms[r] for r < *rounds (the rounds launched, those behind
+ * the closing one included; round_ms holds 32 entries).  A counter read falls into the
+ * round after it. */
+int dymu_last_route_usage_round_ms(dymu_ctx* ctx, double round_ms[32], uint32_t* rounds);
 
 /* ---- batched solves: many maps in one pass sequence ----
  * A batch is B planes of nx x ny cells stacked into ONE domain of nx x (B * P) cells with

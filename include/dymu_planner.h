@@ -173,6 +173,23 @@ int dymu_planner_get_route_fields(dymu_planner* p, const double* const* fields, 
  * for b >= batch_count. */
 int dymu_planner_get_route_fields_to(dymu_planner* p, uint32_t b, const double* const* fields,
                                      int n_fields, const dymu_route_out* out, uint32_t* rounds);
+/* getRouteUsage (extension, DyMu.hpp): how much of the map drains through
+ * every cell, as include/dymu_fim.h defines it with dymu_usage_out.  weights: a row-major
+ * ny x nx uint32 array, or NULL for 1 a cell.  out: HOST maps of nx * ny elements (out->ld
+ * is ignored: the pitch is nx); a NULL map is not computed.  catchment: n_catchment HOST
+ * entries, one per goal (dymu_planner_goal_count; entries beyond the goals are set to 0),
+ * or NULL.  DYMU_ERR_ARG if nothing is asked for, or if n_catchment is below the number of
+ * goals.  The route is get_paths' unless host is non-zero;
+ * dymu_planner_last_paths_on_device / _kernel_ms report the call.  *rounds (may be NULL) =
+ * doubling rounds on the device, 0 on the host.  Returns DYMU_OK or a negative status. */
+int dymu_planner_get_route_usage(dymu_planner* p, const uint32_t* weights, int host,
+                                 const dymu_usage_out* out, uint64_t* catchment,
+                                 uint32_t n_catchment, uint32_t* rounds);
+/* ... on map b of the batch with goal b as the root (always on the device; one catchment
+ * entry).  DYMU_ERR_ARG for b >= batch_count. */
+int dymu_planner_get_route_usage_to(dymu_planner* p, uint32_t b, const uint32_t* weights,
+                                    const dymu_usage_out* out, uint64_t* catchment,
+                                    uint32_t n_catchment, uint32_t* rounds);
 /* goalI() / goalJ(): the single goal's cell (goal 0 of a goal set); 1 = written, 0 = no
  * goal set yet */
 int dymu_planner_goal_cell(dymu_planner* p, uint32_t* i, uint32_t* j);

@@ -42,6 +42,12 @@ struct dymu_ctx {
   // the last dymu_route_fields_device: before init, after it, after the rounds, after finalize
   hipEvent_t ev_route[4] = {nullptr, nullptr, nullptr, nullptr};
   bool route_timed = false;
+  // the last dymu_route_usage_device: the same four stamps, and one before every round
+  // launched with one behind the last
+  hipEvent_t ev_usage[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev_usage_round[kRouteRounds + 1] = {};
+  uint32_t usage_rounds_timed = 0;
+  bool usage_timed = false;
   dymu_opts opts{};
   int cu_count = 256;
   uint32_t* d_xchg = nullptr;  // k_exchange's block ticket (zero between launches)
@@ -1740,6 +1746,10 @@ int dymu_destroy(dymu_ctx* c) {
   if (c->d_lab_cnt) (void)hipFree(c->d_lab_cnt);
   for (hipEvent_t e : c->ev_route)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->ev_usage)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->ev_usage_round)
+    if (e) (void)hipEventDestroy(e);
   if (c->d_lists) (void)hipFree(c->d_lists);
   if (c->d_tile_epoch) (void)hipFree(c->d_tile_epoch);
   if (c->d_counts) (void)hipFree(c->d_counts);
@@ -2268,6 +2278,180 @@ int dymu_last_route_fields_stages(dymu_ctx* c, double stage_ms[3]) {
     const int rc = event_ms(c, c->ev_route[k], c->ev_route[k + 1], &stage_ms[k]);
     if (rc) return rc;
   }
+  return DYMU_OK;
+}
+
+// ---- how much of the map drains through every cell (usage_kernels.hip) ----
+namespace {
+constexpr size_t kUsageCntBytes = 512;  // 2 * kRouteRounds counters at the workspace's start
+static_assert(sizeof(uint32_t) * 2 * kRouteRounds <= kUsageCntBytes, "the counters fit");
+struct UsageState {
+  uint32_t* next[2];
+  unsigned long long* sum[2];
+  unsigned long long* far;
+};
+// the workspace's layout: the counters, the two entry arrays, the two sums, the maximum;
+// returns the bytes used, and with ws the arrays
+size_t usage_layout(uint64_t n, bool sums, bool far, char* ws, UsageState* s) {
+  size_t off = kUsageCntBytes;
+  auto take = [&](size_t elem) {
+    char* p = ws ? ws + off : nullptr;
+    off += (elem * n + kRouteAlign - 1) / kRouteAlign * kRouteAlign;
+    return p;
+  };
+  UsageState d{};
+  d.next[0] = reinterpret_cast<uint32_t*>(take(4));
+  d.next[1] = reinterpret_cast<uint32_t*>(take(4));
+  if (sums) {
+    d.sum[0] = reinterpret_cast<unsigned long long*>(take(8));
+    d.sum[1] = reinterpret_cast<unsigned long long*>(take(8));
+  }
+  if (far) d.far = reinterpret_cast<unsigned long long*>(take(8));
+  if (s) *s = d;
+  return off;
+}
+}  // namespace
+
+size_t dymu_route_usage_workspace(uint32_t nx, uint32_t ny, const dymu_usage_out* out) {
+  const uint64_t n = (uint64_t)nx * ny;
+  if (n == 0 || n >= (1ull << 31)) return 0;
+  return usage_layout(n, !out || out->usage, !out || out->far, nullptr, nullptr);
+}
+
+int dymu_route_usage_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
+                            const dymu_seed* seeds, uint32_t n_seeds, const uint32_t* d_weight,
+                            uint64_t weight_ld, const dymu_usage_out* out, uint64_t* catchment,
+                            void* d_workspace, size_t workspace_bytes, void* stream,
+                            uint32_t* rounds) {
+  if (!c || !dT || !out || !d_workspace || nx == 0 || ny == 0 || ld < nx || out->ld < nx)
+    return DYMU_ERR_ARG;
+  if ((uint64_t)nx * ny >= (1ull << 31)) return DYMU_ERR_ARG;  // entries hold a cell index + tag
+  if (d_weight && weight_ld < nx) return DYMU_ERR_ARG;
+  if (!out->usage && !out->far && !out->sink && !catchment) return DYMU_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(d_workspace) % kRouteAlign) return DYMU_ERR_ARG;
+  const uint32_t n = nx * ny;
+  const bool sums = out->usage || catchment;
+  UsageState s{};
+  if (usage_layout(n, sums, out->far != nullptr, static_cast<char*>(d_workspace), &s) >
+      workspace_bytes)
+    return DYMU_ERR_ARG;
+  // round 0 by neighbour reads instead of atomics (the faster form at
+  // 16384^2); development override: DYMU_USAGE_ROUND0=0 runs the plain atomic form, the
+  // reference path
+  bool gather0 = true;
+  if (const char* kv = std::getenv("DYMU_USAGE_ROUND0")) gather0 = std::atoi(kv) != 0;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  const GoalSeed* d_seeds = nullptr;
+  // the catchments come back through the transfer buffer, behind the seeds
+  const uint64_t catch_bytes = catchment ? sizeof(uint64_t) * (uint64_t)n_seeds : 0;
+  int rc = stage_seeds(c, nx, ny, seeds, n_seeds, st, &d_seeds, nullptr, catch_bytes);
+  if (rc) return rc;
+  const uint64_t catch_off = sizeof(GoalSeed) * (uint64_t)n_seeds;  // a multiple of 16
+  for (hipEvent_t& e : c->ev_usage)
+    if (!e) HIPC(c, hipEventCreate(&e));
+  for (hipEvent_t& e : c->ev_usage_round)
+    if (!e) HIPC(c, hipEventCreate(&e));
+  uint32_t* d_cnt = static_cast<uint32_t*>(d_workspace);
+  RouteInitArgs ia{};  // the entries only: no hop counts, no fields
+  ia.T = dT;
+  ia.ld = (int64_t)ld;
+  ia.nx = nx;
+  ia.ny = ny;
+  ia.res = 1.0;
+  ia.s0.next = s.next[0];
+  ia.s1.next = s.next[1];
+  c->usage_timed = false;
+  HIPC(c, hipEventRecord(c->ev_usage[0], st));
+  HIPC(c, hipMemsetAsync(d_cnt, 0, kUsageCntBytes, st));
+  HIPC(c, launch_route_init(ia, d_seeds, n_seeds, st));
+  HIPC(c, launch_usage_init(dT, (int64_t)ld, nx, ny, d_weight, (int64_t)weight_ld, s.sum[0], s.far,
+                            st));
+  HIPC(c, hipEventRecord(c->ev_usage[1], st));
+  // rounds in batches of 4 between read-backs of the counters, as dymu_route_fields_device
+  // runs them.  Round r reads buffer r & 1.
+  uint32_t launched = 0, done = 0;
+  uint32_t h_cnt[kRouteRounds];
+  while (done == 0 && launched < kRouteRounds) {
+    const uint32_t r0 = launched;
+    for (uint32_t k = 0; k < 4 && launched < kRouteRounds; ++k, ++launched) {
+      UsageRoundArgs ra{};
+      ra.nx = nx;
+      ra.ny = ny;
+      ra.nsrc = s.next[launched & 1u];
+      ra.ndst = s.next[(launched + 1u) & 1u];
+      ra.asrc = s.sum[launched & 1u];
+      ra.adst = s.sum[(launched + 1u) & 1u];
+      ra.far = s.far;
+      HIPC(c, hipEventRecord(c->ev_usage_round[launched], st));
+      HIPC(c, launch_usage_round(ra, d_cnt, launched, gather0, st));
+    }
+    HIPC(c, hipStreamSynchronize(st));
+    HIPC(c, hipMemcpy(h_cnt + r0, d_cnt + r0, sizeof(uint32_t) * (launched - r0),
+                      hipMemcpyDeviceToHost));
+    for (uint32_t r = r0; r < launched && done == 0; ++r)
+      if (h_cnt[r] == 0) done = r + 1;
+  }
+  HIPC(c, hipEventRecord(c->ev_usage_round[launched], st));
+  c->usage_rounds_timed = launched;
+  HIPC(c, hipEventRecord(c->ev_usage[2], st));
+  const uint32_t ran = done ? done : launched;
+  UsageFinalArgs fa{};
+  fa.nx = nx;
+  fa.ny = ny;
+  fa.next = s.next[ran & 1u];  // the state after `ran` rounds
+  fa.sum = s.sum[ran & 1u];
+  fa.far = s.far;
+  fa.n_seeds = n_seeds;
+  fa.o_usage = reinterpret_cast<unsigned long long*>(out->usage);
+  fa.o_far = out->far;
+  fa.o_sink = out->sink;
+  fa.o_ld = (int64_t)out->ld;
+  unsigned long long* d_catch =
+      catchment ? reinterpret_cast<unsigned long long*>(static_cast<char*>(c->d_xfer) + catch_off)
+                : nullptr;
+  HIPC(c, launch_usage_final(fa, d_seeds, d_catch, st));
+  HIPC(c, hipEventRecord(c->ev_usage[3], st));
+  c->usage_timed = true;
+  if (rounds) *rounds = ran;
+  if (catchment) {  // written by the kernel in host memory
+    HIPC(c, hipStreamSynchronize(st));
+    std::memcpy(catchment, static_cast<const char*>(c->h_xfer) + catch_off, (size_t)catch_bytes);
+  }
+  if (done == 0) {
+    c->last_error = "route usage: round cap reached";
+    return DYMU_ERR_NOT_CONVERGED;
+  }
+  return DYMU_OK;
+}
+
+int dymu_last_route_usage_ms(dymu_ctx* c, double* ms) {
+  if (!c || !ms) return DYMU_ERR_ARG;
+  if (!c->usage_timed) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  return event_ms(c, c->ev_usage[0], c->ev_usage[3], ms);
+}
+
+int dymu_last_route_usage_stages(dymu_ctx* c, double stage_ms[3]) {
+  if (!c || !stage_ms) return DYMU_ERR_ARG;
+  if (!c->usage_timed) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  for (int k = 0; k < 3; ++k) {
+    const int rc = event_ms(c, c->ev_usage[k], c->ev_usage[k + 1], &stage_ms[k]);
+    if (rc) return rc;
+  }
+  return DYMU_OK;
+}
+
+int dymu_last_route_usage_round_ms(dymu_ctx* c, double round_ms[32], uint32_t* rounds) {
+  if (!c || !round_ms || !rounds) return DYMU_ERR_ARG;
+  if (!c->usage_timed) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  for (uint32_t r = 0; r < c->usage_rounds_timed; ++r) {
+    const int rc = event_ms(c, c->ev_usage_round[r], c->ev_usage_round[r + 1], &round_ms[r]);
+    if (rc) return rc;
+  }
+  *rounds = c->usage_rounds_timed;
   return DYMU_OK;
 }
 

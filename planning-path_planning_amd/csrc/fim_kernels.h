@@ -526,6 +526,42 @@ hipError_t launch_route_round(const RouteState& src, const RouteState& dst, uint
                               uint32_t* cnt, uint32_t round, hipStream_t st);
 hipError_t launch_route_final(const RouteFinalArgs& a, hipStream_t st);
 
+// how much of the map drains through every cell (usage_kernels.hip): the
+// reverse of the doubling above on the same entries (launch_route_init with the `next`
+// arrays only).  All arrays are workspace, pitch nx; a null sum or far array is not carried.
+struct UsageRoundArgs {
+  uint32_t nx, ny;
+  const uint32_t* nsrc;  // the entries of state r
+  uint32_t* ndst;        // ... of state r + 1
+  const unsigned long long* asrc;  // A_r
+  unsigned long long* adst;        // A_{r+1}
+  unsigned long long* far;         // M, bit patterns of doubles >= +0.0, in place
+};
+struct UsageFinalArgs {
+  uint32_t nx, ny;
+  const uint32_t* next;  // the final entries
+  const unsigned long long* sum;
+  const unsigned long long* far;
+  uint32_t n_seeds;
+  // the outputs, pitch o_ld elements; null: not written
+  unsigned long long* o_usage;
+  double* o_far;
+  uint32_t* o_sink;
+  int64_t o_ld;
+};
+// A_0 = w (W null: 1), M_0 = T for the cells with T < +inf, 0 elsewhere
+hipError_t launch_usage_init(const double* T, int64_t ld, uint32_t nx, uint32_t ny,
+                             const uint32_t* W, int64_t w_ld, unsigned long long* sum,
+                             unsigned long long* far, hipStream_t st);
+// one round: adst <- asrc, then every open entry sends.  cnt[round] = entries still open
+// after it, cnt[kRouteRounds + round] = entries that sent in it; a round after a 0 does
+// nothing.  gather0: round 0 by reads of the eight neighbours instead of atomics.
+hipError_t launch_usage_round(const UsageRoundArgs& a, uint32_t* cnt, uint32_t round,
+                              bool gather0, hipStream_t st);
+// the masked outputs, and with catchment (n_seeds words, device-visible) the roots' sums
+hipError_t launch_usage_final(const UsageFinalArgs& a, const GoalSeed* seeds,
+                              unsigned long long* catchment, hipStream_t st);
+
 // batched solves (batch_kernels.hip): `planes` maps of nx x ny stacked at
 // a plane pitch of P rows (dymu_batch_plane_rows), rows ny .. P-1 of each being +inf walls
 // dst (pitch ld, planes * P rows) <- plane b from src + b * src_plane_stride (pitch src_ld;

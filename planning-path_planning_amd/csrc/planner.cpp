@@ -2764,6 +2764,40 @@ namespace {
 inline double route_min(double a, double b) { return (b < a || (b == a && std::signbit(b))) ? b : a; }
 inline double route_max(double a, double b) { return (b > a || (b == a && !std::signbit(b))) ? b : a; }
 inline bool route_finite(double v) { return v > -kInf && v < kInf; }
+// include/dymu_fim.h's rp(c) on a row-major nx x ny map t, for a node with t[c] < +inf: the
+// hop target of the arriving descent evaluated at c, or -1 for a dead end; *diag = whether
+// the hop is diagonal.  getRouteFields' and getRouteUsage's host routes share it.
+int64_t route_parent(const double* t, int64_t nx, int64_t ny, uint64_t c, bool* diag) {
+  const int64_t i = (int64_t)(c % (uint64_t)nx), j = (int64_t)(c / (uint64_t)nx);
+  const double tn = t[c];
+  // a neighbour off the grid is +inf: no test accepts it
+  auto at = [&](int di, int dj) {
+    const int64_t a = i + di, b = j + dj;
+    return a >= 0 && a < nx && b >= 0 && b < ny ? t[b * nx + a] : kInf;
+  };
+  double best = -1.0;
+  int bi = 0, bj = 0;
+  auto hop_try = [&](bool ok, int di, int dj) {
+    const double tm = at(di, dj);
+    if (ok && tm < tn) {
+      const double s = (di && dj) ? (tn - tm) * 0.7071067811865476 : tn - tm;
+      if (s > best) best = s, bi = di, bj = dj;
+    }
+  };
+  const bool w = at(-1, 0) < kInf, ea = at(1, 0) < kInf, s = at(0, -1) < kInf,
+             no = at(0, 1) < kInf;
+  hop_try(true, 0, -1);
+  hop_try(true, -1, 0);
+  hop_try(true, 1, 0);
+  hop_try(true, 0, 1);
+  hop_try(w && s, -1, -1);
+  hop_try(ea && s, 1, -1);
+  hop_try(w && no, -1, 1);
+  hop_try(ea && no, 1, 1);
+  if (bi == 0 && bj == 0) return -1;
+  *diag = bi != 0 && bj != 0;
+  return (j + bj) * nx + (i + bi);
+}
 void route_check_request(const DyMuPathPlanner::RouteRequest& rq) {
   if (rq.fields.size() > DYMU_PATH_FIELDS)
     throw std::invalid_argument("getRouteFields: at most DYMU_PATH_FIELDS fields");
@@ -2854,36 +2888,11 @@ void DyMuPathPlanner::routeFieldsOnHost(const RouteRequest& rq, RouteFields& out
   const int64_t nx = nx_, ny = ny_;
   for (const auto& e : order) {
     const uint64_t c = e.second;
-    const int64_t i = (int64_t)(c % nx_), j = (int64_t)(c / nx_);
-    const double tn = e.first;
-    // a neighbour off the grid is +inf: no test accepts it
-    auto at = [&](int di, int dj) {
-      const int64_t a = i + di, b = j + dj;
-      return a >= 0 && a < nx && b >= 0 && b < ny ? t[b * nx + a] : kInf;
-    };
-    double best = -1.0;
-    int bi = 0, bj = 0;
-    auto hop_try = [&](bool ok, int di, int dj) {
-      const double tm = at(di, dj);
-      if (ok && tm < tn) {
-        const double s = (di && dj) ? (tn - tm) * 0.7071067811865476 : tn - tm;
-        if (s > best) best = s, bi = di, bj = dj;
-      }
-    };
-    const bool w = at(-1, 0) < kInf, ea = at(1, 0) < kInf, s = at(0, -1) < kInf,
-               no = at(0, 1) < kInf;
-    hop_try(true, 0, -1);
-    hop_try(true, -1, 0);
-    hop_try(true, 1, 0);
-    hop_try(true, 0, 1);
-    hop_try(w && s, -1, -1);
-    hop_try(ea && s, 1, -1);
-    hop_try(w && no, -1, 1);
-    hop_try(ea && no, 1, 1);
-    if (bi == 0 && bj == 0) continue;  // a dead end
-    const uint64_t p = (uint64_t)((j + bj) * nx + (i + bi));
+    bool dg = false;
+    const int64_t rp = route_parent(t, nx, ny, c, &dg);
+    if (rp < 0) continue;  // a dead end
+    const uint64_t p = (uint64_t)rp;
     if (sink[p] == DYMU_LABEL_NONE) continue;  // drains to a dead end
-    const bool dg = bi != 0 && bj != 0;
     sink[c] = sink[p];
     axis[c] = axis[p] + (dg ? 0u : 1u);
     diag[c] = diag[p] + (dg ? 1u : 0u);
@@ -3011,6 +3020,161 @@ void DyMuPathPlanner::dropRouteBuffers() {
     for (auto& p : row) drop(p);
   drop(d_route_ws_);
   route_ws_bytes_ = 0;
+  drop(d_uweight_);
+  drop(d_uout_usage_);
+  drop(d_uout_far_);
+  drop(d_uout_sink_);
+  drop(d_usage_ws_);
+  usage_ws_bytes_ = 0;
+}
+
+// ---- getRouteUsage: how much of the map drains through every cell (extension) ----
+#pragma weak dymu_route_usage_device
+#pragma weak dymu_route_usage_workspace
+#pragma weak dymu_last_route_usage_ms
+
+DyMuPathPlanner::RouteUsage DyMuPathPlanner::getRouteUsage(const RouteUsageRequest& rq) {
+  RouteUsage out;
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  const uint64_t n = (uint64_t)nx_ * ny_;
+  if (!n || !has_goal_) {  // every cell is without a route; no goal, no catchment
+    if (rq.outputs & kUsageUsage) out.usage.assign(n, 0u);
+    if (rq.outputs & kUsageFar) out.far.assign(n, std::nan(""));
+    if (rq.outputs & kUsageSink) out.sink.assign(n, DYMU_LABEL_NONE);
+    return out;
+  }
+  if (!rq.host && (rq.outputs & kUsageAll) && ctx_ && dT_ && dev_map_current_ &&
+      n < (1ull << 31) && &dymu_route_usage_device && &dymu_route_usage_workspace &&
+      &dymu_last_route_usage_ms && &dymu_device_alloc_cached) {
+    routeUsageOnDevice(rq, dT_, seedList(), out);
+    last_paths_device_ = true;
+    return out;
+  }
+  routeUsageOnHost(rq, out);
+  return out;
+}
+
+// The definition of include/dymu_fim.h on the host mirror: the finite cells in descending
+// total cost, each added into its parent (a child is strictly higher, so it is complete by
+// then); the same order backwards hands the sinks down from the roots.
+void DyMuPathPlanner::routeUsageOnHost(const RouteUsageRequest& rq, RouteUsage& out) {
+  const uint64_t n = (uint64_t)nx_ * ny_;
+  fetchAll();
+  const double* t = total_cost_.data();
+  const std::vector<dymu_seed> seeds = seedList();
+  std::vector<uint32_t> sink(n, DYMU_LABEL_NONE);
+  std::vector<uint8_t> root(n, 0);
+  for (size_t k = seeds.size(); k-- > 0;) {  // descending: the lowest k is written last
+    const uint64_t c = idx(seeds[k].i, seeds[k].j);
+    if (std::memcmp(&t[c], &seeds[k].t0, sizeof(double)) != 0) continue;  // dominated
+    sink[c] = (uint32_t)k;
+    root[c] = 1;
+  }
+  std::vector<std::pair<double, uint64_t>> order;
+  for (uint64_t c = 0; c < n; ++c)
+    if (t[c] < kInf && !root[c]) order.emplace_back(t[c], c);
+  parallel_sort(order);
+  std::vector<uint64_t> usage(n, 0u);
+  std::vector<double> far(n, 0.0);
+  for (uint64_t c = 0; c < n; ++c)
+    if (t[c] < kInf) {
+      usage[c] = rq.weights ? rq.weights[c] : 1u;
+      far[c] = t[c];
+    }
+  // parent[k] of order[k]; n: none
+  std::vector<uint64_t> parent(order.size(), n);
+  const int64_t nx = nx_, ny = ny_;
+  for (size_t k = order.size(); k-- > 0;) {
+    const uint64_t c = order[k].second;
+    bool dg = false;
+    const int64_t p = route_parent(t, nx, ny, c, &dg);
+    if (p < 0) continue;  // a dead end
+    parent[k] = (uint64_t)p;
+    usage[p] += usage[c];
+    if (far[c] > far[p]) far[p] = far[c];
+  }
+  for (size_t k = 0; k < order.size(); ++k)
+    if (parent[k] != n) sink[order[k].second] = sink[parent[k]];
+  for (uint64_t c = 0; c < n; ++c)
+    if (sink[c] == DYMU_LABEL_NONE) {
+      usage[c] = 0u;
+      far[c] = std::nan("");
+    }
+  if (rq.outputs & kUsageCatchment) {
+    out.catchment.assign(seeds.size(), 0u);
+    for (size_t k = 0; k < seeds.size(); ++k) {
+      const uint64_t c = idx(seeds[k].i, seeds[k].j);
+      if (root[c] && sink[c] == (uint32_t)k) out.catchment[k] = usage[c];
+    }
+  }
+  if (rq.outputs & kUsageUsage) out.usage.swap(usage);
+  if (rq.outputs & kUsageFar) out.far.swap(far);
+  if (rq.outputs & kUsageSink) out.sink.swap(sink);
+}
+
+// The device route: the caller's weights up, dymu_route_usage_device into the planner's
+// output maps, the requested maps down.
+void DyMuPathPlanner::routeUsageOnDevice(const RouteUsageRequest& rq, const double* map,
+                                         const std::vector<dymu_seed>& seeds, RouteUsage& out) {
+  const uint64_t n = (uint64_t)nx_ * ny_;
+  auto check = [&](int rc, const char* what) {
+    if (rc != DYMU_OK)
+      throw std::runtime_error(std::string("dymu: getRouteUsage ") + what + " failed: " +
+                               dymu_strerror(rc) + " " + dymu_last_error(ctx_));
+  };
+  auto ensure = [&](auto*& p, size_t elem) {
+    if (p) return;
+    void* q = nullptr;
+    check(dymu_device_alloc_cached(ctx_, elem * dcells_, &q), "allocation");
+    p = static_cast<std::remove_reference_t<decltype(p)>>(q);
+  };
+  if (rq.weights) {
+    ensure(d_uweight_, sizeof(uint32_t));
+    check(dymu_memcpy_h2d(ctx_, d_uweight_, rq.weights, sizeof(uint32_t) * n), "weight upload");
+  }
+  dymu_usage_out o{};
+  o.ld = nx_;
+  if (rq.outputs & kUsageUsage) {
+    ensure(d_uout_usage_, sizeof(uint64_t));
+    o.usage = d_uout_usage_;
+  }
+  if (rq.outputs & kUsageFar) {
+    ensure(d_uout_far_, sizeof(double));
+    o.far = d_uout_far_;
+  }
+  if (rq.outputs & kUsageSink) {
+    ensure(d_uout_sink_, sizeof(uint32_t));
+    o.sink = d_uout_sink_;
+  }
+  const bool want_catch = (rq.outputs & kUsageCatchment) != 0;
+  dymu_usage_out sized = o;  // the catchment needs the sums: size the workspace with them
+  uint64_t dummy = 0;
+  if (want_catch && !sized.usage) sized.usage = &dummy;
+  const size_t need = dymu_route_usage_workspace(nx_, ny_, &sized);
+  if (!need) check(DYMU_ERR_ARG, "workspace query");
+  if (need > usage_ws_bytes_) {
+    if (d_usage_ws_) (void)dymu_device_free(ctx_, d_usage_ws_);
+    d_usage_ws_ = nullptr;
+    usage_ws_bytes_ = 0;
+    check(dymu_device_alloc_cached(ctx_, need, &d_usage_ws_), "workspace allocation");
+    usage_ws_bytes_ = need;
+  }
+  if (want_catch) out.catchment.assign(seeds.size(), 0u);
+  check(dymu_route_usage_device(ctx_, map, nx_, ny_, nx_, seeds.data(), (uint32_t)seeds.size(),
+                                rq.weights ? d_uweight_ : nullptr, nx_, &o,
+                                want_catch ? out.catchment.data() : nullptr, d_usage_ws_,
+                                usage_ws_bytes_, nullptr, &out.rounds),
+        "kernels");
+  auto down = [&](auto& v, const void* d) {
+    v.resize(n);
+    check(dymu_memcpy_d2h(ctx_, v.data(), d, sizeof(v[0]) * n), "download");
+  };
+  if (o.usage) down(out.usage, o.usage);
+  if (o.far) down(out.far, o.far);
+  if (o.sink) down(out.sink, o.sink);
+  double ms = 0.0;
+  if (dymu_last_route_usage_ms(ctx_, &ms) == DYMU_OK) last_paths_kernel_ms_ = ms;
 }
 
 // ---- goal sets (extension) ----
@@ -4166,6 +4330,23 @@ DyMuPathPlanner::RouteFields DyMuPathPlanner::getRouteFieldsTo(unsigned b,
   const BatchGoal& g = batch_goals_[b];
   routeFieldsOnDevice(rq, dT_batch_ + (uint64_t)b * dymu_batch_plane_rows(ny_) * nx_,
                       {dymu_seed{g.i, g.j, 0.0}}, out);
+  last_paths_device_ = true;
+  return out;
+}
+
+DyMuPathPlanner::RouteUsage DyMuPathPlanner::getRouteUsageTo(unsigned b,
+                                                            const RouteUsageRequest& rq) {
+  if (b >= batch_goals_.size() || !ctx_ || !dT_batch_ || !(rq.outputs & kUsageAll) ||
+      (uint64_t)nx_ * ny_ >= (1ull << 31) || !&dymu_route_usage_device ||
+      !&dymu_route_usage_workspace || !&dymu_last_route_usage_ms ||
+      !&dymu_device_alloc_cached || !refreshBatch())
+    throw std::invalid_argument("getRouteUsageTo: no such map in the batch");
+  RouteUsage out;
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  const BatchGoal& g = batch_goals_[b];
+  routeUsageOnDevice(rq, dT_batch_ + (uint64_t)b * dymu_batch_plane_rows(ny_) * nx_,
+                     {dymu_seed{g.i, g.j, 0.0}}, out);
   last_paths_device_ = true;
   return out;
 }

@@ -700,6 +700,62 @@ int dymu_planner_get_route_fields_to(dymu_planner* p, uint32_t b, const double* 
   });
 }
 
+namespace {
+// a flat usage request: the outputs are the non-NULL maps of `out` and the catchment;
+// false: rejected
+bool usage_request(const uint32_t* weights, const dymu_usage_out* out, const uint64_t* catchment,
+                   DyMuPathPlanner::RouteUsageRequest& rq) {
+  typedef DyMuPathPlanner P;
+  if (!out) return false;
+  rq.outputs = (out->usage ? P::kUsageUsage : 0u) | (out->far ? P::kUsageFar : 0u) |
+               (out->sink ? P::kUsageSink : 0u) | (catchment ? P::kUsageCatchment : 0u);
+  rq.weights = weights;
+  return rq.outputs != 0;
+}
+int usage_copy(const DyMuPathPlanner::RouteUsage& r, const dymu_usage_out* out,
+               uint64_t* catchment, uint32_t n_catchment) {
+  if (catchment && r.catchment.size() > n_catchment) return DYMU_ERR_ARG;
+  if (out->usage) std::copy(r.usage.begin(), r.usage.end(), out->usage);
+  if (out->far) std::copy(r.far.begin(), r.far.end(), out->far);
+  if (out->sink) std::copy(r.sink.begin(), r.sink.end(), out->sink);
+  if (catchment) {
+    std::fill(catchment, catchment + n_catchment, (uint64_t)0);
+    std::copy(r.catchment.begin(), r.catchment.end(), catchment);
+  }
+  return DYMU_OK;
+}
+}  // namespace
+
+int dymu_planner_get_route_usage(dymu_planner* p, const uint32_t* weights, int host,
+                                 const dymu_usage_out* out, uint64_t* catchment,
+                                 uint32_t n_catchment, uint32_t* rounds) {
+  DyMuPathPlanner::RouteUsageRequest rq;
+  if (!p || !usage_request(weights, out, catchment, rq)) return DYMU_ERR_ARG;
+  if (catchment && p->pl.hasGoal() && p->pl.goalCount() > n_catchment) return DYMU_ERR_ARG;
+  rq.host = host != 0;
+  return guarded([&] {
+    const auto r = p->pl.getRouteUsage(rq);
+    const int rc = usage_copy(r, out, catchment, n_catchment);
+    if (rc == DYMU_OK && rounds) *rounds = r.rounds;
+    return rc;
+  });
+}
+
+int dymu_planner_get_route_usage_to(dymu_planner* p, uint32_t b, const uint32_t* weights,
+                                    const dymu_usage_out* out, uint64_t* catchment,
+                                    uint32_t n_catchment, uint32_t* rounds) {
+  DyMuPathPlanner::RouteUsageRequest rq;
+  if (!p || !usage_request(weights, out, catchment, rq) || b >= p->pl.batchCount() ||
+      (catchment && n_catchment < 1))
+    return DYMU_ERR_ARG;
+  return guarded([&] {
+    const auto r = p->pl.getRouteUsageTo(b, rq);
+    const int rc = usage_copy(r, out, catchment, n_catchment);
+    if (rc == DYMU_OK && rounds) *rounds = r.rounds;
+    return rc;
+  });
+}
+
 int dymu_planner_goal_cell(dymu_planner* p, uint32_t* i, uint32_t* j) {
   if (!p || !i || !j) return DYMU_ERR_ARG;
   if (!p->pl.hasGoal()) return 0;

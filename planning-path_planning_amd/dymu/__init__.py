@@ -118,6 +118,15 @@ class DymuRouteOut(ctypes.Structure):
 ROUTE_OUTPUTS = ("sink", "axis", "diag", "length", "integral", "vmin", "vmax")
 
 
+class DymuUsageOut(ctypes.Structure):
+    """dymu_usage_out (include/dymu_fim.h): output maps, NULL = not computed."""
+    _fields_ = [("usage", ctypes.c_void_p), ("far", ctypes.c_void_p), ("sink", ctypes.c_void_p),
+                ("ld", ctypes.c_uint64)]
+
+
+USAGE_OUTPUTS = ("usage", "far", "sink", "catchment")
+
+
 class DymuCorridorInfo(ctypes.Structure):
     """dymu_corridor_info (include/dymu_planner.h)."""
     _fields_ = [("d_min", ctypes.c_double), ("min_i", ctypes.c_uint32), ("min_j", ctypes.c_uint32),
@@ -289,6 +298,14 @@ FIM_SYMBOLS = {
                                         ctypes.c_size_t, _vp, ctypes.POINTER(_u32)]),
     "dymu_last_route_fields_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "dymu_last_route_fields_stages": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_route_usage_workspace": (ctypes.c_size_t, [_u32, _u32, ctypes.POINTER(DymuUsageOut)]),
+    "dymu_route_usage_device": (_i32, [_vp, _vp, _u32, _u32, _u64, _vp, _u32, _vp, _u64,
+                                       ctypes.POINTER(DymuUsageOut), _vp, _vp, ctypes.c_size_t,
+                                       _vp, ctypes.POINTER(_u32)]),
+    "dymu_last_route_usage_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_last_route_usage_stages": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_last_route_usage_round_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double),
+                                              ctypes.POINTER(_u32)]),
     "dymu_batch_plane_rows": (_u32, [_u32]),
     "dymu_stack_speed_device": (_i32, [_vp, _vp, _u64, _u64, _u32, _u32, _u32, _vp, _u64, _vp]),
     "dymu_solve_batch_device": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _u32, _vp,
@@ -974,6 +991,54 @@ class Engine:
         _check(self._lib.dymu_last_route_fields_stages(self.ctx, ms), self.ctx)
         return tuple(ms)
 
+    # -- how much of the map drains through every cell --
+    @staticmethod
+    def usage_out(ld: int, usage: int = 0, far: int = 0, sink: int = 0) -> DymuUsageOut:
+        """A dymu_usage_out of device (or host) pointers; 0 / missing: not computed."""
+        return DymuUsageOut(usage or None, far or None, sink or None, ld)
+
+    def route_usage_workspace(self, nx: int, ny: int, out=None) -> int:
+        """dymu_route_usage_workspace: the bytes route_usage needs for the outputs of `out`
+        (a DymuUsageOut; None: every output); 0: rejected.  The catchment needs the sums:
+        size a call that wants it with a non-zero usage."""
+        return int(self._lib.dymu_route_usage_workspace(
+            nx, ny, ctypes.byref(out) if out is not None else None))
+
+    def route_usage(self, dT: int, nx: int, ny: int, ld: int, seeds, out, workspace: int,
+                    workspace_bytes: int, weight: int = 0, weight_ld: int = 0,
+                    catchment: bool = True, stream: int = 0) -> dict:
+        """dymu_route_usage_device on raw pointers: usage, far and sink of all cells of the
+        device map dT for the seeds (i, j[, t0]) and the device weight map (0: unit weights)
+        into the device maps of `out` (usage_out).  Returns {'rounds', 'catchment'}: the
+        doubling rounds run and, with catchment, one uint64 per seed (else None)."""
+        a = self._seeds(seeds)
+        cat = np.zeros(len(a), dtype=np.uint64) if catchment else None
+        rounds = _u32()
+        _check(self._lib.dymu_route_usage_device(
+            self.ctx, dT, nx, ny, ld, a.ctypes.data, len(a), weight or None, weight_ld,
+            ctypes.byref(out), cat.ctypes.data if catchment and len(a) else None,
+            workspace or None, workspace_bytes, stream or None, ctypes.byref(rounds)), self.ctx)
+        return {"rounds": rounds.value, "catchment": cat}
+
+    def last_route_usage_ms(self) -> float:
+        """Device time of the last route_usage, first kernel to last (waits for it)."""
+        ms = ctypes.c_double()
+        _check(self._lib.dymu_last_route_usage_ms(self.ctx, ctypes.byref(ms)), self.ctx)
+        return ms.value
+
+    def last_route_usage_stages(self):
+        """(init, rounds, final) device times of the last route_usage, ms."""
+        ms = (ctypes.c_double * 3)()
+        _check(self._lib.dymu_last_route_usage_stages(self.ctx, ms), self.ctx)
+        return tuple(ms)
+
+    def last_route_usage_round_ms(self):
+        """Device time of every round launched by the last route_usage, ms."""
+        ms = (ctypes.c_double * 32)()
+        n = _u32()
+        _check(self._lib.dymu_last_route_usage_round_ms(self.ctx, ms, ctypes.byref(n)), self.ctx)
+        return tuple(ms[:n.value])
+
     def alloc(self, nbytes: int) -> int:
         p = _vp()
         _check(self._lib.dymu_device_alloc(self.ctx, nbytes, ctypes.byref(p)), self.ctx)
@@ -1269,6 +1334,10 @@ PLANNER_SYMBOLS = {
     "dymu_planner_get_route_fields_to": (_i32, [_vp, _u32, _vp, _i32,
                                                 ctypes.POINTER(DymuRouteOut),
                                                 ctypes.POINTER(_u32)]),
+    "dymu_planner_get_route_usage": (_i32, [_vp, _vp, _i32, ctypes.POINTER(DymuUsageOut), _vp,
+                                            _u32, ctypes.POINTER(_u32)]),
+    "dymu_planner_get_route_usage_to": (_i32, [_vp, _u32, _vp, ctypes.POINTER(DymuUsageOut), _vp,
+                                               _u32, ctypes.POINTER(_u32)]),
     "dymu_planner_goal_cell": (_i32, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "dymu_planner_get_locomotion_mode": (_i32, [_vp, _d, _d, _d, _d, ctypes.c_char_p, _i32]),
     "dymu_planner_set_global_risk": (_i32, [_vp, _d, _d]),
@@ -1839,6 +1908,62 @@ class Planner:
             lambda fp, n, o, r: self._lib.dymu_planner_get_route_fields_to(
                 self.h, b, fp, n, ctypes.byref(o), ctypes.byref(r)),
             fields, outputs)
+
+    # -- how much of the map drains through every cell (DyMuPathPlanner::getRouteUsage) --
+    def _route_usage(self, call, weights, outputs, n_goals):
+        bad = set(outputs) - set(USAGE_OUTPUTS)
+        if bad:
+            raise ValueError(f"unknown outputs {sorted(bad)}; the outputs are {USAGE_OUTPUTS}")
+        if not outputs:
+            raise ValueError(f"no output asked for; the outputs are {USAGE_OUTPUTS}")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights)
+            if w.shape != (self.ny, self.nx):
+                raise ValueError(f"weights must be [{self.ny}, {self.nx}], got {w.shape}")
+            if w.dtype.kind not in "ui" or (w.size and (w.min() < 0 or w.max() > 0xFFFFFFFF)):
+                raise ValueError("weights must be integers in [0, 2^32)")
+            w = np.ascontiguousarray(w, dtype=np.uint32)
+        res = {}
+        o = DymuUsageOut()
+        o.ld = self.nx
+        for name, dt in (("usage", np.uint64), ("far", np.float64), ("sink", np.uint32)):
+            if name in outputs:
+                res[name] = np.empty((self.ny, self.nx), dtype=dt)
+                setattr(o, name, res[name].ctypes.data)
+        cat = None
+        if "catchment" in outputs:
+            # one spare entry keeps the pointer non-NULL without a goal
+            cat = np.zeros(n_goals + 1, dtype=np.uint64)
+            res["catchment"] = cat[:n_goals]
+        rounds = _u32()
+        _b_int(call(w.ctypes.data if w is not None else None, o,
+                    cat.ctypes.data if cat is not None else None,
+                    len(cat) if cat is not None else 0, rounds))
+        res["rounds"] = rounds.value
+        return res
+
+    def getRouteUsage(self, weights=None, outputs=USAGE_OUTPUTS, host: bool = False) -> dict:
+        """How much of the map drains through every cell (DyMuPathPlanner::getRouteUsage,
+        DESIGN.md s5.17): a dict of [ny, nx] maps -- 'usage' (uint64: the weight of all cells
+        whose route passes through the cell, itself included), 'far' (the largest total cost
+        among them, NaN without a route), 'sink' (uint32, LABEL_NONE: no route) -- plus
+        'catchment' (uint64 per goal: the usage at its root, 0 for a dominated goal) and
+        'rounds'.  weights: a [ny, nx] array of integers below 2^32, or None for 1 a cell.
+        outputs: the names wanted; only they are computed.  On the GPU while the device map
+        is current, else -- or with host=True -- on the host; the two are equal bit for bit."""
+        n_goals = int(self._lib.dymu_planner_goal_count(self.h))
+        return self._route_usage(
+            lambda w, o, c, nc, r: self._lib.dymu_planner_get_route_usage(
+                self.h, w, int(bool(host)), ctypes.byref(o), c, nc, ctypes.byref(r)),
+            weights, outputs, max(n_goals, 0))
+
+    def getRouteUsageTo(self, b: int, weights=None, outputs=USAGE_OUTPUTS) -> dict:
+        """getRouteUsage on map b of the batch, with goal b as the root (one catchment)."""
+        return self._route_usage(
+            lambda w, o, c, nc, r: self._lib.dymu_planner_get_route_usage_to(
+                self.h, b, w, ctypes.byref(o), c, nc, ctypes.byref(r)),
+            weights, outputs, 1)
 
     def goalCell(self):
         """(goalI(), goalJ()): the single goal's cell (goal 0 of a goal set), or None."""
