@@ -509,6 +509,37 @@ class DyMuPathPlanner {
   std::vector<ArriveStats> getArrivingStatsTo(unsigned b,
                                               const std::vector<base::Waypoint>& starts,
                                               unsigned max_wp = 1u << 20);
+  // getArrivingPaths thinned while the descent runs: of the waypoints
+  // walked, only those the rule of csrc/path_simplify.h keeps are stored, moved and
+  // returned -- the first, the last, the sink, and enough in between that every dropped
+  // waypoint lies within eps (map units, > 0) of the segment between the kept waypoints on
+  // either side of it (include/dymu_fim.h states the rule with
+  // dymu_arrive_simplified_device).  The bound is one-sided -- dropped waypoints to the
+  // polyline, not the polyline to anything: choose eps below the clearance relied on.
+  // max_wp bounds the walk as in getArrivingStats (status -3 beyond it).  Every returned
+  // waypoint equals its getArrivingPaths(stride 1) twin in all four components; index
+  // (optional, one vector per start) gives each one's number in that path.  status, sinks
+  // and stats are getArrivingPaths'.  The route is getPaths' (bit-identical either way);
+  // on the device the first slot capacity is a guess sized from the grid, and a path that
+  // keeps more runs once more with the capacity it reported (lastSimplifiedReruns()).
+  // Throws std::invalid_argument for eps not finite or <= 0, or max_wp == 0.
+  std::vector<std::vector<base::Waypoint>> getSimplifiedPaths(
+      const std::vector<base::Waypoint>& starts, double eps, std::vector<int>* status = nullptr,
+      unsigned max_wp = 1u << 20, std::vector<int>* sinks = nullptr,
+      std::vector<ArriveStats>* stats = nullptr,
+      std::vector<std::vector<uint32_t>>* index = nullptr);
+  // ... on map b of the batch with goal b as the sink (always on the device).  Throws
+  // std::invalid_argument for b >= batchCount().
+  std::vector<std::vector<base::Waypoint>> getSimplifiedPathsTo(
+      unsigned b, const std::vector<base::Waypoint>& starts, double eps,
+      std::vector<int>* status = nullptr, unsigned max_wp = 1u << 20,
+      std::vector<ArriveStats>* stats = nullptr,
+      std::vector<std::vector<uint32_t>>* index = nullptr);
+  // the paths of the last getSimplifiedPaths[To] that ran a second time on the device
+  // because they kept more waypoints than the first slot capacity (0 on the host route),
+  // and the bytes of records, counts, slots and indices that call downloaded
+  uint64_t lastSimplifiedReruns() const { return last_simplified_reruns_; }
+  uint64_t lastSimplifiedBytes() const { return last_simplified_bytes_; }
   // Every cell's node route to the goal at once (include/dymu_fim.h states
   // the definition with dymu_route_out): per cell the goal its route ends on, the hops
   // between axis and diagonal neighbours, the length, and per sampled field the integral
@@ -763,8 +794,18 @@ class DyMuPathPlanner {
                    const base::Waypoint& sink, std::vector<base::Waypoint>& path) const;
   // the arriving descent from grid-local (x, y) on T() (labels_ under a goal set): the
   // kept slots into *slots (null: none stored), the record into rec; returns the status
+  // eps (null: none): the walk at stride 1 through the rule of csrc/path_simplify.h --
+  // only the waypoints it keeps go to *slots, their numbers in the walk to *index
   int descendArriving(double x, double y, uint64_t max_wp, unsigned stride,
-                      std::vector<double>* slots, ArriveStats& rec) const;
+                      std::vector<double>* slots, ArriveStats& rec, const double* eps = nullptr,
+                      std::vector<uint32_t>* index = nullptr) const;
+  // the device route of getSimplifiedPaths[To]
+  void simplifiedOnDevice(const std::vector<base::Waypoint>& starts, double eps,
+                          std::vector<std::vector<base::Waypoint>>& out, std::vector<int>& st,
+                          std::vector<int>& sinks, unsigned max_wp, const PathTarget* target,
+                          std::vector<ArriveStats>& rec,
+                          std::vector<std::vector<uint32_t>>* index);
+  uint64_t last_simplified_reruns_ = 0, last_simplified_bytes_ = 0;
   void arriveStatsOnDevice(const std::vector<base::Waypoint>& starts,
                            std::vector<ArriveStats>& out, unsigned max_wp,
                            const PathTarget* target);

@@ -329,6 +329,56 @@ int dymu_arrive_paths_device(dymu_ctx* ctx, const double* dT, uint32_t nx, uint3
 /* Device time (ms, HIP events) of the last dymu_arrive_paths_device kernel; waits for it.
  * DYMU_ERR_STATE before the first one. */
 int dymu_last_arrive_ms(dymu_ctx* ctx, double* ms);
+/* ---- the simplified arriving descent (DyMuPathPlanner::getSimplifiedPaths) ----
+ * The walk of dymu_arrive_paths_device at stride 1, thinned while it runs: a dropped
+ * waypoint is never stored or moved.  The rule (csrc/path_simplify.h, one header for the
+ * kernel and the host) runs on the waypoints w_0 .. w_{n-1} walked, the sink excluded,
+ * with eps > 0 in map units and cross(a, b) = a.x*b.y - a.y*b.x.  Its state is the anchor
+ * A (a kept waypoint), the previous waypoint, a cone (l, h) with a flag `open` (no
+ * constraint yet) and far2.  w_0 is kept: A = w_0, open, far2 = 0.  For each further P:
+ *   1. v = P - A, d2 = v.x*v.x + v.y*v.y.
+ *   2. P is admissible iff d2 >= far2 and (open, or cross(l, v) >= 0 and cross(v, h) >= 0).
+ *   3. not admissible: the previous waypoint is kept and becomes A, open, far2 = 0, and P
+ *      is taken again from step 1 (the first waypoint after an anchor is admissible).
+ *   4. admissible: far2 = d2; if d2 > eps*eps, with c = sqrt(d2 - eps*eps),
+ *        tl = (v.x*c + v.y*eps, v.y*c - v.x*eps), th = (v.x*c - v.y*eps, v.y*c + v.x*eps);
+ *      open: l = tl, h = th, not open; else l = tl if cross(l, tl) > 0 and h = th if
+ *      cross(th, h) > 0.
+ *   5. when the walk ends, for whatever reason, the last waypoint walked is kept if it is
+ *      not yet; with status 1 the sink follows it, as in dymu_arrive_paths_device.
+ * Guarantee: every dropped waypoint lies within eps of the SEGMENT between the kept
+ * waypoints on either side of it -- the cone bounds its distance to the ray from A, the
+ * far2 rule (distances from A never fall inside a window) puts the foot on the segment.
+ * It is one-sided: it bounds the dropped waypoints' distance to the polyline, not the
+ * polyline's distance to the waypoints walked or to anything else; a caller who needs the
+ * polyline to clear obstacles chooses eps below the clearance they rely on.
+ * A kept waypoint's slot is the slot dymu_arrive_paths_device(stride 1) writes for it
+ * (x, y, dcx, dcy): the output is a subsequence of that call's, element for element, and
+ * d_index (optional) gives each kept waypoint's number in it (the sink's included).
+ *   max_steps  the walk limit, dymu_arrive_paths_device's max_wp at stride 1: status -3
+ *              beyond it, and the record covers the waypoints walked
+ *   max_kept   slots per path in d_out and d_index
+ *   d_out      NULL: count only; else [n_paths][max_kept][4]
+ *   d_index    NULL or [n_paths][max_kept]
+ *   d_count    [n_paths], required: the waypoints the rule keeps (the sink included),
+ *              WHETHER STORED OR NOT.  Only the first max_kept are stored; d_count[p] >
+ *              max_kept is an overflow, which changes neither the status nor the record.
+ *   d_stats    [n_paths], required: byte for byte dymu_arrive_paths_device's record with
+ *              max_wp = max_steps
+ * Argument errors are dymu_arrive_paths_device's, and eps not finite or <= 0, max_steps
+ * == 0, max_kept == 0 with d_out or d_index: DYMU_ERR_ARG.  Bit-identical to the host
+ * rule like dymu_arrive_paths_device.  Asynchronous on `stream`; one call at a time per
+ * context. */
+int dymu_arrive_simplified_device(dymu_ctx* ctx, const double* dT, uint32_t nx, uint32_t ny,
+                                  uint64_t ld, double res, uint32_t goal_i, uint32_t goal_j,
+                                  const uint32_t* d_label, const double* d_goal_xy,
+                                  uint32_t n_goals, double tau, const double* d_start_xy,
+                                  uint32_t n_paths, double eps, uint32_t max_steps,
+                                  uint32_t max_kept, double* d_out, uint32_t* d_index,
+                                  int32_t* d_count, dymu_arrive_stat* d_stats, void* stream);
+/* Device time (ms, HIP events) of the last dymu_arrive_simplified_device kernel; waits for
+ * it.  DYMU_ERR_STATE before the first one. */
+int dymu_last_arrive_simplified_ms(dymu_ctx* ctx, double* ms);
 /* Device time (ms, HIP events) of the last dymu_goal_labels_device, first kernel to last.
  * DYMU_ERR_STATE before the first one. */
 int dymu_last_labels_ms(dymu_ctx* ctx, double* ms);

@@ -159,6 +159,32 @@ int dymu_planner_get_arriving_stats(dymu_planner* p, const double* starts_xyzh, 
                                     int host, dymu_arrive_stat* out);
 int dymu_planner_get_arriving_stats_to(dymu_planner* p, uint32_t b, const double* starts_xyzh,
                                        int n, int max_wp, dymu_arrive_stat* out);
+/* getSimplifiedPaths (extension, DyMu.hpp): the arriving paths thinned
+ * while the descent runs -- every dropped waypoint lies within eps (map units) of the
+ * segment between the kept waypoints on either side of it (the rule and its one-sided
+ * guarantee are stated with dymu_arrive_simplified_device in include/dymu_fim.h).  max_wp
+ * bounds the walk as in dymu_planner_get_arriving_stats.  The two-call protocol of
+ * dymu_planner_get_arriving_paths: with starts the call computes, fills counts / status /
+ * stats (each may be NULL) and keeps the result; with starts NULL (n as before) it copies
+ * the held result out and releases it -- out_xyzh packed path after path, and index (may
+ * be NULL) packed the same way: each waypoint's number in the path
+ * dymu_planner_get_arriving_paths(stride 1) returns, of which it is the exact copy.  A
+ * first call with out_xyzh does both.  DYMU_ERR_ARG for eps not finite or <= 0 and for
+ * max_wp <= 0.  dymu_planner_last_path_sinks / _last_paths_on_device / _kernel_ms report
+ * the call. */
+int dymu_planner_get_simplified_paths(dymu_planner* p, const double* starts_xyzh, int n,
+                                      double eps, int max_wp, double* out_xyzh, uint32_t* index,
+                                      int* counts, int* status, dymu_arrive_stat* stats);
+/* ... on map b of the batch with goal b as the sink (always on the device).
+ * DYMU_ERR_ARG for b >= batch_count. */
+int dymu_planner_get_simplified_paths_to(dymu_planner* p, uint32_t b, const double* starts_xyzh,
+                                         int n, double eps, int max_wp, double* out_xyzh,
+                                         uint32_t* index, int* counts, int* status,
+                                         dymu_arrive_stat* stats);
+/* the last dymu_planner_get_simplified_paths[_to]: the paths that ran a second time on the
+ * device because they kept more waypoints than the first slot capacity (0 on the host
+ * route), and the bytes it downloaded (either may be NULL) */
+int dymu_planner_last_simplified(dymu_planner* p, uint64_t* reruns, uint64_t* bytes);
 /* getRouteFields (extension, DyMu.hpp): every cell's node route to the
  * goal at once, as include/dymu_fim.h defines it with dymu_route_out.  fields: n_fields <=
  * DYMU_PATH_FIELDS row-major ny x nx arrays, a NULL entry being the speed map the solve

@@ -22,6 +22,7 @@
 // which no test accepts.
 #include "descent_step.h"
 #include "fim_kernels.h"
+#include "path_simplify.h"
 
 namespace dymu {
 namespace {
@@ -58,13 +59,35 @@ __device__ __forceinline__ void hop_try(bool ok, double tn, double tm, bool diag
 }
 
 // GOALS: the sink is the goal labelled on the path's node, looked up when the node
-// changes; STORE: the kept waypoints go to a.out (else only the record is written)
-template <bool GOALS, bool STORE>
+// changes; STORE: the kept waypoints go to a.out (else only the record is written);
+// SIMPLIFY: the waypoints walked (stride 1, at most max_wp) pass through the rule of
+// path_simplify.h, and only those it keeps -- the first max_kept of them -- take a slot
+template <bool GOALS, bool STORE, bool SIMPLIFY>
 __global__ __launch_bounds__(64) void k_arrive_paths(ArriveArgs a) {
   const uint32_t p = blockIdx.x * 64u + threadIdx.x;
   if (p >= a.n_paths) return;
   double x = a.start_xy[2 * (uint64_t)p], y = a.start_xy[2 * (uint64_t)p + 1];
-  double* out = STORE ? a.out + (uint64_t)p * a.max_wp * 4 : nullptr;
+  double* out = STORE ? a.out + (uint64_t)p * (SIMPLIFY ? a.max_kept : a.max_wp) * 4 : nullptr;
+  // SIMPLIFY: the rule's state, the direction of the previous waypoint's slot (its
+  // position is (px, py)), the waypoints the rule kept, and where their numbers go
+  PathSimplifier sim;
+  double qdx = 0, qdy = 0;
+  uint32_t skept = 0;
+  uint32_t* index = SIMPLIFY && a.index ? a.index + (uint64_t)p * a.max_kept : nullptr;
+  // the rule keeps waypoint i of the walk, whose slot is (ex, ey, edx, edy)
+  auto keep = [&](double ex, double ey, double edx, double edy, uint32_t i) {
+    if (skept < a.max_kept) {
+      if (STORE) {
+        double* o = out + 4 * (uint64_t)skept;
+        o[0] = ex;
+        o[1] = ey;
+        o[2] = edx;
+        o[3] = edy;
+      }
+      if (index) index[skept] = i;
+    }
+    ++skept;
+  };
   const int64_t nx = a.nx, ny = a.ny, ld = a.ld;
   // every lane's loop ends after at most max_wp * stride steps
   const uint64_t limit = (uint64_t)a.max_wp * a.stride;
@@ -169,7 +192,16 @@ __global__ __launch_bounds__(64) void k_arrive_paths(ArriveArgs a) {
     if (w > 0) length = length + dist2d(px, py, x, y);
     ++count;
     if (phase == 0) {  // kept < max_wp: w < max_wp * stride
-      if (STORE) {
+      if (SIMPLIFY) {
+        if (w == 0) {
+          sim.anchor(x, y);
+          keep(x, y, pdx, pdy, 0u);
+        } else if (sim.next(px, py, x, y, a.eps, a.eps2)) {
+          keep(px, py, qdx, qdy, (uint32_t)w - 1u);
+        }
+        qdx = pdx;
+        qdy = pdy;
+      } else if (STORE) {
         double* o = out + 4 * (uint64_t)kept;
         o[0] = x;
         o[1] = y;
@@ -253,11 +285,15 @@ __global__ __launch_bounds__(64) void k_arrive_paths(ArriveArgs a) {
       fresh = true;
     }
   }
+  // the last waypoint walked is kept; it is the anchor only where it is waypoint 0
+  if (SIMPLIFY && count >= 2u) keep(px, py, qdx, qdy, count - 1u);
   if (status == 1) {
     if (kept < a.max_wp) {
       length = length + dist2d(px, py, sink_x, sink_y);
       ++count;
-      if (STORE) {
+      if (SIMPLIFY) {
+        keep(sink_x, sink_y, 0, 0, count - 1u);
+      } else if (STORE) {
         double* o = out + 4 * (uint64_t)kept;
         o[0] = sink_x;
         o[1] = sink_y;
@@ -269,7 +305,7 @@ __global__ __launch_bounds__(64) void k_arrive_paths(ArriveArgs a) {
       status = -3;
     }
   }
-  if (a.count) a.count[p] = (int32_t)kept;
+  if (a.count) a.count[p] = (int32_t)(SIMPLIFY ? skept : kept);
   ArriveRec* o = a.stats + p;
   o->status = status;
   o->sink = status == 1 ? sink_k : -1;
@@ -285,11 +321,25 @@ hipError_t launch_arrive_paths(const ArriveArgs& a, hipStream_t st) {
   if (a.n_paths == 0) return hipSuccess;
   const dim3 grid((a.n_paths + 63u) / 64u), block(64);
   if (a.label) {
-    if (a.out) hipLaunchKernelGGL((k_arrive_paths<true, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((k_arrive_paths<true, false>), grid, block, 0, st, a);
+    if (a.out) hipLaunchKernelGGL((k_arrive_paths<true, true, false>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_arrive_paths<true, false, false>), grid, block, 0, st, a);
   } else {
-    if (a.out) hipLaunchKernelGGL((k_arrive_paths<false, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((k_arrive_paths<false, false>), grid, block, 0, st, a);
+    if (a.out) hipLaunchKernelGGL((k_arrive_paths<false, true, false>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_arrive_paths<false, false, false>), grid, block, 0, st, a);
+  }
+  return hipGetLastError();
+}
+
+// the simplified form: a.stride is 1, a.max_wp bounds the walk, a.out may be null
+hipError_t launch_arrive_simplified(const ArriveArgs& a, hipStream_t st) {
+  if (a.n_paths == 0) return hipSuccess;
+  const dim3 grid((a.n_paths + 63u) / 64u), block(64);
+  if (a.label) {
+    if (a.out) hipLaunchKernelGGL((k_arrive_paths<true, true, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_arrive_paths<true, false, true>), grid, block, 0, st, a);
+  } else {
+    if (a.out) hipLaunchKernelGGL((k_arrive_paths<false, true, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_arrive_paths<false, false, true>), grid, block, 0, st, a);
   }
   return hipGetLastError();
 }

@@ -35,6 +35,8 @@ struct dymu_ctx {
   bool pstat_timed = false;
   hipEvent_t ev_arr0 = nullptr, ev_arr1 = nullptr;  // around the last k_arrive_paths
   bool arr_timed = false;
+  hipEvent_t ev_simp0 = nullptr, ev_simp1 = nullptr;  // around the last simplified k_arrive_paths
+  bool simp_timed = false;
   uint32_t* d_pq = nullptr;  // k_path_stats' work queue: the next path index
   hipEvent_t ev_lab0 = nullptr, ev_lab1 = nullptr;  // around the last dymu_goal_labels_device
   bool lab_timed = false;
@@ -1740,6 +1742,8 @@ int dymu_destroy(dymu_ctx* c) {
   if (c->ev_pstat1) (void)hipEventDestroy(c->ev_pstat1);
   if (c->ev_arr0) (void)hipEventDestroy(c->ev_arr0);
   if (c->ev_arr1) (void)hipEventDestroy(c->ev_arr1);
+  if (c->ev_simp0) (void)hipEventDestroy(c->ev_simp0);
+  if (c->ev_simp1) (void)hipEventDestroy(c->ev_simp1);
   if (c->d_pq) (void)hipFree(c->d_pq);
   if (c->ev_lab0) (void)hipEventDestroy(c->ev_lab0);
   if (c->ev_lab1) (void)hipEventDestroy(c->ev_lab1);
@@ -2106,6 +2110,42 @@ int dymu_arrive_paths_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_
 
 int dymu_last_arrive_ms(dymu_ctx* c, double* ms) {
   return elapsed_ms(c, &dymu_ctx::arr_timed, &dymu_ctx::ev_arr0, &dymu_ctx::ev_arr1, ms);
+}
+
+// ---- the simplified arriving descent (path_simplify.h) ----
+int dymu_arrive_simplified_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny,
+                                  uint64_t ld, double res, uint32_t gi, uint32_t gj,
+                                  const uint32_t* d_label, const double* d_goal_xy,
+                                  uint32_t n_goals, double tau, const double* d_start_xy,
+                                  uint32_t n_paths, double eps, uint32_t max_steps,
+                                  uint32_t max_kept, double* d_out, uint32_t* d_index,
+                                  int32_t* d_count, dymu_arrive_stat* d_stats, void* stream) {
+  ArriveArgs a{};
+  const int rc = descent_args(c, dT, nx, ny, ld, res, gi, gj, d_label, d_goal_xy, n_goals, tau,
+                              d_start_xy, n_paths, max_steps, a);
+  if (rc) return rc;
+  if (!(eps > 0) || !(eps < HUGE_VAL)) return DYMU_ERR_ARG;
+  if (max_kept == 0 && (d_out || d_index)) return DYMU_ERR_ARG;
+  if (n_paths && (!d_stats || !d_count)) return DYMU_ERR_ARG;
+  if (n_paths == 0) return DYMU_OK;
+  a.goal_i = gi;
+  a.goal_j = gj;
+  a.stride = 1;
+  a.out = d_out;
+  a.count = d_count;
+  a.stats = reinterpret_cast<ArriveRec*>(d_stats);
+  a.eps = eps;
+  a.eps2 = eps * eps;
+  a.max_kept = max_kept;
+  a.index = d_index;
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = pick_stream(c, stream);
+  return timed_launch(c, st, &dymu_ctx::simp_timed, &dymu_ctx::ev_simp0, &dymu_ctx::ev_simp1,
+                      [&] { return launch_arrive_simplified(a, st); });
+}
+
+int dymu_last_arrive_simplified_ms(dymu_ctx* c, double* ms) {
+  return elapsed_ms(c, &dymu_ctx::simp_timed, &dymu_ctx::ev_simp0, &dymu_ctx::ev_simp1, ms);
 }
 
 // ---- every cell's node route (route_kernels.hip) ----

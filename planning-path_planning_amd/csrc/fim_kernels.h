@@ -440,8 +440,15 @@ struct ArriveArgs : DescentArgs {  // the label is looked up at the node; two_re
   double* out;       // null: no waypoint is stored; else PathArgs' slots
   int32_t* count;    // slots kept per path (may be null with out)
   ArriveRec* stats;  // n_paths records
+  // ---- the simplified form only (path_simplify.h) ----
+  double eps, eps2;    // the bound and eps * eps
+  uint32_t max_kept;   // slots per path in out and index; count = waypoints kept, stored or not
+  uint32_t* index;     // null, or per kept waypoint its number in the walk
 };
 hipError_t launch_arrive_paths(const ArriveArgs& a, hipStream_t st);
+// the same walk at stride 1 with only the waypoints the rule keeps stored: max_wp bounds
+// the walk, max_kept the slots
+hipError_t launch_arrive_simplified(const ArriveArgs& a, hipStream_t st);
 
 // goal sets (goal_kernels.hip)
 struct GoalSeed {  // dymu_seed's layout

@@ -26,6 +26,7 @@
 
 #include "DyMu.hpp"
 #include "local_layer.hpp"
+#include "path_simplify.h"
 #include "pop_order.hpp"
 
 namespace PathPlanning_lib {
@@ -2257,6 +2258,40 @@ struct DyMuPathPlanner::DeviceQuery {
   }
 };
 
+namespace {
+// The download of per-path rows of a device array with one fixed pitch (pathsOnDevice,
+// simplifiedOnDevice): runs of consecutive paths, each downloaded by one pitched copy as
+// wide as its longest row -- a run grows while that moves at most twice its elements (plus
+// 1024), so few commands move little more than the counts.  len[q] = the elements of row
+// q; off[q] = where it lands in the host buffer; returns that buffer's elements.
+struct RowRun {
+  uint32_t q0, n;
+  uint64_t width, base;
+};
+uint64_t planRowRuns(const std::vector<uint64_t>& len, std::vector<uint64_t>& off,
+                     std::vector<RowRun>& runs) {
+  const uint32_t m = (uint32_t)len.size();
+  off.assign(m, 0);
+  runs.clear();
+  uint64_t total = 0;
+  for (uint32_t q0 = 0; q0 < m;) {
+    uint64_t width = len[q0], sum = len[q0];
+    uint32_t q1 = q0 + 1;
+    for (; q1 < m; ++q1) {
+      const uint64_t w2 = std::max(width, len[q1]), s2 = sum + len[q1];
+      if (w2 * (q1 + 1 - q0) > 2 * s2 + 1024) break;
+      width = w2;
+      sum = s2;
+    }
+    for (uint32_t q = q0; q < q1; ++q) off[q] = total + (uint64_t)(q - q0) * width;
+    runs.push_back({q0, q1 - q0, width, total});
+    total += width * (q1 - q0);
+    q0 = q1;
+  }
+  return total;
+}
+}  // namespace
+
 // getPaths' host post-pass: z from the elevation with the host's interpolate call and its
 // argument order (nextWaypoint), heading = atan2(-dcy, -dcx) with the host libm
 void DyMuPathPlanner::slotsToPath(const double* r, uint64_t c, int status,
@@ -2329,11 +2364,7 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
   std::vector<int32_t> cnt, sts;
   std::vector<ArriveStats> recs;  // arrive: the batch's records (status and sink are theirs)
   std::vector<uint64_t> off, len;  // per path: its row in `raw` (waypoints), its count
-  struct Run {
-    uint32_t q0, n;
-    uint64_t width, base;
-  };
-  std::vector<Run> runs;
+  std::vector<RowRun> runs;
   while (!pending.empty()) {
     const uint64_t per_batch = std::max<uint64_t>(1, kOutBytes / (32 * cap));
     again.clear();
@@ -2388,24 +2419,9 @@ void DyMuPathPlanner::pathsOnDevice(const std::vector<base::Waypoint>& starts,
         len[q] = rerun ? 0 : (uint64_t)std::max(cnt[q], 0);
         if (rerun) again.push_back(ids[q]);
       }
-      runs.clear();
-      uint64_t total = 0;
-      for (uint32_t q0 = 0; q0 < m;) {
-        uint64_t width = len[q0], sum = len[q0];
-        uint32_t q1 = q0 + 1;
-        for (; q1 < m; ++q1) {
-          const uint64_t w2 = std::max(width, len[q1]), s2 = sum + len[q1];
-          if (w2 * (q1 + 1 - q0) > 2 * s2 + 1024) break;
-          width = w2;
-          sum = s2;
-        }
-        for (uint32_t q = q0; q < q1; ++q) off[q] = total + (uint64_t)(q - q0) * width;
-        runs.push_back({q0, q1 - q0, width, total});
-        total += width * (q1 - q0);
-        q0 = q1;
-      }
+      const uint64_t total = planRowRuns(len, off, runs);
       raw.resize(4 * total);
-      for (const Run& r : runs)
+      for (const RowRun& r : runs)
         if (r.width)
           check(dymu_memcpy2d_d2h(ctx_, &raw[4 * r.base], 32 * r.width, d_out + 4 * cap * r.q0,
                                   32 * cap, 32 * r.width, r.n),
@@ -2451,9 +2467,19 @@ constexpr DyMuPathPlanner::ArriveStats kNoArrival{-1, -1, 0u, 0u, 0.0, 0.0};
 // (arrive_kernels.hip) follows statement for statement: every expression here is formed
 // there in the same order.
 int DyMuPathPlanner::descendArriving(double x, double y, uint64_t max_wp, unsigned stride,
-                                     std::vector<double>* slots, ArriveStats& rec) const {
+                                     std::vector<double>* slots, ArriveStats& rec,
+                                     const double* eps, std::vector<uint32_t>* index) const {
   rec = kNoArrival;
   if (slots) slots->clear();
+  if (index) index->clear();
+  // eps: the rule of path_simplify.h as k_arrive_paths' simplified form applies it
+  dymu::PathSimplifier sim;
+  const double eps1 = eps ? *eps : 0.0, eps2 = eps1 * eps1;
+  double qdx = 0, qdy = 0;  // the direction of the previous waypoint's slot
+  auto keep = [&](double ex, double ey, double edx, double edy, uint32_t i) {
+    if (slots) slots->insert(slots->end(), {ex, ey, edx, edy});
+    if (index) index->push_back(i);
+  };
   if (!has_goal_) return -1;
   const double res = global_res_, tau = std::min(0.4, risk_distance_);
   const double res_tau = res * tau, stall = 0.01 * tau * res;
@@ -2500,7 +2526,18 @@ int DyMuPathPlanner::descendArriving(double x, double y, uint64_t max_wp, unsign
     if (w > 0) rec.length = rec.length + dist(px, py, x, y);
     ++rec.count;
     if (phase == 0) {
-      if (slots) slots->insert(slots->end(), {x, y, pdx, pdy});
+      if (eps) {
+        if (w == 0) {
+          sim.anchor(x, y);
+          keep(x, y, pdx, pdy, 0u);
+        } else if (sim.next(px, py, x, y, eps1, eps2)) {
+          keep(px, py, qdx, qdy, (uint32_t)w - 1u);
+        }
+        qdx = pdx;
+        qdy = pdy;
+      } else if (slots) {
+        slots->insert(slots->end(), {x, y, pdx, pdy});
+      }
       ++kept;
     }
     if (++phase == stride) phase = 0;
@@ -2593,11 +2630,14 @@ int DyMuPathPlanner::descendArriving(double x, double y, uint64_t max_wp, unsign
     ++rec.hops;
     track();
   }
+  // the last waypoint walked is kept; it is the anchor only where it is waypoint 0
+  if (eps && rec.count >= 2u) keep(px, py, qdx, qdy, rec.count - 1u);
   if (status == 1) {
     if (kept < max_wp) {
       rec.length = rec.length + dist(px, py, sink_x, sink_y);
       ++rec.count;
-      if (slots) slots->insert(slots->end(), {sink_x, sink_y, 0.0, 0.0});
+      if (eps) keep(sink_x, sink_y, 0.0, 0.0, rec.count - 1u);
+      else if (slots) slots->insert(slots->end(), {sink_x, sink_y, 0.0, 0.0});
     } else {
       status = -3;
     }
@@ -2683,6 +2723,170 @@ void DyMuPathPlanner::arriveStatsOnDevice(const std::vector<base::Waypoint>& sta
            "kernel");
   dq.check(dymu_memcpy_d2h(ctx_, out.data(), d_rec, sizeof(ArriveStats) * n), "download");
   dq.addKernelMs(&dymu_last_arrive_ms);
+}
+
+// ---- getSimplifiedPaths: arriving paths thinned within a bound (extension) ----
+// null with an engine that predates the entry (tests/hostengine): the host route runs
+#pragma weak dymu_arrive_simplified_device
+#pragma weak dymu_last_arrive_simplified_ms
+
+namespace {
+void simplified_check(const char* who, double eps, unsigned max_wp) {
+  if (!(eps > 0) || !(eps < std::numeric_limits<double>::infinity()) || max_wp == 0)
+    throw std::invalid_argument(std::string(who) + ": eps > 0 and finite, max_wp >= 1");
+}
+}  // namespace
+
+std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getSimplifiedPaths(
+    const std::vector<base::Waypoint>& starts, double eps, std::vector<int>* status,
+    unsigned max_wp, std::vector<int>* sinks, std::vector<ArriveStats>* stats,
+    std::vector<std::vector<uint32_t>>* index) {
+  simplified_check("getSimplifiedPaths", eps, max_wp);
+  const size_t n = starts.size();
+  std::vector<std::vector<base::Waypoint>> out(n);
+  std::vector<int> st(n, -1), sk(n, -1);
+  std::vector<ArriveStats> rec(n, kNoArrival);
+  if (index) index->assign(n, std::vector<uint32_t>());
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  last_simplified_reruns_ = last_simplified_bytes_ = 0;
+  if (n && has_goal_) {
+    if (descentOnDevice() && n <= 0xffffffffull && max_wp <= 0x7fffffffu &&
+        &dymu_arrive_simplified_device && &dymu_last_arrive_simplified_ms) {
+      simplifiedOnDevice(starts, eps, out, st, sk, max_wp, nullptr, rec, index);
+      last_paths_device_ = true;
+    } else {
+      if (!goals_.empty()) ensureHostLabels();
+      for_each_start(n, [&](size_t q) {
+        std::vector<double> slots;
+        st[q] = descendArriving(starts[q].position[0] - global_offset_[0],
+                                starts[q].position[1] - global_offset_[1], max_wp, 1, &slots,
+                                rec[q], &eps, index ? &(*index)[q] : nullptr);
+        sk[q] = rec[q].sink;
+        base::Waypoint end = !goals_.empty() && sk[q] >= 0
+                                 ? sinkWaypoint((size_t)sk[q])
+                                 : nodeSink(goal_i_, goal_j_, goal_heading_);
+        end.position[0] += global_offset_[0];
+        end.position[1] += global_offset_[1];
+        slotsToPath(slots.data(), slots.size() / 4, st[q], starts[q], end, out[q]);
+      });
+    }
+  }
+  if (status) status->swap(st);
+  if (sinks) sinks->swap(sk);
+  if (stats) stats->swap(rec);
+  return out;
+}
+
+// The device route: the starts up, one simplified k_arrive_paths launch per batch, the
+// records and the counts down, then only the slots (and numbers) the rule kept, by
+// pathsOnDevice's pitched copies; z and the heading on the host threads.  The kernel
+// counts every waypoint the rule keeps and stores the first `cap` of them.  The first cap
+// is a guess from the grid and eps (below), and a path that kept more runs once more, with
+// the largest count reported as the capacity: the rule is deterministic, so the second run
+// fits exactly.
+void DyMuPathPlanner::simplifiedOnDevice(const std::vector<base::Waypoint>& starts, double eps,
+                                         std::vector<std::vector<base::Waypoint>>& out,
+                                         std::vector<int>& st, std::vector<int>& sinks,
+                                         unsigned max_wp, const PathTarget* target,
+                                         std::vector<ArriveStats>& rec,
+                                         std::vector<std::vector<uint32_t>>* index) {
+  constexpr uint64_t kOutBytes = 4ull << 30;  // device output of one batch, at most
+  const size_t n = starts.size();
+  DeviceQuery dq(*this, "getSimplifiedPaths", target);
+  DeviceScratch& dev = dq.dev;
+  auto check = [&](int rc, const char* what) { dq.check(rc, what); };
+  auto shifted = [&](base::Waypoint w) {
+    w.position[0] += global_offset_[0];
+    w.position[1] += global_offset_[1];
+    return w;
+  };
+  const base::Waypoint sink =
+      shifted(nodeSink(dq.gi, dq.gj, target ? target->heading : goal_heading_));
+  std::vector<base::Waypoint> gsinks;
+  if (dq.gs)
+    for (size_t k = 0; k < goals_.size(); ++k) gsinks.push_back(shifted(sinkWaypoint(k)));
+  // The first capacity, a guess: a long path walks about nx + ny waypoints (a diagonal
+  // from a corner to the middle at 0.4 cell a step) and the rule keeps about one in
+  // 16 sqrt(eps in cells) of them on the maps measured, eps taken between
+  // 1/64 and 64 cells; 64 slots at the least.  A path keeps at most max_wp waypoints: the
+  // sink follows fewer than max_wp walked.
+  const double eps_cells = std::min(64.0, std::max(1.0 / 64.0, eps / global_res_));
+  uint64_t cap = (uint64_t)((double)((uint64_t)nx_ + ny_) / (16.0 * std::sqrt(eps_cells)));
+  cap = std::min<uint64_t>(std::max<uint64_t>(64, cap), max_wp);
+  const uint64_t slot_bytes = 32 + (index ? 4 : 0);
+  std::vector<uint32_t> pending(n), again, idx;
+  for (size_t q = 0; q < n; ++q) pending[q] = (uint32_t)q;
+  std::vector<double> raw;
+  std::vector<int32_t> cnt;
+  std::vector<ArriveStats> recs;
+  std::vector<uint64_t> off, len;
+  std::vector<RowRun> runs;
+  for (int round = 0; !pending.empty(); ++round) {
+    const uint64_t per_batch = std::max<uint64_t>(1, kOutBytes / (slot_bytes * cap));
+    again.clear();
+    uint64_t next_cap = 0;
+    for (size_t b0 = 0; b0 < pending.size(); b0 += per_batch) {
+      const uint32_t m = (uint32_t)std::min<uint64_t>(per_batch, pending.size() - b0);
+      const uint32_t* ids = &pending[b0];
+      double* d_xy = dq.uploadStarts(starts, ids, m);
+      int32_t* d_cnt = dev.alloc<int32_t>(m);
+      ArriveStats* d_rec = dev.alloc<ArriveStats>(m);
+      double* d_out = dev.alloc<double>(4 * cap * m);
+      uint32_t* d_idx = index ? dev.alloc<uint32_t>(cap * m) : nullptr;
+      check(dymu_arrive_simplified_device(ctx_, dq.map, nx_, ny_, nx_, global_res_, dq.gi, dq.gj,
+                                          dq.labels(), dq.d_gxy, dq.goals(), dq.tau, d_xy, m, eps,
+                                          max_wp, (uint32_t)cap, d_out, d_idx, d_cnt, d_rec,
+                                          nullptr),
+            "kernel");
+      cnt.resize(m);
+      recs.resize(m);
+      check(dymu_memcpy_d2h(ctx_, cnt.data(), d_cnt, sizeof(int32_t) * m), "download");
+      check(dymu_memcpy_d2h(ctx_, recs.data(), d_rec, sizeof(ArriveStats) * m), "download");
+      last_simplified_bytes_ += (sizeof(int32_t) + sizeof(ArriveStats)) * (uint64_t)m;
+      dq.addKernelMs(&dymu_last_arrive_simplified_ms);
+      len.assign(m, 0);
+      for (uint32_t q = 0; q < m; ++q) {
+        const uint64_t c = (uint64_t)std::max(cnt[q], 0);
+        if (c > cap) {
+          if (round > 0) throw std::runtime_error("dymu: getSimplifiedPaths: a rerun overflowed");
+          again.push_back(ids[q]);
+          next_cap = std::max(next_cap, c);
+        } else {
+          len[q] = c;
+        }
+      }
+      const uint64_t total = planRowRuns(len, off, runs);
+      raw.resize(4 * total);
+      if (index) idx.resize(total);
+      for (const RowRun& r : runs) {
+        if (!r.width) continue;
+        check(dymu_memcpy2d_d2h(ctx_, &raw[4 * r.base], 32 * r.width, d_out + 4 * cap * r.q0,
+                                32 * cap, 32 * r.width, r.n),
+              "download");
+        if (index)
+          check(dymu_memcpy2d_d2h(ctx_, &idx[r.base], 4 * r.width, d_idx + cap * r.q0, 4 * cap,
+                                  4 * r.width, r.n),
+                "download");
+        last_simplified_bytes_ += slot_bytes * r.width * r.n;
+      }
+      for (void* p : {(void*)d_xy, (void*)d_cnt, (void*)d_rec, (void*)d_out}) dev.release(p);
+      if (d_idx) dev.release(d_idx);
+      for_each_start(m, [&](size_t q) {
+        if ((uint64_t)std::max(cnt[q], 0) > cap) return;
+        const uint32_t id = ids[q];
+        st[id] = recs[q].status;
+        sinks[id] = recs[q].sink;
+        rec[id] = recs[q];
+        slotsToPath(raw.data() + 4 * off[q], len[q], st[id], starts[id],
+                    dq.gs ? gsinks[(size_t)std::max(sinks[id], 0)] : sink, out[id]);
+        if (index) (*index)[id].assign(idx.begin() + off[q], idx.begin() + off[q] + len[q]);
+      });
+    }
+    last_simplified_reruns_ += again.size();
+    pending.swap(again);
+    cap = next_cap;
+  }
 }
 
 // ---- getPathStats: per-path summaries (extension) ----
@@ -4289,6 +4493,34 @@ std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getArrivingPathsTo(
     const PathTarget tgt{dT_batch_ + (uint64_t)b * dymu_batch_plane_rows(ny_) * nx_, g.i, g.j,
                          g.heading};
     pathsOnDevice(starts, out, st, sk, max_wp, stride, &tgt, &rec);
+    last_paths_device_ = true;
+  }
+  if (status) status->swap(st);
+  if (stats) stats->swap(rec);
+  return out;
+}
+
+std::vector<std::vector<base::Waypoint>> DyMuPathPlanner::getSimplifiedPathsTo(
+    unsigned b, const std::vector<base::Waypoint>& starts, double eps, std::vector<int>* status,
+    unsigned max_wp, std::vector<ArriveStats>* stats, std::vector<std::vector<uint32_t>>* index) {
+  simplified_check("getSimplifiedPathsTo", eps, max_wp);
+  if (b >= batch_goals_.size() || !ctx_ || !dT_batch_ || starts.size() > 0xffffffffull ||
+      max_wp > 0x7fffffffu || !&dymu_arrive_simplified_device ||
+      !&dymu_last_arrive_simplified_ms || !refreshBatch())
+    throw std::invalid_argument("getSimplifiedPathsTo: no such map in the batch");
+  const size_t n = starts.size();
+  std::vector<std::vector<base::Waypoint>> out(n);
+  std::vector<int> st(n, -1), sk(n, -1);
+  std::vector<ArriveStats> rec(n, kNoArrival);
+  if (index) index->assign(n, std::vector<uint32_t>());
+  last_paths_device_ = false;
+  last_paths_kernel_ms_ = 0.0;
+  last_simplified_reruns_ = last_simplified_bytes_ = 0;
+  if (n) {
+    const BatchGoal& g = batch_goals_[b];
+    const PathTarget tgt{dT_batch_ + (uint64_t)b * dymu_batch_plane_rows(ny_) * nx_, g.i, g.j,
+                         g.heading};
+    simplifiedOnDevice(starts, eps, out, st, sk, max_wp, &tgt, rec, index);
     last_paths_device_ = true;
   }
   if (status) status->swap(st);

@@ -2,6 +2,7 @@
 // over PathPlanning_lib::DyMuPathPlanner.  Exceptions never cross the ABI:
 // an engine failure becomes DYMU_ERR_NO_DEVICE / DYMU_ERR_HIP.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <exception>
 #include <functional>
@@ -24,6 +25,8 @@ struct dymu_planner {
   std::vector<std::vector<base::Waypoint>> paths;
   std::vector<int> paths_status;
   std::vector<int> paths_sinks;  // the goal each of those paths ended on (-1: none)
+  // dymu_planner_get_simplified_paths: each kept waypoint's number in the unsimplified path
+  std::vector<std::vector<uint32_t>> paths_index;
   dymu_planner(double a, double b, double c, PathPlanning_lib::repairingAproach r)
       : pl(a, b, c, r) {}
 };
@@ -619,6 +622,70 @@ int dymu_planner_get_arriving_paths_to(dymu_planner* p, uint32_t b, const double
       if (p->paths_status[q] != 1) p->paths_sinks[q] = -1;
     if (stats) std::copy(rec.begin(), rec.end(), stats);
   });
+}
+
+namespace {
+// dymu_planner_get_simplified_paths[_to]: `run` leaves the result in the handle (first
+// call), or the held result is copied out -- the indices packed like the waypoints
+int simplified_paths(dymu_planner* p, bool first, int n, double* out, uint32_t* index,
+                     int* counts, int* status, const std::function<void()>& run) {
+  if (first) {
+    const int rc = guarded([&] {
+      run();
+      return DYMU_OK;
+    });
+    if (rc != DYMU_OK) return rc;
+    for (int q = 0; q < n; ++q) {
+      if (counts) counts[q] = (int)p->paths[q].size();
+      if (status) status[q] = p->paths_status[q];
+    }
+    if (!out) return n;
+  }
+  if (!out || (size_t)n != p->paths.size() || p->paths_index.size() != p->paths.size())
+    return DYMU_ERR_ARG;
+  if (index)
+    for (const auto& v : p->paths_index) index = std::copy(v.begin(), v.end(), index);
+  p->paths_index.clear();
+  p->paths_index.shrink_to_fit();
+  return dymu_planner_get_paths(p, nullptr, n, 0, 0, out, nullptr, nullptr);
+}
+}  // namespace
+
+int dymu_planner_get_simplified_paths(dymu_planner* p, const double* starts, int n, double eps,
+                                      int max_wp, double* out, uint32_t* index, int* counts,
+                                      int* status, dymu_arrive_stat* stats) {
+  if (!p || n < 0) return DYMU_ERR_ARG;
+  if (starts && (max_wp <= 0 || !(eps > 0) || !(eps < HUGE_VAL))) return DYMU_ERR_ARG;
+  return simplified_paths(p, starts != nullptr, n, out, index, counts, status, [&] {
+    std::vector<DyMuPathPlanner::ArriveStats> rec;
+    p->paths = p->pl.getSimplifiedPaths(wps(starts, n, 4), eps, &p->paths_status,
+                                        (unsigned)max_wp, &p->paths_sinks, &rec, &p->paths_index);
+    if (stats) std::copy(rec.begin(), rec.end(), stats);
+  });
+}
+
+int dymu_planner_get_simplified_paths_to(dymu_planner* p, uint32_t b, const double* starts, int n,
+                                         double eps, int max_wp, double* out, uint32_t* index,
+                                         int* counts, int* status, dymu_arrive_stat* stats) {
+  if (!p || n < 0) return DYMU_ERR_ARG;
+  if (starts && (max_wp <= 0 || !(eps > 0) || !(eps < HUGE_VAL) || b >= p->pl.batchCount()))
+    return DYMU_ERR_ARG;
+  return simplified_paths(p, starts != nullptr, n, out, index, counts, status, [&] {
+    std::vector<DyMuPathPlanner::ArriveStats> rec;
+    p->paths = p->pl.getSimplifiedPathsTo(b, wps(starts, n, 4), eps, &p->paths_status,
+                                          (unsigned)max_wp, &rec, &p->paths_index);
+    p->paths_sinks.assign((size_t)n, 0);
+    for (int q = 0; q < n; ++q)
+      if (p->paths_status[q] != 1) p->paths_sinks[q] = -1;
+    if (stats) std::copy(rec.begin(), rec.end(), stats);
+  });
+}
+
+int dymu_planner_last_simplified(dymu_planner* p, uint64_t* reruns, uint64_t* bytes) {
+  if (!p) return DYMU_ERR_ARG;
+  if (reruns) *reruns = p->pl.lastSimplifiedReruns();
+  if (bytes) *bytes = p->pl.lastSimplifiedBytes();
+  return DYMU_OK;
 }
 
 int dymu_planner_get_arriving_stats(dymu_planner* p, const double* starts, int n, int max_wp,

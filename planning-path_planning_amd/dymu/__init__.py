@@ -291,6 +291,11 @@ FIM_SYMBOLS = {
                                         _vp, _vp, _u32, ctypes.c_double, _vp, _u32, _u32, _u32,
                                         _vp, _vp, _vp, _vp]),
     "dymu_last_arrive_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "dymu_arrive_simplified_device": (_i32, [_vp, _vp, _u32, _u32, _u64, ctypes.c_double, _u32,
+                                             _u32, _vp, _vp, _u32, ctypes.c_double, _vp, _u32,
+                                             ctypes.c_double, _u32, _u32, _vp, _vp, _vp, _vp,
+                                             _vp]),
+    "dymu_last_arrive_simplified_ms": (_i32, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "dymu_route_fields_workspace": (ctypes.c_size_t, [_u32, _u32, _u32,
                                                       ctypes.POINTER(DymuRouteOut)]),
     "dymu_route_fields_device": (_i32, [_vp, _vp, _u32, _u32, _u64, ctypes.c_double, _vp, _u32,
@@ -750,6 +755,65 @@ class Engine:
         """Device time of the last arrive_paths kernel (waits for it)."""
         ms = ctypes.c_double()
         _check(self._lib.dymu_last_arrive_ms(self.ctx, ctypes.byref(ms)), self.ctx)
+        return ms.value
+
+    # -- the simplified arriving descent (DESIGN.md s5.18) --
+    def arrive_simplified(self, dT: int, nx: int, ny: int, ld: int, res: float, goal_i: int,
+                          goal_j: int, tau: float, starts_xy, eps: float, max_steps: int,
+                          max_kept: int, store: bool = True, with_index: bool = True,
+                          d_label: int = 0, goals_ij=None, stream: int = 0):
+        """dymu_arrive_simplified_device on the device map dT for host starts (n, 2) in
+        grid-local metres: (out [n, max_kept, 4] of x, y, dcx, dcy; index [n, max_kept]
+        uint32; counts [n]; records).  counts[q] is what the rule keeps, stored or not:
+        only the first max_kept have a slot, the rest of out and index is zero.
+        store=False passes d_out = NULL, with_index=False d_index = NULL (None returned)."""
+        xy = np.ascontiguousarray(starts_xy, dtype=np.float64).reshape(-1, 2)
+        n = len(xy)
+        rec = np.zeros(n, dtype=ARRIVE_STAT_DTYPE)
+        out = np.zeros((n, max_kept, 4)) if store else None
+        idx = np.zeros((n, max_kept), dtype=np.uint32) if with_index else None
+        cnt = np.zeros(n, dtype=np.int32)
+        gxy = None
+        if d_label:
+            gxy = res * np.ascontiguousarray(goals_ij, dtype=np.float64).reshape(-1, 2)
+        ptrs = [self.alloc(max(xy.nbytes, 8)), self.alloc(max(rec.nbytes, 8)),
+                self.alloc(max(out.nbytes, 8)) if store else 0,
+                self.alloc(max(idx.nbytes, 8)) if with_index else 0,
+                self.alloc(4 * max(n, 1)),
+                self.alloc(max(gxy.nbytes, 8)) if gxy is not None else 0]
+        try:
+            if n:
+                self.h2d(ptrs[0], xy)
+            if gxy is not None and len(gxy):
+                self.h2d(ptrs[5], gxy)
+            _check(self._lib.dymu_arrive_simplified_device(
+                self.ctx, dT, nx, ny, ld, res, goal_i, goal_j, d_label or None, ptrs[5] or None,
+                len(gxy) if gxy is not None else 0, tau, ptrs[0], n, eps, max_steps, max_kept,
+                ptrs[2] or None, ptrs[3] or None, ptrs[4], ptrs[1], stream or None), self.ctx)
+            if n:
+                if stream:  # d2h is ordered on the context stream only
+                    self.last_arrive_simplified_ms()
+                self.d2h(rec, ptrs[1])
+                self.d2h(cnt, ptrs[4])
+                if store and out.size:
+                    self.d2h(out, ptrs[2])
+                if with_index and idx.size:
+                    self.d2h(idx, ptrs[3])
+        finally:
+            for p in ptrs:
+                if p:
+                    self.free(p)
+        for q in range(n):  # slots past the count were never written
+            if store:
+                out[q, max(cnt[q], 0):] = 0.0
+            if with_index:
+                idx[q, max(cnt[q], 0):] = 0
+        return out, idx, cnt, rec
+
+    def last_arrive_simplified_ms(self) -> float:
+        """Device time of the last arrive_simplified kernel (waits for it)."""
+        ms = ctypes.c_double()
+        _check(self._lib.dymu_last_arrive_simplified_ms(self.ctx, ctypes.byref(ms)), self.ctx)
         return ms.value
 
     # -- batched solves (DESIGN.md s5.7) --
@@ -1327,6 +1391,11 @@ PLANNER_SYMBOLS = {
     "dymu_planner_get_arriving_paths": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "dymu_planner_get_arriving_paths_to": (_i32, [_vp, _u32, _vp, _i32, _i32, _i32, _vp, _vp, _vp,
                                                   _vp]),
+    "dymu_planner_get_simplified_paths": (_i32, [_vp, _vp, _i32, ctypes.c_double, _i32, _vp, _vp,
+                                                 _vp, _vp, _vp]),
+    "dymu_planner_get_simplified_paths_to": (_i32, [_vp, _u32, _vp, _i32, ctypes.c_double, _i32,
+                                                    _vp, _vp, _vp, _vp, _vp]),
+    "dymu_planner_last_simplified": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "dymu_planner_get_arriving_stats": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "dymu_planner_get_arriving_stats_to": (_i32, [_vp, _u32, _vp, _i32, _i32, _vp]),
     "dymu_planner_get_route_fields": (_i32, [_vp, _vp, _i32, _i32, ctypes.POINTER(DymuRouteOut),
@@ -1849,6 +1918,59 @@ class Planner:
         _b_int(self._lib.dymu_planner_get_arriving_stats_to(self.h, b, s.ctypes.data, len(s),
                                                             max_wp, out.ctypes.data))
         return out
+
+    # -- arriving paths thinned within a bound (DyMuPathPlanner::getSimplifiedPaths, s5.18) --
+    def _simplified(self, fn, pre, starts, eps, max_wp):
+        s = np.ascontiguousarray([self._wp(w) for w in starts], dtype=np.float64).reshape(-1, 4)
+        n = len(s)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        rec = np.zeros(max(n, 1), dtype=ARRIVE_STAT_DTYPE)
+        _b_int(fn(self.h, *pre, s.ctypes.data, n, eps, max_wp, None, None, cnt.ctypes.data,
+                  st.ctypes.data, rec.ctypes.data))
+        self._sinks = np.full(n, -1, dtype=np.int32)
+        if n:
+            _b_int(self._lib.dymu_planner_last_path_sinks(self.h, self._sinks.ctypes.data, n))
+        total = max(int(cnt[:n].sum()), 1)
+        buf = np.empty((total, 4))
+        idx = np.zeros(total, dtype=np.uint32)
+        _b_int(fn(self.h, *pre, None, n, 0.0, 0, buf.ctypes.data, idx.ctypes.data, None, None,
+                  None))
+        ends = np.cumsum(cnt[:n])
+        return ([buf[e - c:e].copy() for e, c in zip(ends, cnt[:n])], st[:n].copy(),
+                rec[:n].copy(), [idx[e - c:e].copy() for e, c in zip(ends, cnt[:n])])
+
+    def getSimplifiedPaths(self, starts, eps: float, max_wp: int = 1 << 20):
+        """getArrivingPaths thinned while the descent runs: every dropped waypoint lies
+        within eps (map units) of the segment between the kept waypoints on either side of
+        it.  The bound is one-sided (dropped waypoints to the polyline): choose eps below
+        the clearance relied on.  max_wp bounds the walk.  Returns (paths, status, records,
+        indices): getArrivingPaths' three -- the records are those of the unsimplified
+        path -- and per path the uint32 numbers of its waypoints in
+        getArrivingPaths(stride=1), whose rows they equal in all four components.
+        lastPathSinks / lastPathsOnDevice / lastPathsKernelMs / lastSimplifiedReruns
+        report the call."""
+        return self._simplified(self._lib.dymu_planner_get_simplified_paths, (), starts, eps,
+                                max_wp)
+
+    def getSimplifiedPathsTo(self, b: int, starts, eps: float, max_wp: int = 1 << 20):
+        """getSimplifiedPaths on map b of the batch, with goal b as the sink."""
+        return self._simplified(self._lib.dymu_planner_get_simplified_paths_to, (b,), starts,
+                                eps, max_wp)
+
+    def _last_simplified(self):
+        r, b = _u64(), _u64()
+        _b_int(self._lib.dymu_planner_last_simplified(self.h, ctypes.byref(r), ctypes.byref(b)))
+        return r.value, b.value
+
+    def lastSimplifiedReruns(self) -> int:
+        """Paths of the last getSimplifiedPaths[To] that ran a second time on the device
+        because they kept more waypoints than the first slot capacity."""
+        return self._last_simplified()[0]
+
+    def lastSimplifiedBytes(self) -> int:
+        """Bytes of records, counts, slots and indices that call downloaded (0 on the host)."""
+        return self._last_simplified()[1]
 
     # -- every cell's node route to the goal (DyMuPathPlanner::getRouteFields, DESIGN.md s5.16) --
     def _route_fields(self, call, fields, outputs):
