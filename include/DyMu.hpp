@@ -279,7 +279,8 @@ class DyMuPathPlanner {
   // a box not inside the grid (as the windowed setters above).  Only the rows of the box
   // are re-packed at the next solve, so a converged map follows by the windowed
   // re-propagation; with setGlobalRisk on, obstacles the box adds reach R through the
-  // incremental update (below), an obstacle it frees through the whole recompute.
+  // incremental update (below), an obstacle it frees through the whole recompute, or, with
+  // trackObstacleRemoval on, through the incremental update as well.
   bool setCostMapWindow(unsigned i0, unsigned j0, unsigned w, unsigned h, const double* cost);
   // Narrow-band cells left by the last computeTotalCostMap (0 after a full solve).
   uint64_t lastBandSize() const { return band_cells_.size(); }
@@ -638,12 +639,25 @@ class DyMuPathPlanner {
   // How R was last brought up to date: 0 not yet, 1 the whole clearance solve, 2 the
   // incremental update after setCostMapWindow added obstacles (dymu_clearance_update_device:
   // the box's speed uploaded, the field re-propagated from the new cells, the rows of the
-  // box the engine reports downloaded and re-packed).
+  // box the engine reports downloaded and re-packed), 3 the same after a box that freed
+  // obstacles, with or without adding others (trackObstacleRemoval,
+  // dymu_clearance_edit_device: the field raised where the freed cells supported it, then
+  // re-propagated; R falls as well as rises inside the box).
   int lastRiskUpdateKind() const { return risk_update_kind_; }
+  // Off (the default): an obstacle that setCostMapWindow frees sends R through the whole
+  // clearance solve.  On: it joins the pending box like an added one, provided the global
+  // risk is on, R is current, the resident maps are those R belongs to and the engine has
+  // the edit entry; a stale R, dropped maps or an engine error leave the whole solve
+  // (kind 1) as before.  Takes effect from the next setCostMapWindow.
+  void trackObstacleRemoval(bool on) { track_removal_ = on; }
+  bool tracksObstacleRemoval() const { return track_removal_; }
   // ... the engine's statistics of that solve or update (ms: its device time), and the box
   // {i0, j0, w, h} of R it rewrote: the whole grid, or what the incremental update reported
   const dymu_stats& lastRiskStats() const { return risk_stats_; }
   const uint32_t* lastRiskBox() const { return risk_box_; }
+  // {raise passes, raise tile visits, cells invalidated, 0} of the last update of kind 3
+  // (dymu_last_update_stats); zeros after every other kind
+  const uint64_t* lastRiskRaise() const { return risk_raise_; }
 
  private:
   // the global risk: on iff both are > 0; R (ny*nx, empty while off) belongs to the
@@ -658,12 +672,14 @@ class DyMuPathPlanner {
   double *dMask_ = nullptr, *dW_ = nullptr, *dS_ = nullptr;
   bool risk_dev_valid_ = false;
   void dropRiskMaps();
-  // obstacles setCostMapWindow added since R was brought up to date: their bounding box
-  bool risk_pend_ = false;
+  // obstacles setCostMapWindow added since R was brought up to date (and, with
+  // track_removal_, freed: risk_pend_freed_): their bounding box
+  bool risk_pend_ = false, risk_pend_freed_ = false, track_removal_ = false;
   unsigned rpend_i0_ = 0, rpend_i1_ = 0, rpend_j0_ = 0, rpend_j1_ = 0;
   int risk_update_kind_ = 0;
   dymu_stats risk_stats_{};
   uint32_t risk_box_[4] = {0, 0, 0, 0};
+  uint64_t risk_raise_[4] = {0, 0, 0, 0};
   // the speed without the risk factor, +inf for an obstacle node: the mask's source
   double rawSpeed(uint64_t k) const {
     return is_obstacle_[k] ? std::numeric_limits<double>::infinity()

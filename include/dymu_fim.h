@@ -713,6 +713,35 @@ int dymu_clearance_update_device(dymu_ctx* ctx, const double* dF, double* dW, do
                                  uint32_t nx, uint32_t ny, uint64_t ld, double c, uint32_t i0,
                                  uint32_t j0, uint32_t w, uint32_t h, void* stream,
                                  uint32_t box[4], dymu_stats* stats);
+/* The field after the obstacle set changed in ANY way inside a window -- cells added, cells
+ * freed, or both -- without a whole solve.  Arguments, preconditions and
+ * argument errors are dymu_clearance_update_device's, except that the obstacle set of dF may
+ * differ from the old one in any way inside the clipped window.
+ * Every state the passes leave is a supersolution: a cell's value was the update of its
+ * neighbours when it was written, and they only fell afterwards.  The call sets the freed
+ * cells (finite in dF, +0.0 in dS) to +inf and then every finite cell, obstacle cells of dF
+ * excepted, whose update from its current neighbours exceeds its value by more than 1e-13
+ * relative, until nothing changes (a raise front on 16 x 16 tiles from the window's tiles,
+ * whatever the pass kernel's tile is).  What is left bounds the new field from above, and a
+ * kept converged value <= 1 is the new value.  The added cells are then seeded at +0.0, the
+ * tiles the raise claimed that hold a +inf cell of finite dF beside a finite cell are queued
+ * with the smallest such neighbour value as their key, and the priority passes run to the
+ * level 1 as in dymu_clearance_update_device.
+ * Postcondition: dS meets dymu_clearance_device's contract for the mask of dF; a freed cell
+ * no longer holds +0.0.  box as in dymu_clearance_update_device, over the tiles the raise
+ * and the passes each claimed: every cell of dS outside it is bit for bit what it was, every
+ * cell either wrote lies inside it; dF, dW and the columns nx .. ld-1 are not written.  The
+ * raise ends where the values of the old solve end: no bound short of that is proven.  With
+ * no added and no freed cell in the window: box = {i0, j0, 0, 0}, stats->passes = 0, nothing
+ * written.  dymu_last_update_stats afterwards: {raise passes, raise tile visits, cells
+ * invalidated, 0}, zeros when nothing was freed.  stats->ms covers the count, the raise, the
+ * seeding and the passes.  Always runs a priority kernel; deterministic and exact_sqrt as
+ * for any solve, and in deterministic mode two calls from the same state give the same
+ * bytes.  DYMU_ERR_STATE while stepping is on.  Blocks until the exit. */
+int dymu_clearance_edit_device(dymu_ctx* ctx, const double* dF, double* dW, double* dS,
+                               uint32_t nx, uint32_t ny, uint64_t ld, double c, uint32_t i0,
+                               uint32_t j0, uint32_t w, uint32_t h, void* stream,
+                               uint32_t box[4], dymu_stats* stats);
 /* The risk folded into the speed, per cell and operation by operation:
  *   R = fmax(1.0 - S, 0.0);  out = F * (risk_ratio * R + 1.0)
  * so S > 1, S = +inf and risk_ratio = 0 give F bit for bit, and an obstacle stays +inf or

@@ -276,9 +276,16 @@ int dymu_planner_set_trafficability_window(dymu_planner* p, uint32_t i0, uint32_
 /* setCostMapWindow: setCostMap's per-cell rule for the cells [i0, i0+w) x [j0, j0+h) only
  * (w*h costs, row-major).  1 = set; 0 = rejected, nothing changed (a box not inside the
  * grid); DYMU_ERR_ARG for a null pointer.  Only the box's rows are re-packed at the next
- * solve; with the global risk on, added obstacles update R incrementally. */
+ * solve; with the global risk on, added obstacles update R incrementally, and freed ones
+ * too once dymu_planner_track_obstacle_removal is on (else by the whole clearance solve). */
 int dymu_planner_set_cost_map_window(dymu_planner* p, uint32_t i0, uint32_t j0, uint32_t w,
                                      uint32_t h, const double* cost);
+/* trackObstacleRemoval(on != 0): off by default.  On: an obstacle that a later
+ * dymu_planner_set_cost_map_window frees joins the pending box of the incremental update
+ * (dymu_clearance_edit_device) instead of sending R through the whole clearance solve,
+ * provided the global risk is on, R is current and the engine has the entry.  DYMU_OK;
+ * DYMU_ERR_ARG for a null handle. */
+int dymu_planner_track_obstacle_removal(dymu_planner* p, int on);
 /* DyMuPathPlanner::setGlobalRisk (off by default): the obstacle clearance
  * of the global map as one more factor of the speed, F * (risk_ratio * R + 1) with
  * R = max(1 - distance to the nearest obstacle / risk_distance, 0).  Either argument 0
@@ -288,11 +295,15 @@ int dymu_planner_set_global_risk(dymu_planner* p, double risk_distance, double r
 /* getGlobalRiskMatrix(): R, ny*nx (recomputed first when stale; zeros while off) */
 int dymu_planner_get_global_risk(dymu_planner* p, double* out);
 /* lastRiskUpdateKind(): how R was last brought up to date: 0 not yet, 1 the whole clearance
- * solve, 2 the incremental update after setCostMapWindow added obstacles */
+ * solve, 2 the incremental update after setCostMapWindow added obstacles, 3 the incremental
+ * update after it freed some (dymu_planner_track_obstacle_removal) */
 int dymu_planner_last_risk_update_kind(dymu_planner* p);
 /* ... the engine's statistics of that clearance solve or update (either may be NULL) and the
  * box {i0, j0, w, h} of R it rewrote: the whole grid, or the box the update reported */
 int dymu_planner_last_risk_update(dymu_planner* p, dymu_stats* out, uint32_t box[4]);
+/* ... and, after an update of kind 3, the raise's figures as dymu_last_update_stats gives
+ * them: {raise passes, raise tile visits, cells invalidated, 0}; zeros after any other kind */
+int dymu_planner_last_risk_raise(dymu_planner* p, uint64_t out[4]);
 /* narrow-band cells left by the last computeTotalCostMap's early exit (0 after
  * computeEntireTotalCostMap) */
 int64_t dymu_planner_last_band_size(dymu_planner* p);

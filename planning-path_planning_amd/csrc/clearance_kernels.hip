@@ -17,6 +17,8 @@
 // k_seed_mask_window and k_claimed_box serve the incremental update after obstacles were
 // added inside a window: the new cells seeded into the old field, which is an upper bound
 // of the new one, and the bounding box of the tiles the passes behind it claimed.
+// k_cone_keys and k_cone_queue serve the edit that also frees obstacles (s5.11.2): behind
+// the seeded raise (update_kernels.hip) they queue the boundary of what it invalidated.
 #include "fim_kernels.h"
 
 #include <algorithm>
@@ -248,6 +250,67 @@ __global__ __launch_bounds__(256) void k_claimed_box(const uint32_t* __restrict_
   }
 }
 
+// The cone's boundary after a seeded raise (dymu_clearance_edit_device), in two launches so
+// that the first reads the raise's stamps while nothing overwrites them: the pass domain's
+// claims go to the same array, and with 8-cell pass tiles to other indices of it.
+//
+// k_cone_keys: a workgroup of 256 lanes on one 16x16 raise tile of the box at a time, one
+// lane per cell.  A tile the raise did not claim is skipped: its +inf cells beside finite
+// ones are where the old solve stopped at the level, not a cone.  A boundary cell lowers the
+// key of its pass tile (one of up to four under a raise tile) through LDS, then one atomic
+// per pass tile and raise tile on the key, and one on theta.
+__global__ __launch_bounds__(256) void k_cone_keys(ConeArgs a) {
+  __shared__ unsigned long long s_key[4];
+  constexpr unsigned long long kInfBits = 0x7FF0000000000000ull;
+  const uint32_t ci = threadIdx.x & 15u, cj = threadIdx.x >> 4;
+  const uint32_t per = 16u / a.tw;  // pass tiles per raise tile edge: 1 or 2 (tw = th)
+  const uint32_t sub = (cj / a.th) * per + ci / a.tw;
+  const uint32_t nb = a.nbx * a.nby;
+  for (uint32_t q = blockIdx.x; q < nb; q += gridDim.x) {  // block-uniform
+    const uint32_t by = q / a.nbx, tx = a.bx0 + (q - by * a.nbx), ty = a.by0 + by;
+    if (a.tile_epoch[ty * a.ntx16 + tx] < a.stamp_lo) continue;
+    if (threadIdx.x < 4u) s_key[threadIdx.x] = kInfBits;
+    __syncthreads();
+    const uint32_t i = tx * 16u + ci, j = ty * 16u + cj;
+    if (i < a.nx && j < a.ny) {
+      const int64_t k = (int64_t)j * a.ld + i;
+      if (a.S[k] == kInfD && a.F[k] < kInfD) {
+        double m = kInfD;  // S >= 0 and never NaN: fmin over the in-grid neighbours
+        if (j > 0u) m = fmin(m, a.S[k - a.ld]);
+        if (i > 0u) m = fmin(m, a.S[k - 1]);
+        if (i + 1u < a.nx) m = fmin(m, a.S[k + 1]);
+        if (j + 1u < a.ny) m = fmin(m, a.S[k + a.ld]);
+        if (m < kInfD) atomicMin(&s_key[sub], (unsigned long long)__double_as_longlong(m));
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < per * per && s_key[threadIdx.x] != kInfBits) {
+      const uint32_t px = tx * per + threadIdx.x % per, py = ty * per + threadIdx.x / per;
+      atomicMin(&a.keys[py * a.ntx + px], s_key[threadIdx.x]);
+      atomicMin(a.theta_bits, s_key[threadIdx.x]);
+    }
+    __syncthreads();  // s_key is written again for the next tile
+  }
+}
+
+// k_cone_queue: a lane per pass tile under the raise's box; a tile whose key is finite --
+// k_cone_keys lowered it, or the seeding of the added cells stored +0.0 and claimed the tile
+// already -- enters list 0 once.  The histogram is binned from the final keys afterwards.
+__global__ __launch_bounds__(256) void k_cone_queue(ConeArgs a) {
+  const uint32_t per = 16u / a.tw;
+  const uint32_t px0 = a.bx0 * per, py0 = a.by0 * per;
+  const uint32_t nty = (a.ny + a.th - 1u) / a.th;
+  const uint32_t pw = min((a.bx0 + a.nbx) * per, a.ntx) - px0;
+  const uint32_t ph = min((a.by0 + a.nby) * per, nty) - py0;
+  const uint32_t n = pw * ph, shard = blockIdx.x % kShards;
+  for (uint32_t q = blockIdx.x * 256u + threadIdx.x; q < n; q += gridDim.x * 256u) {
+    const uint32_t y = q / pw, t = (py0 + y) * a.ntx + px0 + (q - y * pw);
+    if (a.keys[t] == 0x7FF0000000000000ull) continue;
+    if (atomicMax(&a.tile_epoch[t], a.epoch) < a.epoch)
+      a.list[(uint64_t)shard * a.shard_cap + atomicAdd(&a.counts[shard], 1u)] = t;
+  }
+}
+
 // a wave on 64 consecutive doubles of a row, 2-D grid stride; out may be F (every cell is
 // read and written by its own lane)
 __global__ __launch_bounds__(256) void k_inflate_speed(const double* F, const double* S,
@@ -297,6 +360,21 @@ hipError_t launch_claimed_box(const uint32_t* tile_epoch, uint32_t ntiles, uint3
   const unsigned blocks = (unsigned)std::min<uint64_t>(((uint64_t)ntiles + 255u) / 256u, 1024u);
   hipLaunchKernelGGL(k_claimed_box, dim3(blocks), dim3(256), 0, st, tile_epoch, ntiles, ntx,
                      epoch_lo, box);
+  return hipGetLastError();
+}
+
+hipError_t launch_cone_keys(const ConeArgs& a, uint32_t blocks, hipStream_t st) {
+  const uint32_t nb = a.nbx * a.nby;
+  if (nb == 0u) return hipSuccess;
+  hipLaunchKernelGGL(k_cone_keys, dim3(std::min(nb, std::max(blocks, 1u))), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cone_queue(const ConeArgs& a, hipStream_t st) {
+  const uint64_t per = 16u / a.tw, n = (uint64_t)a.nbx * per * a.nby * per;
+  if (n == 0u) return hipSuccess;
+  const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255u) / 256u, 1024u);
+  hipLaunchKernelGGL(k_cone_queue, dim3(blocks), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -2689,14 +2689,24 @@ int dymu_clearance_device(dymu_ctx* c, const double* dF, double* dW, double* dS,
 // The field after obstacles were added inside a window: a warm, decrease-only start on
 // (dW, dS) -- the old field bounds the new one from above, so nothing is reset -- from the
 // new obstacle cells, the passes under converge_level, then the box of the claimed tiles.
-int dymu_clearance_update_device(dymu_ctx* c, const double* dF, double* dW, double* dS,
-                                 uint32_t nx, uint32_t ny, uint64_t ld, double step, uint32_t i0,
-                                 uint32_t j0, uint32_t w, uint32_t h, void* stream,
-                                 uint32_t box[4], dymu_stats* stats) {
+//
+// edit (dymu_clearance_edit_device): the window may free obstacle cells
+// too.  Every state the passes leave is a supersolution (a cell's value was the update of its
+// neighbours when it was written, and they only fell since), so after the freed cells are
+// set to +inf and every cell whose value its current neighbours no longer support followed
+// them (the seeded raise, k_raise<true>, on the domain's plain lists in 16x16 tiles as in
+// resolve_core), what is left bounds the new field from above and the warm start above fills
+// the cone: from the added cells and from the cone's boundary inside the tiles the raise
+// claimed.  The box is the union of what the raise and the passes each claimed.
+namespace {
+int clearance_window(dymu_ctx* c, const double* dF, double* dW, double* dS, uint32_t nx,
+                     uint32_t ny, uint64_t ld, double step, uint32_t i0, uint32_t j0, uint32_t w,
+                     uint32_t h, void* stream, uint32_t box[4], dymu_stats* stats, bool edit) {
   if (!c || !dF || !dW || !dS || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
   if (!(step > 0.0) || !(step < __builtin_inf())) return DYMU_ERR_ARG;
   if (w == 0 || h == 0 || i0 >= nx || j0 >= ny) return DYMU_ERR_ARG;
   if (c->stepping) return DYMU_ERR_STATE;
+  if (edit) std::memset(c->last_update, 0, sizeof c->last_update);
   HIPC(c, hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, stream);
   HIPC(c, hipEventRecord(c->ev0, st));
@@ -2730,11 +2740,12 @@ int dymu_clearance_update_device(dymu_ctx* c, const double* dF, double* dW, doub
                        hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return fail_hip(c, e, "obstacle window count");
-  if (c->h_probe[1] != 0ull) {
+  const bool added = c->h_probe[0] != 0ull, freed = c->h_probe[1] != 0ull;
+  if (freed && !edit) {
     c->last_error = "clearance update: the window frees an obstacle cell";
     return DYMU_ERR_STATE;
   }
-  if (c->h_probe[0] == 0ull) {  // nothing new: the field stands, and no domain to finish
+  if (!added && !freed) {  // nothing new: the field stands, and no domain to finish
     HIPC(c, hipEventRecord(c->ev1, st));
     double ms = 0.0;
     const int rc = event_ms(c, c->ev0, c->ev1, &ms);
@@ -2748,6 +2759,93 @@ int dymu_clearance_update_device(dymu_ctx* c, const double* dF, double* dW, doub
       stats->kernel = variant;
     }
     return DYMU_OK;
+  }
+  // The raise, on a domain of its own: its lists as plain lists of 16x16 tiles whatever the
+  // pass kernel's tile is, from the tiles that meet the window, until a pass queues nothing.
+  // rt: the tiles it claimed, {x0, y0, x1, y1} in raise tiles; stamps from raise_lo on.
+  const uint32_t ntx16 = (nx + 15u) / 16u, nty16 = (ny + 15u) / 16u;
+  uint32_t rt[4] = {0u, 0u, 0u, 0u}, raise_lo = 0u;
+  uint32_t* dbox = reinterpret_cast<uint32_t*>(c->d_scratch + 2);
+  if (freed) {
+    int rc = dom_begin(c, dW, dS, nx, ny, ld, 0, 0, -1, -1, st, /*cold=*/false, /*need_keys=*/true);
+    if (rc) return rc;
+    auto& D = c->dom;
+    UpdateArgs u{};
+    bind_list0(c, u);
+    u.tw = u.th = 16;
+    u.ntx = ntx16;
+    u.keys = nullptr;  // no keys, no histogram: the raise front has no order
+    u.hist = nullptr;
+    raise_lo = u.epoch;
+    unsigned long long* rst = c->d_scratch + 4;  // [visits, cells]; the count was read above
+    e = launch_seed_window(u, win.i0, win.j0, win.i1, win.j1, st);
+    if (e == hipSuccess) e = hipMemsetAsync(rst, 0, 2 * sizeof(unsigned long long), st);
+    if (e != hipSuccess) {
+      dom_retire(c);
+      return fail_hip(c, e, "raise seeding");
+    }
+    RaiseArgs ra{};
+    ra.T = dS;
+    ra.F = dF;  // the mask; the speed is the constant
+    ra.c = step;
+    ra.ld = (int64_t)ld;
+    ra.nx = nx;
+    ra.ny = ny;
+    ra.ntx = ntx16;
+    ra.nty = nty16;
+    ra.shard_cap = D.ntiles;
+    ra.tile_epoch = c->d_tile_epoch;
+    ra.tol = 1e-13;
+    ra.stats = rst;
+    uint64_t K = 4, raise_passes = 0;
+    for (;;) {
+      for (uint64_t k = 0; k < K; ++k, ++D.p) {
+        const uint64_t p = D.p;
+        if (p > D.max_passes) {
+          c->last_error = "raise: pass cap reached";
+          dom_retire(c);
+          return DYMU_ERR_NOT_CONVERGED;
+        }
+        ra.list_in = D.lists[p % 3];
+        ra.count_in = D.counts[p % 3];
+        ra.list_out = D.lists[(p + 1) % 3];
+        ra.count_out = D.counts[(p + 1) % 3];
+        ra.count_clear = D.counts[(p + 2) % 3];
+        ra.epoch = D.eb + (uint32_t)p + 2u;
+        e = launch_raise_seeded(ra, c->cu_count * 2, st);
+        if (e != hipSuccess) {
+          dom_retire(c);
+          return fail_hip(c, e, "raise pass");
+        }
+        ++raise_passes;
+      }
+      uint64_t pending = 0;
+      rc = dom_pending(c, st, &pending);
+      if (rc) {
+        dom_retire(c);
+        return rc;
+      }
+      if (pending == 0) break;
+      K = std::min<uint64_t>(K * 2, 64);
+    }
+    // what the raise claimed, before the pass domain's claims go to the same stamps
+    unsigned long long hr[2];
+    e = launch_store_u64(c->d_scratch + 2, ~0ull, st);
+    if (e == hipSuccess) e = launch_store_u64(c->d_scratch + 3, 0ull, st);
+    if (e == hipSuccess)
+      e = launch_claimed_box(c->d_tile_epoch, ntx16 * nty16, ntx16, raise_lo, dbox, st);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(c->h_probe, dbox, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(hr, rst, sizeof hr, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+      dom_retire(c);
+      return fail_hip(c, e, "raise box");
+    }
+    std::memcpy(rt, c->h_probe, sizeof rt);
+    c->last_update[0] = raise_passes;
+    c->last_update[1] = hr[0];
+    c->last_update[2] = hr[1];
   }
   // A per-pass target of one tile: every pass relaxes the lowest non-empty key bin only
   // (pass_scan's b*), so the tiles are visited in key order and none whose key lies above
@@ -2766,13 +2864,54 @@ int dymu_clearance_update_device(dymu_ctx* c, const double* dF, double* dW, doub
   a.ec = D.a.ec;
   win.seed = 1u;
   const uint32_t eb = D.eb, ntiles = D.ntiles, ntx = (uint32_t)D.a.ntx;
-  e = launch_store_u64(prio_minkey(c, 0), 0ull, st);
-  if (e == hipSuccess)
-    e = launch_store_u64(reinterpret_cast<unsigned long long*>(prio_base(c, 0)), 0ull, st);
-  // the edge columns belong to whatever domain ran last: from the old field, then the
-  // seeding kernel adds the new cells'
-  if (e == hipSuccess && D.a.ec) e = launch_ec_rebuild(dS, ld, nx, ny, D.a.ec, ntx, 0, ntiles, st);
-  if (e == hipSuccess) e = launch_seed_mask_window(dF, a, win, blocks, st);
+  // the edge columns belong to whatever domain ran last: from the old field (after the raise
+  // wrote it), then the seeding kernel adds the new cells'
+  e = D.a.ec ? launch_ec_rebuild(dS, ld, nx, ny, D.a.ec, ntx, 0, ntiles, st) : hipSuccess;
+  if (!freed) {  // list 0's smallest key and histogram origin: +0.0, the value of every seed
+    if (e == hipSuccess) e = launch_store_u64(prio_minkey(c, 0), 0ull, st);
+    if (e == hipSuccess)
+      e = launch_store_u64(reinterpret_cast<unsigned long long*>(prio_base(c, 0)), 0ull, st);
+    if (e == hipSuccess) e = launch_seed_mask_window(dF, a, win, blocks, st);
+  } else {
+    // The cone's boundary joins the added cells in list 0, keyed with the boundary's values:
+    // the keys first (they read the raise's stamps), then the claims.  theta: the smallest
+    // key queued, +0.0 with an added cell; the histogram is binned from the final keys, as
+    // after the single-goal raise (resolve_core).
+    unsigned long long* theta = c->d_scratch;
+    uint32_t* hist0 = a.hist;
+    a.hist = nullptr;
+    ConeArgs k{};
+    k.S = dS;
+    k.F = dF;
+    k.ld = (int64_t)ld;
+    k.nx = nx;
+    k.ny = ny;
+    k.ntx16 = ntx16;
+    k.bx0 = rt[0], k.by0 = rt[1];
+    k.nbx = rt[2] > rt[0] ? rt[2] - rt[0] : 0u;
+    k.nby = rt[3] > rt[1] ? rt[3] - rt[1] : 0u;
+    // dom_begin restarted the epochs (its wrap guard zeroed every stamp, the raise's too):
+    // every tile of the raise's box is scanned then.  The box was reduced before that, and
+    // a tile the raise did not claim holds the old solve's stop at the level: a visit of it
+    // writes values above the level at most, inside the box.
+    k.stamp_lo = D.eb < raise_lo ? 0u : raise_lo;
+    k.tw = a.tw, k.th = a.th, k.ntx = a.ntx;
+    k.list = a.list;
+    k.counts = a.counts;
+    k.shard_cap = a.shard_cap;
+    k.tile_epoch = a.tile_epoch;
+    k.epoch = a.epoch;
+    k.keys = a.keys;
+    k.theta_bits = theta;
+    if (e == hipSuccess) e = launch_store_u64(theta, added ? 0ull : 0x7FF0000000000000ull, st);
+    if (e == hipSuccess) e = launch_cone_keys(k, blocks, st);
+    if (e == hipSuccess && added) e = launch_seed_mask_window(dF, a, win, blocks, st);
+    if (e == hipSuccess) e = launch_cone_queue(k, st);
+    if (e == hipSuccess) e = launch_theta_state(theta, prio_minkey(c, 0), prio_base(c, 0), st);
+    if (e == hipSuccess)
+      e = launch_rehist(D.lists[0], D.counts[0], D.ntiles, prio_keys(c, 0), prio_base(c, 0),
+                        prio_delta(c), hist0, c->d_hist + (uint64_t)4 * kShards * kBins, st);
+  }
   if (e != hipSuccess) {
     dom_retire(c);
     return fail_hip(c, e, "obstacle window seeding");
@@ -2781,7 +2920,6 @@ int dymu_clearance_update_device(dymu_ctx* c, const double* dF, double* dW, doub
   if (rc) return rc;
   // every tile a list of this domain held carries a stamp above eb; the stamps are left to
   // the next domain, whose epochs lie above them
-  uint32_t* dbox = reinterpret_cast<uint32_t*>(c->d_scratch + 2);
   e = launch_store_u64(c->d_scratch + 2, ~0ull, st);
   if (e == hipSuccess) e = launch_store_u64(c->d_scratch + 3, 0ull, st);
   if (e == hipSuccess) e = launch_claimed_box(c->d_tile_epoch, ntiles, ntx, eb + 1u, dbox, st);
@@ -2792,12 +2930,42 @@ int dymu_clearance_update_device(dymu_ctx* c, const double* dF, double* dW, doub
   if (box) {
     uint32_t t[4];
     std::memcpy(t, c->h_probe, sizeof t);
-    const uint32_t bi0 = t[0] * a.tw, bj0 = t[1] * a.th;
-    const uint32_t bi1 = (uint32_t)std::min<uint64_t>((uint64_t)t[2] * a.tw, nx);
-    const uint32_t bj1 = (uint32_t)std::min<uint64_t>((uint64_t)t[3] * a.th, ny);
-    box[0] = bi0, box[1] = bj0, box[2] = bi1 - bi0, box[3] = bj1 - bj0;
+    // in cells: the pass domain's tiles (none when nothing was queued), then the raise's
+    uint64_t b[4] = {~0ull, ~0ull, 0ull, 0ull};
+    auto join = [&](const uint32_t q[4], uint32_t tw, uint32_t th) {
+      if (q[2] == 0u) return;
+      b[0] = std::min<uint64_t>(b[0], (uint64_t)q[0] * tw);
+      b[1] = std::min<uint64_t>(b[1], (uint64_t)q[1] * th);
+      b[2] = std::max<uint64_t>(b[2], std::min<uint64_t>((uint64_t)q[2] * tw, nx));
+      b[3] = std::max<uint64_t>(b[3], std::min<uint64_t>((uint64_t)q[3] * th, ny));
+    };
+    join(t, a.tw, a.th);
+    join(rt, 16u, 16u);
+    if (b[2] == 0ull) {
+      box[0] = i0, box[1] = j0, box[2] = box[3] = 0u;
+    } else {
+      box[0] = (uint32_t)b[0], box[1] = (uint32_t)b[1];
+      box[2] = (uint32_t)(b[2] - b[0]), box[3] = (uint32_t)(b[3] - b[1]);
+    }
   }
   return DYMU_OK;
+}
+}  // namespace
+
+int dymu_clearance_update_device(dymu_ctx* c, const double* dF, double* dW, double* dS,
+                                 uint32_t nx, uint32_t ny, uint64_t ld, double step, uint32_t i0,
+                                 uint32_t j0, uint32_t w, uint32_t h, void* stream,
+                                 uint32_t box[4], dymu_stats* stats) {
+  return clearance_window(c, dF, dW, dS, nx, ny, ld, step, i0, j0, w, h, stream, box, stats,
+                          /*edit=*/false);
+}
+
+int dymu_clearance_edit_device(dymu_ctx* c, const double* dF, double* dW, double* dS, uint32_t nx,
+                               uint32_t ny, uint64_t ld, double step, uint32_t i0, uint32_t j0,
+                               uint32_t w, uint32_t h, void* stream, uint32_t box[4],
+                               dymu_stats* stats) {
+  return clearance_window(c, dF, dW, dS, nx, ny, ld, step, i0, j0, w, h, stream, box, stats,
+                          /*edit=*/true);
 }
 
 int dymu_inflate_speed_device(dymu_ctx* c, const double* dF, const double* dS, double* dOut,

@@ -342,8 +342,14 @@ struct RaiseArgs {
   uint32_t epoch;
   double tol;
   unsigned long long* stats;  // [0] tile visits, [1] cells invalidated
+  double c;                   // launch_raise_seeded: the constant speed
 };
 hipError_t launch_raise(const RaiseArgs& a, int blocks, hipStream_t st);
+// The raise of a seeded constant-speed field (the clearance field after obstacle cells were
+// freed): the speed is a.c everywhere, a.F is the mask whose obstacle cells (+inf or NaN) are
+// the seeds and exempt (a.gi, a.gj are not read), and a cell that is free in the mask and
+// holds +0.0 becomes +inf whatever its neighbours hold.
+hipError_t launch_raise_seeded(const RaiseArgs& a, int blocks, hipStream_t st);
 // after the raise: list 0 <- every tile holding a finite-speed +inf cell (not the goal)
 // next to a finite cell, key = the smallest such neighbour value of the tile (a
 // scheduling hint), histogram bin 0; *theta_bits lowered to the smallest key
@@ -637,6 +643,34 @@ hipError_t launch_seed_mask_window(const double* F, const MaskSeedArgs& a, const
 // tile_epoch >= epoch_lo
 hipError_t launch_claimed_box(const uint32_t* tile_epoch, uint32_t ntiles, uint32_t ntx,
                               uint32_t epoch_lo, uint32_t* box, hipStream_t st);
+// The boundary of the cone a seeded raise left (dymu_clearance_edit_device), from the 16x16
+// raise tiles of the box [bx0, bx0 + nbx) x [by0, by0 + nby) whose stamp is at least stamp_lo
+// (the tiles the raise claimed) and from no other tile: the old field's own stop at the level
+// is a +inf cell beside a finite one too, map-wide.
+struct ConeArgs {
+  const double* S;
+  const double* F;  // the mask
+  int64_t ld;
+  uint32_t nx, ny;
+  uint32_t ntx16;                  // raise tiles per row
+  uint32_t bx0, by0, nbx, nby;     // the raise's box, in raise tiles
+  uint32_t stamp_lo;               // the raise's first epoch; 0 (every tile of the box) when
+                                   // the epochs restarted behind the raise and took its stamps
+  uint32_t tw, th, ntx;            // the pass kernel's tiles (8 or 16 cells), bind_list0
+  uint32_t* list;                  // list 0 (kShards x shard_cap)
+  uint32_t* counts;
+  uint32_t shard_cap;
+  uint32_t* tile_epoch;
+  uint32_t epoch;
+  unsigned long long* keys;        // keys of list 0: +inf bits wherever no seeding kernel wrote
+  unsigned long long* theta_bits;  // lowered to the smallest key
+};
+// keys[t] = min(keys[t], v) for every pass tile t that holds a cell with S = +inf, finite F
+// and a finite in-grid 4-neighbour, v the smallest such neighbour value; reads the stamps,
+// writes none
+hipError_t launch_cone_keys(const ConeArgs& a, uint32_t blocks, hipStream_t st);
+// list 0 <- every pass tile under the raise's box whose key is finite, claimed once
+hipError_t launch_cone_queue(const ConeArgs& a, hipStream_t st);
 // out = F * (risk_ratio * max(1 - S, 0) + 1) per cell, operation by operation; out may be F
 hipError_t launch_inflate_speed(const double* F, const double* S, double* out, uint64_t ld,
                                 uint32_t nx, uint32_t ny, double risk_ratio, hipStream_t st);

@@ -168,11 +168,15 @@ bool DyMuPathPlanner::setCostMap(std::vector<std::vector<double>> cost_map) {
 }
 
 #pragma weak dymu_clearance_update_device
+#pragma weak dymu_clearance_edit_device
+#pragma weak dymu_last_update_stats
 
 // setCostMap's per-cell rule on the cells of the box alone.  With the global risk on, the
 // obstacle mask is that of the raw speed (refreshGlobalRisk): a cell the box turns into an
-// obstacle joins the pending box of the incremental update; a cell it frees, or a field
-// on the device that is not the one R belongs to, leaves the whole recompute.
+// obstacle joins the pending box of the incremental update, and so does a cell it frees
+// while trackObstacleRemoval is on and the engine has the edit entry; otherwise a freed
+// cell, or a field on the device that is not the one R belongs to, leaves the whole
+// recompute.
 bool DyMuPathPlanner::setCostMapWindow(unsigned i0, unsigned j0, unsigned w, unsigned h,
                                        const double* cost) {
   if (!cost || (uint64_t)i0 + w > nx_ || (uint64_t)j0 + h > ny_) return false;
@@ -196,9 +200,12 @@ bool DyMuPathPlanner::setCostMapWindow(unsigned i0, unsigned j0, unsigned w, uns
       }
     }
   markDirty(j0, j0 + h);
-  if (freed || (added && (risk_stale_ || !risk_dev_valid_ || !&dymu_clearance_update_device))) {
+  const bool can_free = track_removal_ && &dymu_clearance_edit_device;
+  if ((freed && !can_free) ||
+      ((added || freed) && (risk_stale_ || !risk_dev_valid_ || !&dymu_clearance_update_device))) {
     risk_stale_ = true;
-  } else if (added) {
+  } else if (added || freed) {
+    risk_pend_freed_ = (risk_pend_ && risk_pend_freed_) || freed;
     if (!risk_pend_) {
       rpend_i0_ = i0, rpend_i1_ = i0 + w, rpend_j0_ = j0, rpend_j1_ = j0 + h;
     } else {
@@ -704,13 +711,13 @@ void DyMuPathPlanner::dropRiskMaps() {
   }
   risk_dev_valid_ = false;
   if (risk_pend_) risk_stale_ = true;  // the field the pending box would update is gone
-  risk_pend_ = false;
+  risk_pend_ = risk_pend_freed_ = false;
 }
 
 void DyMuPathPlanner::refreshGlobalRisk() {
   ensureEngine();
   const uint64_t n = (uint64_t)nx_ * ny_;
-  risk_pend_ = false;  // the whole recompute sees every obstacle
+  risk_pend_ = risk_pend_freed_ = false;  // the whole recompute sees every obstacle
   if (n == 0) {
     risk_stale_ = false;
     return;
@@ -742,6 +749,7 @@ void DyMuPathPlanner::refreshGlobalRisk() {
   risk_stale_ = false;
   risk_dev_valid_ = true;
   risk_update_kind_ = 1;
+  std::fill(risk_raise_, risk_raise_ + 4, 0ull);
   risk_stats_ = st;
   risk_box_[0] = risk_box_[1] = 0, risk_box_[2] = nx_, risk_box_[3] = ny_;
   markDirty(0, ny_);
@@ -751,15 +759,20 @@ void DyMuPathPlanner::refreshGlobalRisk() {
 // them: the box's rows of the raw speed into the mask map, the field re-propagated from the new
 // cells (dymu_clearance_update_device), and the box the engine reports -- no cell of the
 // field outside it moved -- downloaded, turned into R and re-packed.  Whatever the engine
-// refuses (a freed cell it finds itself, an error) leaves the whole recompute.
+// refuses (a freed cell it finds itself, an error) leaves the whole recompute.  A pending box
+// that freed obstacles (trackObstacleRemoval) goes through dymu_clearance_edit_device
+// instead, which raises the field where the freed cells supported it first: R can fall as
+// well as rise inside the reported box, which the row diff of syncSpeed sees by itself.
 void DyMuPathPlanner::updateGlobalRisk() {
   ensureEngine();  // a new grid or engine drops the maps and turns the box into risk_stale_
-  if (risk_stale_ || !risk_pend_ || !risk_dev_valid_ || !&dymu_clearance_update_device) {
+  const bool edit = risk_pend_freed_;
+  if (risk_stale_ || !risk_pend_ || !risk_dev_valid_ || !&dymu_clearance_update_device ||
+      (edit && !&dymu_clearance_edit_device)) {
     risk_stale_ = true;
     refreshGlobalRisk();
     return;
   }
-  risk_pend_ = false;
+  risk_pend_ = risk_pend_freed_ = false;
   const unsigned i0 = rpend_i0_, j0 = rpend_j0_, w = rpend_i1_ - i0, h = rpend_j1_ - j0;
   // whole rows, one contiguous copy: outside the box they differ from the mask map in
   // finite values at most, and the engine reads the window's cells only
@@ -769,9 +782,9 @@ void DyMuPathPlanner::updateGlobalRisk() {
   uint32_t box[4] = {0, 0, 0, 0};
   dymu_stats st{};
   if (rc == DYMU_OK)
-    rc = dymu_clearance_update_device(ctx_, dMask_, dW_, dS_, nx_, ny_, nx_,
-                                      global_res_ / grisk_distance_, i0, j0, w, h, nullptr, box,
-                                      &st);
+    rc = (edit ? dymu_clearance_edit_device : dymu_clearance_update_device)(
+        ctx_, dMask_, dW_, dS_, nx_, ny_, nx_, global_res_ / grisk_distance_, i0, j0, w, h, nullptr,
+        box, &st);
   if (rc == DYMU_OK && box[2] && box[3]) {
     const uint64_t o = idx(box[0], box[1]);
     rc = dymu_memcpy2d_d2h(ctx_, &global_risk_[o], sizeof(double) * nx_, dS_ + o,
@@ -791,7 +804,9 @@ void DyMuPathPlanner::updateGlobalRisk() {
     refreshGlobalRisk();
     return;
   }
-  risk_update_kind_ = 2;
+  risk_update_kind_ = edit ? 3 : 2;
+  std::fill(risk_raise_, risk_raise_ + 4, 0ull);
+  if (edit && &dymu_last_update_stats) (void)dymu_last_update_stats(ctx_, risk_raise_);
   risk_stats_ = st;
   std::copy(box, box + 4, risk_box_);
 }

@@ -261,6 +261,18 @@ int dymu_planner_set_cost_map_window(dymu_planner* p, uint32_t i0, uint32_t j0, 
   return guarded([&] { return (int)p->pl.setCostMapWindow(i0, j0, w, h, cost); });
 }
 
+int dymu_planner_track_obstacle_removal(dymu_planner* p, int on) {
+  if (!p) return DYMU_ERR_ARG;
+  p->pl.trackObstacleRemoval(on != 0);
+  return DYMU_OK;
+}
+
+int dymu_planner_last_risk_raise(dymu_planner* p, uint64_t out[4]) {
+  if (!p || !out) return DYMU_ERR_ARG;
+  std::copy(p->pl.lastRiskRaise(), p->pl.lastRiskRaise() + 4, out);
+  return DYMU_OK;
+}
+
 int dymu_planner_last_risk_update_kind(dymu_planner* p) {
   if (!p) return DYMU_ERR_ARG;
   return p->pl.lastRiskUpdateKind();

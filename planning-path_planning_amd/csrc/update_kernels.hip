@@ -156,6 +156,12 @@ __device__ __forceinline__ double ref_update(double tx, double ty, double c) {
 constexpr int RT = 16;       // raise tile edge (kernel 5's tiling)
 constexpr int RP = RT + 2;   // image pitch
 
+// kSeeded: the raise of a seeded constant-speed field (the clearance field after obstacle
+// cells were freed, dymu_clearance_edit_device).  The speed is a.c at
+// every cell and a.F is the mask: its obstacle cells (+inf or NaN) are the seeds of the new
+// field and exempt, where the single-goal raise exempts the goal; a cell that is free in the
+// mask and still holds a seed's +0.0 goes unconditionally.
+template <bool kSeeded>
 __global__ __launch_bounds__(256) void k_raise(RaiseArgs a) {
   __shared__ uint32_t s_pref[kShards + 1];
   __shared__ double s_img[4][RP * RP];
@@ -187,13 +193,21 @@ __global__ __launch_bounds__(256) void k_raise(RaiseArgs a) {
     };
     // image: own cells (r, 4q..4q+3) and the halo ring
     double t[4], f[4];
-    bool live[4];
+    bool live[4], drop[4];  // drop: the value goes whatever the neighbours hold
     for (int c = 0; c < 4; ++c) {
       const int64_t i = i0 + 4 * q + c, j = j0 + r;
       const bool in = i < a.nx && j < a.ny;
       t[c] = in ? a.T[j * a.ld + i] : inf;
       f[c] = in ? a.F[j * a.ld + i] : inf;
-      live[c] = in && t[c] < inf && !(i == a.gi && j == a.gj);
+      if (kSeeded) {
+        const bool obst = !(f[c] < inf);
+        live[c] = in && t[c] < inf && !obst;
+        drop[c] = dbits(t[c]) == 0ull;  // a freed seed
+        f[c] = a.c;
+      } else {
+        live[c] = in && t[c] < inf && !(i == a.gi && j == a.gj);
+        drop[c] = !(f[c] < inf);  // a cell that became an obstacle loses its value outright
+      }
       img[(r + 1) * RP + 4 * q + c + 1] = t[c];
     }
     if (r == 0)
@@ -209,8 +223,7 @@ __global__ __launch_bounds__(256) void k_raise(RaiseArgs a) {
       for (int c = 0; c < 4; ++c) {
         const int s = (r + 1) * RP + 4 * q + c + 1;
         const double u = ref_update(fmin(img[s - 1], img[s + 1]), fmin(img[s - RP], img[s + RP]), f[c]);
-        // a cell that became an obstacle (F = +inf) loses its value outright
-        now[c] = live[c] && !gone[c] && (!(f[c] < inf) || u > t[c] * (1.0 + a.tol));
+        now[c] = live[c] && !gone[c] && (drop[c] || u > t[c] * (1.0 + a.tol));
       }
       __builtin_amdgcn_wave_barrier();
       bool any = false;
@@ -637,7 +650,12 @@ hipError_t launch_seed_window(const UpdateArgs& a, uint32_t i0, uint32_t j0, uin
 }
 
 hipError_t launch_raise(const RaiseArgs& a, int blocks, hipStream_t st) {
-  hipLaunchKernelGGL(k_raise, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_raise<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_raise_seeded(const RaiseArgs& a, int blocks, hipStream_t st) {
+  hipLaunchKernelGGL(k_raise<true>, dim3((unsigned)blocks), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

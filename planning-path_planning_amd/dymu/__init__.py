@@ -333,6 +333,9 @@ FIM_SYMBOLS = {
     "dymu_clearance_update_device": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, ctypes.c_double,
                                             _u32, _u32, _u32, _u32, _vp, ctypes.POINTER(_u32),
                                             ctypes.POINTER(DymuStats)]),
+    "dymu_clearance_edit_device": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, ctypes.c_double,
+                                          _u32, _u32, _u32, _u32, _vp, ctypes.POINTER(_u32),
+                                          ctypes.POINTER(DymuStats)]),
     "dymu_inflate_speed_device": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, ctypes.c_double,
                                          _vp]),
     "dymu_batch_reduce_device": (_i32, [_vp, _vp, _u32, _u32, _u32, _u64, _i32, _vp, _u32, _vp, _vp,
@@ -902,6 +905,22 @@ class Engine:
         d["box"] = tuple(int(v) for v in box)
         return d
 
+    def clearance_edit_device(self, dF: int, dW: int, dS: int, nx: int, ny: int, ld: int,
+                              c: float, i0: int, j0: int, w: int, h: int,
+                              stream: int = 0) -> dict:
+        """dymu_clearance_edit_device: clearance_update_device for a window that may free
+        obstacle cells as well as add them: the field is raised where the freed cells
+        supported it, then re-propagated.  Returns the stats with "box": (i0, j0, w, h) of the
+        cells the call may have written; last_update_stats() holds the raise's figures."""
+        st = DymuStats()
+        box = (_u32 * 4)()
+        _check(self._lib.dymu_clearance_edit_device(self.ctx, dF, dW, dS, nx, ny, ld, c, i0, j0,
+                                                    w, h, stream or None, box,
+                                                    ctypes.byref(st)), self.ctx)
+        d = st.as_dict()
+        d["box"] = tuple(int(v) for v in box)
+        return d
+
     def inflate_speed(self, dF: int, dS: int, dOut: int, nx: int, ny: int, ld: int,
                       risk_ratio: float, stream: int = 0):
         """dymu_inflate_speed_device: dOut = dF * (risk_ratio * max(1 - dS, 0) + 1); dOut may
@@ -1422,6 +1441,8 @@ PLANNER_SYMBOLS = {
     "dymu_planner_set_trafficability_window": (_i32, [_vp, _u32, _u32, _u32, _u32, _dp]),
     "dymu_planner_set_cost_map_window": (_i32, [_vp, _u32, _u32, _u32, _u32, _dp]),
     "dymu_planner_last_risk_update_kind": (_i32, [_vp]),
+    "dymu_planner_track_obstacle_removal": (_i32, [_vp, _i32]),
+    "dymu_planner_last_risk_raise": (_i32, [_vp, ctypes.POINTER(_u64)]),
     "dymu_planner_last_risk_update": (_i32, [_vp, ctypes.POINTER(DymuStats),
                                              ctypes.POINTER(_u32)]),
     "dymu_planner_last_band_size": (ctypes.c_int64, [_vp]),
@@ -2164,8 +2185,17 @@ class Planner:
         h, w = a.shape
         return _b(self._lib.dymu_planner_set_cost_map_window(self.h, i0, j0, w, h, a))
 
+    def trackObstacleRemoval(self, on: bool = True) -> None:
+        """Off by default.  On: with the global risk on and R current, an obstacle a later
+        setCostMapWindow frees reaches R through the incremental update too
+        (dymu_clearance_edit_device, lastRiskUpdateKind() == 3) instead of the whole
+        clearance solve."""
+        _check(self._lib.dymu_planner_track_obstacle_removal(self.h, 1 if on else 0))
+
     def lastRiskUpdateKind(self) -> int:
-        """How R was last brought up to date: 0 not yet, 1 whole solve, 2 incremental."""
+        """How R was last brought up to date: 0 not yet, 1 whole solve, 2 incremental after
+        obstacles were added, 3 incremental after obstacles were freed (trackObstacleRemoval),
+        with or without others added."""
         return _b_int(self._lib.dymu_planner_last_risk_update_kind(self.h))
 
     def lastRiskUpdate(self) -> dict:
@@ -2177,6 +2207,13 @@ class Planner:
         d = st.as_dict()
         d["box"] = tuple(int(v) for v in box)
         return d
+
+    def lastRiskRaise(self) -> dict:
+        """The raise of the last update of kind 3 (Engine.last_update_stats' figures); zeros
+        after any other kind."""
+        out = (_u64 * 4)()
+        _check(self._lib.dymu_planner_last_risk_raise(self.h, out))
+        return {"raise_passes": out[0], "raise_visits": out[1], "cells_invalidated": out[2]}
 
     def lastBandSize(self) -> int:
         """Narrow-band cells left by the last computeTotalCostMap (0 after a full solve)."""
