@@ -25,6 +25,26 @@
 
 using namespace dymu;
 
+// The words of dymu_ctx::d_scratch, one name per use.  A use lives from the
+// kernel that writes it to its read-back in the same call, so two names share a word only
+// where no call has both live: the clearance entries read kScrObst / kScrFreed back before
+// the edit's raise zeroes the same words for kScrEditStats; kScrCount, kScrRaiseStats and
+// kScrReset belong to three other entries, and so do the probe and the box.  kScrTheta is
+// live across the single-goal raise.  Word 1 is free.
+enum ScratchSlot {
+  kScrTheta = 0,       // smallest old value around the window / smallest key queued
+  kScrProbe = 2,       // 2 words: the early-exit probe's (max T, min key)
+  kScrBox = 2,         // 2 words: claimed_box's {x0, y0} and {x1, y1} in tiles
+  kScrCount = 4,       // early-exit band / equal-value cells counted
+  kScrObst = 4,        // obstacle cells seeded (clearance), added in a window
+  kScrFreed = 5,       // obstacle cells a window frees; read back with kScrObst
+  kScrEditStats = 4,   // 2 words: the clearance edit's raise [visits, cells]
+  kScrRaiseStats = 5,  // 2 words: the single-goal raise [visits, cells]
+  kScrReset = 5,       // cells the per-plane update reset
+  kScrRoundTotal = 7,  // dom_round's tiles queued for its first pass (32 bits)
+  kScrWords = 8
+};
+
 struct dymu_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -128,7 +148,7 @@ struct dymu_ctx {
   void* h_red_res = nullptr;
   hipEvent_t ev_red_copy = nullptr, ev_red0 = nullptr, ev_red1 = nullptr;
   bool red_copy_pending = false, red_timed = false;
-  unsigned long long* d_scratch = nullptr;  // 8 words of per-call device scalars
+  unsigned long long* d_scratch = nullptr;  // kScrWords device scalars (ScratchSlot)
   double* d_lut = nullptr;      // computeCostMap LUT (device copy)
   size_t lut_cap = 0;
 
@@ -774,7 +794,7 @@ int dom_round(dymu_ctx* c, uint64_t K, const double* lo, const double* hi, int32
   auto& D = c->dom;
   if (!dom_round_ok(c, K)) return DYMU_ERR_STATE;
   if (!d_total || (lo && !D.a.ghost_lo) || (hi && !D.a.ghost_hi)) return DYMU_ERR_ARG;
-  uint32_t* scratch = reinterpret_cast<uint32_t*>(c->d_scratch + 7);
+  uint32_t* scratch = reinterpret_cast<uint32_t*>(c->d_scratch + kScrRoundTotal);
   D.a.merge_lo = lo;
   D.a.merge_hi = hi;
   D.a.tot_save = scratch;
@@ -802,7 +822,7 @@ int dom_round_peer(dymu_ctx* c, uint64_t K, const dymu_peer_links& L, hipStream_
     if ((L.recv[s] && !L.recv_tag[s]) || (L.send[s] && (!L.send_tag[s] || !L.last[s])))
       return DYMU_ERR_ARG;
   PeerCtl* pc = static_cast<PeerCtl*>(L.ctl);
-  uint32_t* scratch = reinterpret_cast<uint32_t*>(c->d_scratch + 7);
+  uint32_t* scratch = reinterpret_cast<uint32_t*>(c->d_scratch + kScrRoundTotal);
   PassArgs& a = D.a;
   a.merge_lo = L.recv[0];
   a.merge_hi = L.recv[1];
@@ -895,6 +915,25 @@ int elapsed_ms(dymu_ctx* c, bool dymu_ctx::*timed, hipEvent_t dymu_ctx::*ev_a,
   return event_ms(c, c->*ev_a, c->*ev_b, ms);
 }
 
+// the getters of a call with four stamps (before init, after it, after the rounds, after
+// finalize): the whole call, and its three stages
+int total_ms(dymu_ctx* c, bool dymu_ctx::*timed, hipEvent_t (dymu_ctx::*ev)[4], double* ms) {
+  if (!c || !ms) return DYMU_ERR_ARG;
+  if (!(c->*timed)) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  return event_ms(c, (c->*ev)[0], (c->*ev)[3], ms);
+}
+int stage_ms(dymu_ctx* c, bool dymu_ctx::*timed, hipEvent_t (dymu_ctx::*ev)[4], double out[3]) {
+  if (!c || !out) return DYMU_ERR_ARG;
+  if (!(c->*timed)) return DYMU_ERR_STATE;
+  HIPC(c, hipSetDevice(c->device));
+  for (int k = 0; k < 3; ++k) {
+    const int rc = event_ms(c, (c->*ev)[k], (c->*ev)[k + 1], &out[k]);
+    if (rc) return rc;
+  }
+  return DYMU_OK;
+}
+
 // launch() between the event pair of a dymu_last_*_ms getter (elapsed_ms): the events are
 // created on first use, and the flag holds once both are recorded behind the launch
 template <class Launch>
@@ -967,9 +1006,9 @@ int converge(dymu_ctx* c, hipStream_t st, dymu_stats* stats, const ProbeCells* p
     if (!probe) return hipSuccess;
     auto& D = c->dom;
     const hipError_t e =
-        launch_probe(D.a.T, D.a.ld, *probe, prio_minkey(c, D.p % 3), c->d_scratch + 2, st);
+        launch_probe(D.a.T, D.a.ld, *probe, prio_minkey(c, D.p % 3), c->d_scratch + kScrProbe, st);
     if (e != hipSuccess) return e;
-    return hipMemcpyAsync(c->h_probe, c->d_scratch + 2, 2 * sizeof(unsigned long long),
+    return hipMemcpyAsync(c->h_probe, c->d_scratch + kScrProbe, 2 * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost, st);
   };
   auto stop = [&](uint64_t pending) {
@@ -1101,8 +1140,8 @@ int converge_stream(dymu_ctx* c, hipStream_t st, dymu_stats* stats,
   }
   HIPC(c, hipEventRecord(c->ev1, st));
   if (probe) {
-    HIPC(c, launch_probe(D.a.T, D.a.ld, *probe, nullptr, c->d_scratch + 2, st));
-    HIPC(c, hipMemcpyAsync(c->h_probe, c->d_scratch + 2, 2 * sizeof(unsigned long long),
+    HIPC(c, launch_probe(D.a.T, D.a.ld, *probe, nullptr, c->d_scratch + kScrProbe, st));
+    HIPC(c, hipMemcpyAsync(c->h_probe, c->d_scratch + kScrProbe, 2 * sizeof(unsigned long long),
                            hipMemcpyDeviceToHost, st));
   }
   HIPC(c, hipEventSynchronize(c->ev1));
@@ -1165,6 +1204,62 @@ int solve_until_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uin
   return converge(c, st, stats, &p, t_closed);
 }
 
+// The raise front (k_raise) on the live domain's map, its lists as plain lists
+// of 16x16 tiles whatever the pass kernel's tile is (no keys, no histogram: the front has no
+// order), stamps from eb + 1 on: from the tiles that meet the cells [win[0], win[2]) x
+// [win[1], win[3]) until a pass queues nothing -- 4 passes, then doubling up to 64, between
+// reads of the pending count.  The caller sets ra.F and ra.gi, ra.gj, or with seeded
+// (k_raise<true>) the mask and ra.c.  The scratch words at stats_slot take [visits, cells],
+// c->last_update[0..2] the passes and those two -- filled here, so they stand even if a later
+// step of the caller (the clearance edit's box read-back) fails.  Any error retires the domain.
+int run_raise(dymu_ctx* c, RaiseArgs ra, bool seeded, ScratchSlot stats_slot,
+              const uint32_t win[4], hipStream_t st) {
+  auto& D = c->dom;
+  auto fail = [&](int rc) { return dom_retire(c), rc; };
+  ra.T = D.a.T;
+  ra.ld = D.a.ld;
+  ra.nx = D.a.nx, ra.ny = D.a.ny;
+  ra.ntx = (ra.nx + 15u) / 16u, ra.nty = (ra.ny + 15u) / 16u;
+  ra.shard_cap = D.ntiles;
+  ra.tile_epoch = c->d_tile_epoch;
+  ra.tol = 1e-13;
+  ra.stats = c->d_scratch + stats_slot;
+  const int blocks = c->cu_count * 2;
+  UpdateArgs u{};
+  bind_list0(c, u);
+  u.tw = u.th = 16, u.ntx = ra.ntx;
+  u.keys = nullptr, u.hist = nullptr;
+  hipError_t e = launch_seed_window(u, win[0], win[1], win[2], win[3], st);
+  if (e == hipSuccess) e = hipMemsetAsync(ra.stats, 0, 2 * sizeof(unsigned long long), st);
+  if (e != hipSuccess) return fail(fail_hip(c, e, "raise seeding"));
+  uint64_t pending = 1, passes = 0;
+  for (uint64_t K = 4; pending; K = std::min<uint64_t>(K * 2, 64)) {
+    for (uint64_t k = 0; k < K; ++k, ++D.p, ++passes) {
+      const uint64_t p = D.p;
+      if (p > D.max_passes) {
+        c->last_error = "raise: pass cap reached";
+        return fail(DYMU_ERR_NOT_CONVERGED);
+      }
+      ra.list_in = D.lists[p % 3];
+      ra.count_in = D.counts[p % 3];
+      ra.list_out = D.lists[(p + 1) % 3];
+      ra.count_out = D.counts[(p + 1) % 3];
+      ra.count_clear = D.counts[(p + 2) % 3];
+      ra.epoch = D.eb + (uint32_t)p + 2u;
+      e = seeded ? launch_raise_seeded(ra, blocks, st) : launch_raise(ra, blocks, st);
+      if (e != hipSuccess) return fail(fail_hip(c, e, "raise pass"));
+    }
+    if (const int rc = dom_pending(c, st, &pending)) return fail(rc);
+  }
+  unsigned long long hr[2];
+  e = hipMemcpy(hr, ra.stats, sizeof hr, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(fail_hip(c, e, "raise statistics"));
+  c->last_update[0] = passes;
+  c->last_update[1] = hr[0];
+  c->last_update[2] = hr[1];
+  return DYMU_OK;
+}
+
 // Windowed re-propagation (update_kernels.hip): dT holds the converged map of
 // the previous speed, dF the new speed, which differs only inside the window.
 // decrease_only: the caller guarantees no speed in the window went up; then the
@@ -1188,7 +1283,7 @@ int resolve_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_
   const uint32_t wi0 = i0 > 0 ? i0 - 1 : 0, wj0 = j0 > 0 ? j0 - 1 : 0;
   const uint32_t wi1 = (uint32_t)std::min<uint64_t>((uint64_t)i0 + w + 1, nx);
   const uint32_t wj1 = (uint32_t)std::min<uint64_t>((uint64_t)j0 + h + 1, ny);
-  unsigned long long* theta = c->d_scratch;
+  unsigned long long* theta = c->d_scratch + kScrTheta;
   HIPC(c, launch_store_u64(theta, 0x7FF0000000000000ull, st));  // +inf bits
   HIPC(c, launch_window_min(dT, (int64_t)ld, wi0, wj0, wi1, wj1, theta, st));
   UpdateArgs u{};
@@ -1202,63 +1297,13 @@ int resolve_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, uint32_
   u.theta_bits = theta;
   const bool raise = !decrease_only && c->raise;
   if (raise) {
-    // the raise passes use the domain's lists and epochs (plain FIM lists, 16x16 tiles)
-    const uint32_t ntx16 = (nx + 15) / 16, nty16 = (ny + 15) / 16;
-    bind_list0(c, u);
-    u.tw = u.th = 16;
-    u.ntx = ntx16;
-    u.keys = nullptr;  // no keys, no histogram: the raise front has no order
-    u.hist = nullptr;
-    HIPC(c, launch_seed_window(u, i0, j0, i0 + w, j0 + h, st));
-    unsigned long long* rst = c->d_scratch + 5;  // [visits, cells]
-    HIPC(c, hipMemsetAsync(rst, 0, 2 * sizeof(unsigned long long), st));
     RaiseArgs ra{};
-    ra.T = dT;
     ra.F = dF;
-    ra.ld = (int64_t)ld;
-    ra.nx = nx;
-    ra.ny = ny;
     ra.gi = gi;
     ra.gj = gj;
-    ra.ntx = ntx16;
-    ra.nty = nty16;
-    ra.shard_cap = D.ntiles;
-    ra.tile_epoch = c->d_tile_epoch;
-    ra.tol = 1e-13;
-    ra.stats = rst;
-    const int blocks = c->cu_count * 2;
-    uint64_t K = 4, raise_passes = 0;
-    for (;;) {
-      for (uint64_t k = 0; k < K; ++k, ++D.p) {
-        const uint64_t p = D.p;
-        if (p > D.max_passes) {
-          c->last_error = "raise: pass cap reached";
-          dom_retire(c);
-          return DYMU_ERR_NOT_CONVERGED;
-        }
-        ra.list_in = D.lists[p % 3];
-        ra.count_in = D.counts[p % 3];
-        ra.list_out = D.lists[(p + 1) % 3];
-        ra.count_out = D.counts[(p + 1) % 3];
-        ra.count_clear = D.counts[(p + 2) % 3];
-        ra.epoch = D.eb + (uint32_t)p + 2u;
-        HIPC(c, launch_raise(ra, blocks, st));
-        ++raise_passes;
-      }
-      uint64_t pending = 0;
-      rc = dom_pending(c, st, &pending);
-      if (rc) {
-        dom_retire(c);
-        return rc;
-      }
-      if (pending == 0) break;
-      K = std::min<uint64_t>(K * 2, 64);
-    }
-    unsigned long long hr[2];
-    HIPC(c, hipMemcpy(hr, rst, sizeof hr, hipMemcpyDeviceToHost));
-    c->last_update[0] = raise_passes;
-    c->last_update[1] = hr[0];
-    c->last_update[2] = hr[1];
+    const uint32_t win[4] = {i0, j0, i0 + w, j0 + h};
+    rc = run_raise(c, ra, /*seeded=*/false, kScrRaiseStats, win, st);
+    if (rc) return rc;
     // a fresh domain for the re-solve: epochs above every raise epoch (dom_retire)
     rc = dom_begin(c, dF, dT, nx, ny, ld, 0, 0, -1, -1, st, /*cold=*/false);
     if (rc) return rc;
@@ -1498,7 +1543,7 @@ int update_planes_core(dymu_ctx* c, const double* dF, double* dT, uint32_t nx, u
   rc = dom_begin(c, dF, dT, nx, rows, ld, 0, 0, -1, -1, st, /*cold=*/false);
   if (rc) return rc;
   auto& D = c->dom;
-  unsigned long long* n_reset = c->d_scratch + 5;
+  unsigned long long* n_reset = c->d_scratch + kScrReset;
   PlaneUpdateArgs u{};
   u.T = dT;
   u.F = dF;
@@ -1565,6 +1610,28 @@ bool clip_window(uint32_t plane, uint32_t i0, uint32_t j0, uint32_t w, uint32_t 
   return true;
 }
 
+// The rounds of a pointer doubling (goal labels, route fields, route usage): launch_round(r)
+// queues round r, which adds to d_cnt[r] the entries it left open.  Rounds in batches of 4
+// between read-backs of the counters; a round launched behind the one that closed the last
+// entry returns at once.  *launched: the rounds queued; *done: the rounds up to the first
+// that left nothing open, 0 if `cap` rounds did not get there (the caller's error).
+template <class Launch>
+int doubling_rounds(dymu_ctx* c, hipStream_t st, const uint32_t* d_cnt, uint32_t cap,
+                    Launch launch_round, uint32_t* launched, uint32_t* done) {
+  uint32_t h_cnt[std::max(kLabelRounds, kRouteRounds)];
+  if (cap > sizeof h_cnt / sizeof h_cnt[0]) return DYMU_ERR_ARG;
+  uint32_t& n = *launched;
+  for (n = *done = 0; *done == 0 && n < cap;) {
+    const uint32_t r0 = n;
+    for (uint32_t k = 0; k < 4 && n < cap; ++k, ++n) HIPC(c, launch_round(n));
+    HIPC(c, hipStreamSynchronize(st));
+    HIPC(c, hipMemcpy(h_cnt + r0, d_cnt + r0, sizeof(uint32_t) * (n - r0), hipMemcpyDeviceToHost));
+    for (uint32_t r = r0; r < n && *done == 0; ++r)
+      if (h_cnt[r] == 0) *done = r + 1;
+  }
+  return DYMU_OK;
+}
+
 int goal_labels_core(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uint64_t ld,
                      const dymu_seed* seeds, uint32_t n_seeds, uint32_t* d_label, hipStream_t st,
                      uint32_t* rounds) {
@@ -1581,20 +1648,10 @@ int goal_labels_core(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, ui
   HIPC(c, hipEventRecord(c->ev_lab0, st));
   HIPC(c, hipMemsetAsync(c->d_lab_cnt, 0, sizeof(uint32_t) * (kLabelRounds + 1), st));
   HIPC(c, launch_label_init(dT, (int64_t)ld, nx, ny, d_seeds, n_seeds, d_label, st));
-  // rounds in batches of 4 between read-backs of the counters; a round launched
-  // behind the one that resolved the last entry returns at once
+  auto jump = [&](uint32_t r) { return launch_label_jump(d_label, n, c->d_lab_cnt, r, st); };
   uint32_t launched = 0, done = 0;
-  uint32_t h_cnt[kLabelRounds];
-  while (done == 0 && launched < kLabelRounds) {
-    const uint32_t r0 = launched;
-    for (uint32_t k = 0; k < 4 && launched < kLabelRounds; ++k, ++launched)
-      HIPC(c, launch_label_jump(d_label, n, c->d_lab_cnt, launched, st));
-    HIPC(c, hipStreamSynchronize(st));
-    HIPC(c, hipMemcpy(h_cnt + r0, c->d_lab_cnt + r0, sizeof(uint32_t) * (launched - r0),
-                      hipMemcpyDeviceToHost));
-    for (uint32_t r = r0; r < launched && done == 0; ++r)
-      if (h_cnt[r] == 0) done = r + 1;
-  }
+  rc = doubling_rounds(c, st, c->d_lab_cnt, kLabelRounds, jump, &launched, &done);
+  if (rc) return rc;
   HIPC(c, launch_label_strip(d_label, n, st));
   HIPC(c, hipEventRecord(c->ev_lab1, st));
   HIPC(c, hipStreamSynchronize(st));
@@ -1704,7 +1761,7 @@ int dymu_create(dymu_ctx** out, const dymu_opts* opts) {
     if (const char* kv = std::getenv("DYMU_RAISE")) c->raise = std::atoi(kv);
   }
   if (e == hipSuccess) e = hipMalloc(&c->d_counts, sizeof(uint32_t) * 4 * kShards);
-  if (e == hipSuccess) e = hipMalloc(&c->d_scratch, sizeof(unsigned long long) * 8);
+  if (e == hipSuccess) e = hipMalloc(&c->d_scratch, sizeof(unsigned long long) * kScrWords);
   if (e == hipSuccess) e = hipMalloc(&c->d_xchg, sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(c->d_xchg, 0, sizeof(uint32_t));
   if (e == hipSuccess)
@@ -1842,7 +1899,7 @@ int dymu_early_exit_mask(dymu_ctx* c, const double* dF, double* dT, uint32_t nx,
     HIPC(c, hipMalloc(&c->d_band, sizeof(uint64_t) * cap));
     c->band_cap = cap;
   }
-  unsigned long long* cnt = c->d_scratch + 4;
+  unsigned long long* cnt = c->d_scratch + kScrCount;
   HIPC(c, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st));
   HIPC(c, launch_early_mask(dF, dT, (int64_t)ld, nx, ny, t_closed, c->d_band, cnt, cap, st));
   HIPC(c, hipMemcpyAsync(c->h_probe, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -1858,7 +1915,7 @@ int dymu_count_equal(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, ui
   if (!c || !dT || !count || nx == 0 || ny == 0 || ld < nx) return DYMU_ERR_ARG;
   HIPC(c, hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, stream);
-  unsigned long long* cnt = c->d_scratch + 4;
+  unsigned long long* cnt = c->d_scratch + kScrCount;
   HIPC(c, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st));
   HIPC(c, launch_count_equal(dT, (int64_t)ld, nx, ny, value, cnt, nullptr, 0, st));
   HIPC(c, hipMemcpyAsync(c->h_probe, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -1876,7 +1933,7 @@ int dymu_find_equal(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t ny, uin
   int rc = ensure_xfer(c, sizeof(uint64_t) * (cap ? cap : 1));
   if (rc) return rc;
   uint64_t* di = static_cast<uint64_t*>(c->d_xfer);  // written by the kernel in host memory
-  unsigned long long* cnt = c->d_scratch + 4;
+  unsigned long long* cnt = c->d_scratch + kScrCount;
   HIPC(c, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st));
   HIPC(c, launch_count_equal(dT, (int64_t)ld, nx, ny, value, cnt, di, cap, st));
   HIPC(c, hipMemcpyAsync(c->h_probe, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -2257,20 +2314,12 @@ int dymu_route_fields_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_
   HIPC(c, hipMemsetAsync(d_cnt, 0, kRouteCntBytes, st));
   HIPC(c, launch_route_init(ia, d_seeds, n_seeds, st));
   HIPC(c, hipEventRecord(c->ev_route[1], st));
-  // rounds in batches of 4 between read-backs of the counters; a round launched behind
-  // the one that closed the last entry returns at once.  Round r reads buffer r & 1.
+  auto launch_round = [&](uint32_t r) {  // round r reads buffer r & 1
+    return launch_route_round(s[r & 1u], s[(r + 1u) & 1u], n, d_cnt, r, st);
+  };
   uint32_t launched = 0, done = 0;
-  uint32_t h_cnt[kRouteRounds];
-  while (done == 0 && launched < kRouteRounds) {
-    const uint32_t r0 = launched;
-    for (uint32_t k = 0; k < 4 && launched < kRouteRounds; ++k, ++launched)
-      HIPC(c, launch_route_round(s[launched & 1u], s[(launched + 1u) & 1u], n, d_cnt, launched, st));
-    HIPC(c, hipStreamSynchronize(st));
-    HIPC(c, hipMemcpy(h_cnt + r0, d_cnt + r0, sizeof(uint32_t) * (launched - r0),
-                      hipMemcpyDeviceToHost));
-    for (uint32_t r = r0; r < launched && done == 0; ++r)
-      if (h_cnt[r] == 0) done = r + 1;
-  }
+  rc = doubling_rounds(c, st, d_cnt, kRouteRounds, launch_round, &launched, &done);
+  if (rc) return rc;
   HIPC(c, hipEventRecord(c->ev_route[2], st));
   const uint32_t ran = done ? done : launched;
   RouteFinalArgs fa{};
@@ -2304,21 +2353,11 @@ int dymu_route_fields_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_
 }
 
 int dymu_last_route_fields_ms(dymu_ctx* c, double* ms) {
-  if (!c || !ms) return DYMU_ERR_ARG;
-  if (!c->route_timed) return DYMU_ERR_STATE;
-  HIPC(c, hipSetDevice(c->device));
-  return event_ms(c, c->ev_route[0], c->ev_route[3], ms);
+  return total_ms(c, &dymu_ctx::route_timed, &dymu_ctx::ev_route, ms);
 }
 
-int dymu_last_route_fields_stages(dymu_ctx* c, double stage_ms[3]) {
-  if (!c || !stage_ms) return DYMU_ERR_ARG;
-  if (!c->route_timed) return DYMU_ERR_STATE;
-  HIPC(c, hipSetDevice(c->device));
-  for (int k = 0; k < 3; ++k) {
-    const int rc = event_ms(c, c->ev_route[k], c->ev_route[k + 1], &stage_ms[k]);
-    if (rc) return rc;
-  }
-  return DYMU_OK;
+int dymu_last_route_fields_stages(dymu_ctx* c, double out[3]) {
+  return stage_ms(c, &dymu_ctx::route_timed, &dymu_ctx::ev_route, out);
 }
 
 // ---- how much of the map drains through every cell (usage_kernels.hip) ----
@@ -2408,30 +2447,22 @@ int dymu_route_usage_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t
   HIPC(c, launch_usage_init(dT, (int64_t)ld, nx, ny, d_weight, (int64_t)weight_ld, s.sum[0], s.far,
                             st));
   HIPC(c, hipEventRecord(c->ev_usage[1], st));
-  // rounds in batches of 4 between read-backs of the counters, as dymu_route_fields_device
-  // runs them.  Round r reads buffer r & 1.
+  // round r reads buffer r & 1, behind its own time stamp
+  auto launch_round = [&](uint32_t r) {
+    UsageRoundArgs ra{};
+    ra.nx = nx;
+    ra.ny = ny;
+    ra.nsrc = s.next[r & 1u];
+    ra.ndst = s.next[(r + 1u) & 1u];
+    ra.asrc = s.sum[r & 1u];
+    ra.adst = s.sum[(r + 1u) & 1u];
+    ra.far = s.far;
+    const hipError_t e = hipEventRecord(c->ev_usage_round[r], st);
+    return e != hipSuccess ? e : launch_usage_round(ra, d_cnt, r, gather0, st);
+  };
   uint32_t launched = 0, done = 0;
-  uint32_t h_cnt[kRouteRounds];
-  while (done == 0 && launched < kRouteRounds) {
-    const uint32_t r0 = launched;
-    for (uint32_t k = 0; k < 4 && launched < kRouteRounds; ++k, ++launched) {
-      UsageRoundArgs ra{};
-      ra.nx = nx;
-      ra.ny = ny;
-      ra.nsrc = s.next[launched & 1u];
-      ra.ndst = s.next[(launched + 1u) & 1u];
-      ra.asrc = s.sum[launched & 1u];
-      ra.adst = s.sum[(launched + 1u) & 1u];
-      ra.far = s.far;
-      HIPC(c, hipEventRecord(c->ev_usage_round[launched], st));
-      HIPC(c, launch_usage_round(ra, d_cnt, launched, gather0, st));
-    }
-    HIPC(c, hipStreamSynchronize(st));
-    HIPC(c, hipMemcpy(h_cnt + r0, d_cnt + r0, sizeof(uint32_t) * (launched - r0),
-                      hipMemcpyDeviceToHost));
-    for (uint32_t r = r0; r < launched && done == 0; ++r)
-      if (h_cnt[r] == 0) done = r + 1;
-  }
+  rc = doubling_rounds(c, st, d_cnt, kRouteRounds, launch_round, &launched, &done);
+  if (rc) return rc;
   HIPC(c, hipEventRecord(c->ev_usage_round[launched], st));
   c->usage_rounds_timed = launched;
   HIPC(c, hipEventRecord(c->ev_usage[2], st));
@@ -2466,21 +2497,11 @@ int dymu_route_usage_device(dymu_ctx* c, const double* dT, uint32_t nx, uint32_t
 }
 
 int dymu_last_route_usage_ms(dymu_ctx* c, double* ms) {
-  if (!c || !ms) return DYMU_ERR_ARG;
-  if (!c->usage_timed) return DYMU_ERR_STATE;
-  HIPC(c, hipSetDevice(c->device));
-  return event_ms(c, c->ev_usage[0], c->ev_usage[3], ms);
+  return total_ms(c, &dymu_ctx::usage_timed, &dymu_ctx::ev_usage, ms);
 }
 
-int dymu_last_route_usage_stages(dymu_ctx* c, double stage_ms[3]) {
-  if (!c || !stage_ms) return DYMU_ERR_ARG;
-  if (!c->usage_timed) return DYMU_ERR_STATE;
-  HIPC(c, hipSetDevice(c->device));
-  for (int k = 0; k < 3; ++k) {
-    const int rc = event_ms(c, c->ev_usage[k], c->ev_usage[k + 1], &stage_ms[k]);
-    if (rc) return rc;
-  }
-  return DYMU_OK;
+int dymu_last_route_usage_stages(dymu_ctx* c, double out[3]) {
+  return stage_ms(c, &dymu_ctx::usage_timed, &dymu_ctx::ev_usage, out);
 }
 
 int dymu_last_route_usage_round_ms(dymu_ctx* c, double round_ms[32], uint32_t* rounds) {
@@ -2666,7 +2687,7 @@ int dymu_clearance_device(dymu_ctx* c, const double* dF, double* dW, double* dS,
   a.ny = ny;
   bind_list0(c, a);  // a priority kernel (need_keys): keys and histogram
   a.ec = D.a.ec;
-  a.n_obst = c->d_scratch + 4;
+  a.n_obst = c->d_scratch + kScrObst;
   // list 0's smallest key and histogram origin: +0.0, the value of every seed
   hipError_t e = launch_store_u64(prio_minkey(c, 0), 0ull, st);
   if (e == hipSuccess)
@@ -2694,11 +2715,151 @@ int dymu_clearance_device(dymu_ctx* c, const double* dF, double* dW, double* dS,
 // too.  Every state the passes leave is a supersolution (a cell's value was the update of its
 // neighbours when it was written, and they only fell since), so after the freed cells are
 // set to +inf and every cell whose value its current neighbours no longer support followed
-// them (the seeded raise, k_raise<true>, on the domain's plain lists in 16x16 tiles as in
-// resolve_core), what is left bounds the new field from above and the warm start above fills
-// the cone: from the added cells and from the cone's boundary inside the tiles the raise
-// claimed.  The box is the union of what the raise and the passes each claimed.
+// them (run_raise, seeded), what is left bounds the new field from above and the warm start
+// above fills the cone: from the added cells and from the cone's boundary inside the tiles
+// the raise claimed.  The box is the union of what the raise and the passes each claimed.
 namespace {
+// what the stages of a windowed clearance call share
+struct ClearanceCall {
+  const double* dF;  // the mask
+  double* dW;        // the constant speed map
+  double step;
+  int variant;       // the pass kernel (dom_variant): a's tile geometry anticipates its domain
+  MaskSeedArgs a;    // the field (T, ld, nx, ny); list 0 is bound once the pass domain is live
+  MaskWindow win;
+  uint32_t blocks;   // 8 workgroups per CU, as dymu_clearance_device seeds
+  bool added, freed;  // what the count found
+};
+
+// The box {x0, y0, x1, y1}, in tiles, of the first `ntiles` tiles (ntx per row) whose stamp
+// is at least stamp_lo; x1 = 0: none.  Synchronises the stream.
+hipError_t claimed_box(dymu_ctx* c, uint32_t ntiles, uint32_t ntx, uint32_t stamp_lo,
+                       hipStream_t st, uint32_t out[4]) {
+  unsigned long long* dbox = c->d_scratch + kScrBox;
+  hipError_t e = launch_store_u64(dbox, ~0ull, st);
+  if (e == hipSuccess) e = launch_store_u64(dbox + 1, 0ull, st);
+  uint32_t* box32 = reinterpret_cast<uint32_t*>(dbox);
+  if (e == hipSuccess) e = launch_claimed_box(c->d_tile_epoch, ntiles, ntx, stamp_lo, box32, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(c->h_probe, dbox, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) std::memcpy(out, c->h_probe, 4 * sizeof(uint32_t));
+  return e;
+}
+
+// Count first: the new obstacle cells and the freed ones (k.added, k.freed), nothing written.
+// Neither: the field stands, and the call ends here -- the empty box, its time, no domain.
+int clearance_count_window(dymu_ctx* c, ClearanceCall& k, bool edit, hipStream_t st,
+                           uint32_t box[4], dymu_stats* stats) {
+  unsigned long long* cnt = c->d_scratch + kScrObst;  // and kScrFreed behind it
+  hipError_t e = hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), st);
+  if (e == hipSuccess) e = launch_seed_mask_window(k.dF, k.a, k.win, k.blocks, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(c->h_probe, cnt, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail_hip(c, e, "obstacle window count");
+  k.added = c->h_probe[0] != 0ull, k.freed = c->h_probe[1] != 0ull;
+  if (k.freed && !edit) {
+    c->last_error = "clearance update: the window frees an obstacle cell";
+    return DYMU_ERR_STATE;
+  }
+  if (k.added || k.freed) return DYMU_OK;
+  HIPC(c, hipEventRecord(c->ev1, st));
+  double ms = 0.0;
+  const int rc = event_ms(c, c->ev0, c->ev1, &ms);
+  if (rc) return rc;
+  if (box) box[0] = k.win.i0, box[1] = k.win.j0, box[2] = box[3] = 0u;
+  if (stats) {
+    std::memset(stats, 0, sizeof *stats);
+    stats->ms = ms;
+    stats->tile_w = (int)k.a.tw;
+    stats->tile_h = (int)k.a.th;
+    stats->kernel = k.variant;
+  }
+  return DYMU_OK;
+}
+
+// The raise from the window, on a domain of its own (run_raise; its statistics take the words
+// of the count, which was read back), then what it claimed, before the pass domain's claims
+// go to the same stamps: rt = its box {x0, y0, x1, y1} in 16x16 tiles, *raise_lo = its first stamp.
+int clearance_raise(dymu_ctx* c, const ClearanceCall& k, hipStream_t st, uint32_t rt[4],
+                    uint32_t* raise_lo) {
+  const uint32_t ntx16 = (k.a.nx + 15u) / 16u, nty16 = (k.a.ny + 15u) / 16u;
+  int rc = dom_begin(c, k.dW, k.a.T, k.a.nx, k.a.ny, (uint64_t)k.a.ld, 0, 0, -1, -1, st,
+                     /*cold=*/false, /*need_keys=*/true);
+  if (rc) return rc;
+  *raise_lo = c->dom.eb + 1u;
+  RaiseArgs ra{};
+  ra.F = k.dF;  // the mask; the speed is the constant
+  ra.c = k.step;
+  const uint32_t win[4] = {k.win.i0, k.win.j0, k.win.i1, k.win.j1};
+  rc = run_raise(c, ra, /*seeded=*/true, kScrEditStats, win, st);
+  if (rc) return rc;
+  const hipError_t e = claimed_box(c, ntx16 * nty16, ntx16, *raise_lo, st, rt);
+  if (e == hipSuccess) return DYMU_OK;
+  dom_retire(c);
+  return fail_hip(c, e, "raise box");
+}
+
+// List 0 of the live pass domain (bound in k.a): the new obstacle cells, and after a raise
+// the cone's boundary inside the tiles it claimed (rt, raise_lo: clearance_raise's).
+hipError_t clearance_seed(dymu_ctx* c, ClearanceCall& k, const uint32_t rt[4], uint32_t raise_lo,
+                          hipStream_t st) {
+  auto& D = c->dom;
+  MaskSeedArgs& a = k.a;
+  // the edge columns belong to whatever domain ran last: from the old field (after the raise
+  // wrote it), then the seeding kernel adds the new cells'
+  hipError_t e = !D.a.ec ? hipSuccess : launch_ec_rebuild(a.T, (uint64_t)a.ld, a.nx, a.ny, D.a.ec,
+                                                          (uint32_t)D.a.ntx, 0, D.ntiles, st);
+  if (!k.freed) {  // list 0's smallest key and histogram origin: +0.0, the value of every seed
+    if (e == hipSuccess) e = launch_store_u64(prio_minkey(c, 0), 0ull, st);
+    if (e == hipSuccess)
+      e = launch_store_u64(reinterpret_cast<unsigned long long*>(prio_base(c, 0)), 0ull, st);
+    if (e == hipSuccess) e = launch_seed_mask_window(k.dF, a, k.win, k.blocks, st);
+    return e;
+  }
+  // The cone's boundary joins the added cells in list 0, keyed with the boundary's values:
+  // the keys first (they read the raise's stamps), then the claims.  theta: the smallest
+  // key queued, +0.0 with an added cell; the histogram is binned from the final keys, as
+  // after the single-goal raise (resolve_core).
+  unsigned long long* theta = c->d_scratch + kScrTheta;
+  uint32_t* hist0 = a.hist;
+  a.hist = nullptr;
+  ConeArgs cone{};
+  cone.S = a.T;
+  cone.F = k.dF;
+  cone.ld = a.ld;
+  cone.nx = a.nx;
+  cone.ny = a.ny;
+  cone.ntx16 = (a.nx + 15u) / 16u;
+  cone.bx0 = rt[0], cone.by0 = rt[1];
+  cone.nbx = rt[2] > rt[0] ? rt[2] - rt[0] : 0u;
+  cone.nby = rt[3] > rt[1] ? rt[3] - rt[1] : 0u;
+  // dom_begin restarted the epochs (its wrap guard zeroed every stamp, the raise's too):
+  // every tile of the raise's box is scanned then.  The box was reduced before that, and
+  // a tile the raise did not claim holds the old solve's stop at the level: a visit of it
+  // writes values above the level at most, inside the box.
+  cone.stamp_lo = D.eb < raise_lo ? 0u : raise_lo;
+  cone.tw = a.tw, cone.th = a.th, cone.ntx = a.ntx;
+  cone.list = a.list;
+  cone.counts = a.counts;
+  cone.shard_cap = a.shard_cap;
+  cone.tile_epoch = a.tile_epoch;
+  cone.epoch = a.epoch;
+  cone.keys = a.keys;
+  cone.theta_bits = theta;
+  if (e == hipSuccess) e = launch_store_u64(theta, k.added ? 0ull : 0x7FF0000000000000ull, st);
+  if (e == hipSuccess) e = launch_cone_keys(cone, k.blocks, st);
+  if (e == hipSuccess && k.added) e = launch_seed_mask_window(k.dF, a, k.win, k.blocks, st);
+  if (e == hipSuccess) e = launch_cone_queue(cone, st);
+  if (e == hipSuccess) e = launch_theta_state(theta, prio_minkey(c, 0), prio_base(c, 0), st);
+  if (e == hipSuccess)
+    e = launch_rehist(D.lists[0], D.counts[0], D.ntiles, prio_keys(c, 0), prio_base(c, 0),
+                      prio_delta(c), hist0, c->d_hist + (uint64_t)4 * kShards * kBins, st);
+  return e;
+}
+
+// count -> raise (if cells were freed) -> pass domain -> seed -> passes -> box -> join
 int clearance_window(dymu_ctx* c, const double* dF, double* dW, double* dS, uint32_t nx,
                      uint32_t ny, uint64_t ld, double step, uint32_t i0, uint32_t j0, uint32_t w,
                      uint32_t h, void* stream, uint32_t box[4], dymu_stats* stats, bool edit) {
@@ -2710,17 +2871,17 @@ int clearance_window(dymu_ctx* c, const double* dF, double* dW, double* dS, uint
   HIPC(c, hipSetDevice(c->device));
   hipStream_t st = pick_stream(c, stream);
   HIPC(c, hipEventRecord(c->ev0, st));
-  const int variant = dom_variant(c, nx, ny, /*need_keys=*/true);
-  MaskSeedArgs a{};
+  ClearanceCall k{dF, dW, step, dom_variant(c, nx, ny, /*need_keys=*/true)};
+  MaskSeedArgs& a = k.a;
   a.T = dS;
   a.ld = (int64_t)ld;
   a.nx = nx;
   a.ny = ny;
-  a.tw = (uint32_t)tile_w(variant);
-  a.th = (uint32_t)tile_h(variant);
+  a.tw = (uint32_t)tile_w(k.variant);
+  a.th = (uint32_t)tile_h(k.variant);
   a.ntx = (nx + a.tw - 1u) / a.tw;
-  a.n_obst = c->d_scratch + 4;
-  MaskWindow win{};
+  a.n_obst = c->d_scratch + kScrObst;
+  MaskWindow& win = k.win;
   win.i0 = i0;
   win.j0 = j0;
   win.i1 = (uint32_t)std::min<uint64_t>((uint64_t)i0 + w, nx);
@@ -2729,124 +2890,13 @@ int clearance_window(dymu_ctx* c, const double* dF, double* dW, double* dS, uint
   win.ty0 = j0 / a.th;
   win.ntwx = (win.i1 - 1u) / a.tw - win.tx0 + 1u;
   win.ntwy = (win.j1 - 1u) / a.th - win.ty0 + 1u;
-  win.n_freed = c->d_scratch + 5;
+  win.n_freed = c->d_scratch + kScrFreed;
   if ((uint64_t)win.ntwx * win.ntwy >= (1ull << 31)) return DYMU_ERR_ARG;  // as dom_begin's tiles
-  const uint32_t blocks = (uint32_t)c->cu_count * 8u;
-  // count first: the new obstacle cells and the freed ones, nothing written
-  hipError_t e = hipMemsetAsync(c->d_scratch + 4, 0, 2 * sizeof(unsigned long long), st);
-  if (e == hipSuccess) e = launch_seed_mask_window(dF, a, win, blocks, st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(c->h_probe, c->d_scratch + 4, 2 * sizeof(unsigned long long),
-                       hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail_hip(c, e, "obstacle window count");
-  const bool added = c->h_probe[0] != 0ull, freed = c->h_probe[1] != 0ull;
-  if (freed && !edit) {
-    c->last_error = "clearance update: the window frees an obstacle cell";
-    return DYMU_ERR_STATE;
-  }
-  if (!added && !freed) {  // nothing new: the field stands, and no domain to finish
-    HIPC(c, hipEventRecord(c->ev1, st));
-    double ms = 0.0;
-    const int rc = event_ms(c, c->ev0, c->ev1, &ms);
-    if (rc) return rc;
-    if (box) box[0] = i0, box[1] = j0, box[2] = box[3] = 0u;
-    if (stats) {
-      std::memset(stats, 0, sizeof *stats);
-      stats->ms = ms;
-      stats->tile_w = (int)a.tw;
-      stats->tile_h = (int)a.th;
-      stats->kernel = variant;
-    }
-    return DYMU_OK;
-  }
-  // The raise, on a domain of its own: its lists as plain lists of 16x16 tiles whatever the
-  // pass kernel's tile is, from the tiles that meet the window, until a pass queues nothing.
-  // rt: the tiles it claimed, {x0, y0, x1, y1} in raise tiles; stamps from raise_lo on.
-  const uint32_t ntx16 = (nx + 15u) / 16u, nty16 = (ny + 15u) / 16u;
-  uint32_t rt[4] = {0u, 0u, 0u, 0u}, raise_lo = 0u;
-  uint32_t* dbox = reinterpret_cast<uint32_t*>(c->d_scratch + 2);
-  if (freed) {
-    int rc = dom_begin(c, dW, dS, nx, ny, ld, 0, 0, -1, -1, st, /*cold=*/false, /*need_keys=*/true);
-    if (rc) return rc;
-    auto& D = c->dom;
-    UpdateArgs u{};
-    bind_list0(c, u);
-    u.tw = u.th = 16;
-    u.ntx = ntx16;
-    u.keys = nullptr;  // no keys, no histogram: the raise front has no order
-    u.hist = nullptr;
-    raise_lo = u.epoch;
-    unsigned long long* rst = c->d_scratch + 4;  // [visits, cells]; the count was read above
-    e = launch_seed_window(u, win.i0, win.j0, win.i1, win.j1, st);
-    if (e == hipSuccess) e = hipMemsetAsync(rst, 0, 2 * sizeof(unsigned long long), st);
-    if (e != hipSuccess) {
-      dom_retire(c);
-      return fail_hip(c, e, "raise seeding");
-    }
-    RaiseArgs ra{};
-    ra.T = dS;
-    ra.F = dF;  // the mask; the speed is the constant
-    ra.c = step;
-    ra.ld = (int64_t)ld;
-    ra.nx = nx;
-    ra.ny = ny;
-    ra.ntx = ntx16;
-    ra.nty = nty16;
-    ra.shard_cap = D.ntiles;
-    ra.tile_epoch = c->d_tile_epoch;
-    ra.tol = 1e-13;
-    ra.stats = rst;
-    uint64_t K = 4, raise_passes = 0;
-    for (;;) {
-      for (uint64_t k = 0; k < K; ++k, ++D.p) {
-        const uint64_t p = D.p;
-        if (p > D.max_passes) {
-          c->last_error = "raise: pass cap reached";
-          dom_retire(c);
-          return DYMU_ERR_NOT_CONVERGED;
-        }
-        ra.list_in = D.lists[p % 3];
-        ra.count_in = D.counts[p % 3];
-        ra.list_out = D.lists[(p + 1) % 3];
-        ra.count_out = D.counts[(p + 1) % 3];
-        ra.count_clear = D.counts[(p + 2) % 3];
-        ra.epoch = D.eb + (uint32_t)p + 2u;
-        e = launch_raise_seeded(ra, c->cu_count * 2, st);
-        if (e != hipSuccess) {
-          dom_retire(c);
-          return fail_hip(c, e, "raise pass");
-        }
-        ++raise_passes;
-      }
-      uint64_t pending = 0;
-      rc = dom_pending(c, st, &pending);
-      if (rc) {
-        dom_retire(c);
-        return rc;
-      }
-      if (pending == 0) break;
-      K = std::min<uint64_t>(K * 2, 64);
-    }
-    // what the raise claimed, before the pass domain's claims go to the same stamps
-    unsigned long long hr[2];
-    e = launch_store_u64(c->d_scratch + 2, ~0ull, st);
-    if (e == hipSuccess) e = launch_store_u64(c->d_scratch + 3, 0ull, st);
-    if (e == hipSuccess)
-      e = launch_claimed_box(c->d_tile_epoch, ntx16 * nty16, ntx16, raise_lo, dbox, st);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(c->h_probe, dbox, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipMemcpy(hr, rst, sizeof hr, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-      dom_retire(c);
-      return fail_hip(c, e, "raise box");
-    }
-    std::memcpy(rt, c->h_probe, sizeof rt);
-    c->last_update[0] = raise_passes;
-    c->last_update[1] = hr[0];
-    c->last_update[2] = hr[1];
-  }
+  k.blocks = (uint32_t)c->cu_count * 8u;
+  int rc = clearance_count_window(c, k, edit, st, box, stats);
+  if (rc || (!k.added && !k.freed)) return rc;
+  uint32_t rt[4] = {0u, 0u, 0u, 0u}, raise_lo = 0u;  // no raise: an empty box
+  if (k.freed && (rc = clearance_raise(c, k, st, rt, &raise_lo)) != DYMU_OK) return rc;
   // A per-pass target of one tile: every pass relaxes the lowest non-empty key bin only
   // (pass_scan's b*), so the tiles are visited in key order and none whose key lies above
   // the bin of the level is visited before the stop test sees it.  With the solves' target
@@ -2856,7 +2906,7 @@ int clearance_window(dymu_ctx* c, const double* dF, double* dW, double* dS, uint
   // of 13 tiles instead of the 4 tiles within the level's reach plus their ring).
   const uint32_t saved_target = c->prio_target;
   c->prio_target = 1u;
-  int rc = dom_begin(c, dW, dS, nx, ny, ld, 0, 0, -1, -1, st, /*cold=*/false, /*need_keys=*/true);
+  rc = dom_begin(c, dW, dS, nx, ny, ld, 0, 0, -1, -1, st, /*cold=*/false, /*need_keys=*/true);
   c->prio_target = saved_target;
   if (rc) return rc;
   auto& D = c->dom;
@@ -2864,54 +2914,7 @@ int clearance_window(dymu_ctx* c, const double* dF, double* dW, double* dS, uint
   a.ec = D.a.ec;
   win.seed = 1u;
   const uint32_t eb = D.eb, ntiles = D.ntiles, ntx = (uint32_t)D.a.ntx;
-  // the edge columns belong to whatever domain ran last: from the old field (after the raise
-  // wrote it), then the seeding kernel adds the new cells'
-  e = D.a.ec ? launch_ec_rebuild(dS, ld, nx, ny, D.a.ec, ntx, 0, ntiles, st) : hipSuccess;
-  if (!freed) {  // list 0's smallest key and histogram origin: +0.0, the value of every seed
-    if (e == hipSuccess) e = launch_store_u64(prio_minkey(c, 0), 0ull, st);
-    if (e == hipSuccess)
-      e = launch_store_u64(reinterpret_cast<unsigned long long*>(prio_base(c, 0)), 0ull, st);
-    if (e == hipSuccess) e = launch_seed_mask_window(dF, a, win, blocks, st);
-  } else {
-    // The cone's boundary joins the added cells in list 0, keyed with the boundary's values:
-    // the keys first (they read the raise's stamps), then the claims.  theta: the smallest
-    // key queued, +0.0 with an added cell; the histogram is binned from the final keys, as
-    // after the single-goal raise (resolve_core).
-    unsigned long long* theta = c->d_scratch;
-    uint32_t* hist0 = a.hist;
-    a.hist = nullptr;
-    ConeArgs k{};
-    k.S = dS;
-    k.F = dF;
-    k.ld = (int64_t)ld;
-    k.nx = nx;
-    k.ny = ny;
-    k.ntx16 = ntx16;
-    k.bx0 = rt[0], k.by0 = rt[1];
-    k.nbx = rt[2] > rt[0] ? rt[2] - rt[0] : 0u;
-    k.nby = rt[3] > rt[1] ? rt[3] - rt[1] : 0u;
-    // dom_begin restarted the epochs (its wrap guard zeroed every stamp, the raise's too):
-    // every tile of the raise's box is scanned then.  The box was reduced before that, and
-    // a tile the raise did not claim holds the old solve's stop at the level: a visit of it
-    // writes values above the level at most, inside the box.
-    k.stamp_lo = D.eb < raise_lo ? 0u : raise_lo;
-    k.tw = a.tw, k.th = a.th, k.ntx = a.ntx;
-    k.list = a.list;
-    k.counts = a.counts;
-    k.shard_cap = a.shard_cap;
-    k.tile_epoch = a.tile_epoch;
-    k.epoch = a.epoch;
-    k.keys = a.keys;
-    k.theta_bits = theta;
-    if (e == hipSuccess) e = launch_store_u64(theta, added ? 0ull : 0x7FF0000000000000ull, st);
-    if (e == hipSuccess) e = launch_cone_keys(k, blocks, st);
-    if (e == hipSuccess && added) e = launch_seed_mask_window(dF, a, win, blocks, st);
-    if (e == hipSuccess) e = launch_cone_queue(k, st);
-    if (e == hipSuccess) e = launch_theta_state(theta, prio_minkey(c, 0), prio_base(c, 0), st);
-    if (e == hipSuccess)
-      e = launch_rehist(D.lists[0], D.counts[0], D.ntiles, prio_keys(c, 0), prio_base(c, 0),
-                        prio_delta(c), hist0, c->d_hist + (uint64_t)4 * kShards * kBins, st);
-  }
+  hipError_t e = clearance_seed(c, k, rt, raise_lo, st);
   if (e != hipSuccess) {
     dom_retire(c);
     return fail_hip(c, e, "obstacle window seeding");
@@ -2920,16 +2923,10 @@ int clearance_window(dymu_ctx* c, const double* dF, double* dW, double* dS, uint
   if (rc) return rc;
   // every tile a list of this domain held carries a stamp above eb; the stamps are left to
   // the next domain, whose epochs lie above them
-  e = launch_store_u64(c->d_scratch + 2, ~0ull, st);
-  if (e == hipSuccess) e = launch_store_u64(c->d_scratch + 3, 0ull, st);
-  if (e == hipSuccess) e = launch_claimed_box(c->d_tile_epoch, ntiles, ntx, eb + 1u, dbox, st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(c->h_probe, dbox, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  uint32_t t[4];
+  e = claimed_box(c, ntiles, ntx, eb + 1u, st, t);
   if (e != hipSuccess) return fail_hip(c, e, "claimed-tile box");
   if (box) {
-    uint32_t t[4];
-    std::memcpy(t, c->h_probe, sizeof t);
     // in cells: the pass domain's tiles (none when nothing was queued), then the raise's
     uint64_t b[4] = {~0ull, ~0ull, 0ull, 0ull};
     auto join = [&](const uint32_t q[4], uint32_t tw, uint32_t th) {
